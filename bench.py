@@ -40,7 +40,6 @@ The JSON line also carries
   ranks_seen / backend / allgather_us / per_rank_ms / slowest_rank / fastest_rank / scaling_efficiency_vs -- what
                    torch.distributed reports, the HIP-event time of the embedding all-gather, every rank's own step time,
                    N x the committed 1-GPU value for reference;
-  frontend_A, cosine_mfma, stage_kernels, ingest_resample, ragged -- the other hand-written kernels / workloads on their own;
   cpu_baseline  -- the CPU oracle (NumPy/torch-CPU restatement of the reference, kind "port") timed in a
                    fresh child process on rank 0, N = 1 only: the per-utterance chain on single-threaded workers at
                    pool sizes around the container's CPU quota (`value` = the best; every worker warmed before the clock
@@ -48,6 +47,12 @@ The JSON line also carries
                    variants per stage;
   parity        -- the PRODUCTION path (libsvk end to end) vs the oracle on that sample: embeddings, scores, the EER on
                    both sides (eer_equal) + the EER of the 4 874 x 40 matrix through host sklearn, svk_roc_eer and the oracle.
+Rank 0 also writes one JSON line to STDERR, just before the result line: the side benches (host_fed, micro_batch_breakdown,
+frontend_A, cosine_mfma, stage_kernels, ingest_resample, ragged -- the other hand-written kernels / workloads on their own)
+and `notes`, the prose that explains the result's fields, keyed by their path in it ("roofline.note").
+
+--dump-outputs DIR writes what the timed path computed in its last step (float32 .npy): scores.npy, the 4 874 x 40 score
+matrix, and embeddings.npy, the [clips, 128] embeddings, or a fixed sample of 65 536 of them for a larger corpus.
 """
 import argparse
 import json
@@ -88,6 +93,11 @@ NETWORK_KERNELS = (
 N_CORPUS = 148642                # VoxCeleb1 dev utterances (README.md:5-7) = BASELINE configs[4]
 N_TEST, N_TEST_SPK = 4874, 40    # VoxCeleb1 verification split (README.md:4-7)
 UTTS_PER_SPK = 123
+DUMP_MAX_ROWS = 65536            # 32 MiB of float32 embeddings: with the score matrix the dump stays under 64 MB
+# The result line on stdout carries the flagship measurement.  The side benches and the prose that explains fields go to
+# stderr as a second JSON line: with them the line grew past 21 kB, more than a harness reading it accepted.
+SIDE_ENTRIES = ("host_fed", "micro_batch_breakdown", "frontend_A", "cosine_mfma", "stage_kernels", "ingest_resample", "ragged")
+NOTE_KEYS = ("note", "traffic_note")
 
 
 def parse(argv=None):
@@ -122,8 +132,15 @@ def parse(argv=None):
                     help="gloo: rehearse N ranks on ONE GPU (RCCL refuses two ranks on a device)")
     ap.add_argument("--selftest", action="store_true",
                     help="launcher / collective logic only, on CPU with gloo (tests/test_distributed_cpu.py)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as float32 .npy files: DIR/scores.npy = "
+                         "the score matrix, DIR/embeddings.npy = the embeddings of every clip, or of %d clips drawn with a "
+                         "fixed seed (in clip order) when the corpus is larger" % DUMP_MAX_ROWS)
     ap.add_argument("--cpu-child", default=None, help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # --------------------------------------------------------------------------------------------------
@@ -798,6 +815,43 @@ def run_cpu_baseline(sample_pcm, crops, state, preemph, cmvn, use_vad):
     return rec, emb
 
 
+def dump_outputs(out_dir, full, scores):
+    """--dump-outputs: what the timed path handed back in its last step, as float32 .npy files (the inputs are seeded, so
+    two builds run with the same arguments can be compared file by file).  A directory without a .gitignore gets one that
+    names these files, so a dump inside a checkout leaves it clean."""
+    emb = full.cpu().numpy()
+    if emb.shape[0] > DUMP_MAX_ROWS:
+        emb = emb[np.sort(np.random.default_rng(0).choice(emb.shape[0], DUMP_MAX_ROWS, replace=False))]
+    arrays = {"scores": scores.cpu().numpy(), "embeddings": emb}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+    ignore = os.path.join(out_dir, ".gitignore")
+    if not os.path.exists(ignore):
+        with open(ignore, "w") as fh:
+            fh.write("".join(name + ".npy\n" for name in arrays) + ".gitignore\n")
+
+
+def split_record(result):
+    """(result line, detail record): the side entries and every prose field (NOTE_KEYS, kept under their key path, e.g.
+    "roofline.note") move from the result to the detail record."""
+    notes = {}
+
+    def strip(rec, path):
+        out = {}
+        for k, v in rec.items():
+            if k in NOTE_KEYS:
+                notes[path + k] = v
+            else:
+                out[k] = strip(v, path + k + ".") if isinstance(v, dict) else v
+        return out
+
+    line = strip({k: v for k, v in result.items() if k not in SIDE_ENTRIES}, "")
+    detail = {k: result[k] for k in SIDE_ENTRIES if k in result}
+    detail["notes"] = notes
+    return line, detail
+
+
 # --------------------------------------------------------------------------------------------------
 def main():
     args = parse()
@@ -985,6 +1039,8 @@ def main():
         per_rank_ms = [float(t.item()) / args.steps * 1e3 for t in every]
         dt = max(float(t.item()) for t in every)           # ... and the max over ranks is the job's
     bad = int(pipe.bad_clips.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, full, scores)
 
     result = None
     if rank == 0:
@@ -1254,7 +1310,10 @@ def main():
                 "cpu_model": rec["cpu_model"], "os_cpu_count": rec["os_cpu_count"], "versions": rec["versions"],
                 "variants": rec["stages"], "child_wall_s": rec["wall_s"]}
     if rank == 0:
-        print(json.dumps(result))
+        line, detail = split_record(result)
+        sys.stderr.write(json.dumps(detail) + "\n")
+        sys.stderr.flush()
+        print(json.dumps(line))
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

@@ -1973,14 +1973,19 @@ def _bench_line(args, timeout=900):
     return json.loads(lines[0])
 
 
-def test_bench_two_ranks_share_one_gpu():
+def test_bench_two_ranks_share_one_gpu(tmp_path):
     """The N > 1 path on the device: `bench.py --gpus 2 --backend gloo` starts two rank processes on this one GPU
     (RCCL refuses two ranks on a device, so the all-gather goes through gloo / host memory; everything else is the
     code the 8-GPU run executes): contiguous shards, padded gather, every rank scores, rank 0 reports.  The sharded
-    run must report two ranks and give the SAME scores-derived numbers as the one-rank run."""
+    run must report two ranks and give the SAME scores-derived numbers as the one-rank run, and --dump-outputs must
+    hand back the same arrays from both."""
     common = ["--corpus", "5001", "--micro-batch", "1024", "--steps", "1", "--warmup", "1", "--no-extras"]
-    two = _bench_line(["--gpus", "2", "--backend", "gloo"] + common)
-    one = _bench_line(common)
+    two = _bench_line(["--gpus", "2", "--backend", "gloo", "--dump-outputs", str(tmp_path / "two")] + common)
+    one = _bench_line(["--dump-outputs", str(tmp_path / "one")] + common)
+    for name, shape in (("embeddings", (5001, 128)), ("scores", (4874, 40))):
+        got_one, got_two = np.load(tmp_path / "one" / (name + ".npy")), np.load(tmp_path / "two" / (name + ".npy"))
+        assert got_one.shape == shape and got_one.dtype == np.float32 and np.isfinite(got_one).all(), name
+        assert np.array_equal(got_one, got_two), name
     assert two["ranks_seen"] == 2 and two["n_gpus"] == 2 and two["backend"] == "gloo" and two["scaling"] == "strong"
     assert two["config"]["corpus_clips"] == one["config"]["corpus_clips"] == 5001
     assert two["config"]["clips_per_rank"] == 2501 and one["config"]["clips_per_rank"] == 5001

@@ -468,3 +468,45 @@ def test_cube_ring_runs_every_clip_once_in_bounded_memory():
     ring.finish()
     assert torch.equal(emb, want)
     assert launches == [4] * 8 + [2] and ring.done == ring.at == n
+
+
+def test_bench_result_line_and_detail_record():
+    """bench.py's result line stays small enough for a harness to parse (round 4's full record, 21.5 kB, was not): the side
+    benches and the prose fields go to the detail record, and the two together hold everything the record held."""
+    import json
+    import bench
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rec = json.load(open(os.path.join(repo, "profiles", "r04_bench.json")))
+    line, detail = bench.split_record(rec)
+    assert len(json.dumps(line)) < 16000 and not set(line) & set(bench.SIDE_ENTRIES)
+    assert set(detail) == set(bench.SIDE_ENTRIES) | {"notes"}
+    assert detail["notes"]["roofline.note"] == rec["roofline"]["note"] and detail["notes"]["eer.note"] == rec["eer"]["note"]
+    rebuilt = dict(line, **{k: detail[k] for k in bench.SIDE_ENTRIES})
+    for path, text in detail["notes"].items():
+        *parents, key = path.split(".")
+        node = rebuilt
+        for p in parents:
+            node = node[p]
+        node[key] = text
+    assert rebuilt == rec
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: float32 .npy files of what the timed step returned, at most 64 MB; a corpus larger than
+    DUMP_MAX_ROWS is sampled with a fixed seed, the same rows every run."""
+    import bench
+    g = torch.Generator().manual_seed(3)
+    scores = torch.randn((4874, 40), generator=g, dtype=torch.float32)
+    small = torch.randn((5001, 128), generator=g, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "small"), small, scores)
+    np.testing.assert_array_equal(np.load(tmp_path / "small" / "embeddings.npy"), small.numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / "small" / "scores.npy"), scores.numpy())
+    big = torch.arange(148642, dtype=torch.float32)[:, None].repeat(1, 128)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big, scores)
+    a, b = np.load(tmp_path / "a" / "embeddings.npy"), np.load(tmp_path / "b" / "embeddings.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_ROWS, 128) and np.array_equal(a, b)
+    rows = a[:, 0]
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, np.repeat(rows[:, None], 128, axis=1))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < 64 * 2**20
+    assert sorted(open(tmp_path / "a" / ".gitignore").read().split()) == [".gitignore", "embeddings.npy", "scores.npy"]
