@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SVK_VERSION 111 /* 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
+#define SVK_VERSION 112 /* 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
 
 typedef enum svk_status {
   SVK_OK = 0,
@@ -277,6 +277,25 @@ int svk_c3d2_stage1(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t ma
                     const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, const void* d_w1blk,
                     const float* d_bias1, const float* d_slope1, const void* d_w2blk, const float* d_bias2,
                     const float* d_slope2, int32_t flags, float* d_out);
+
+/* The same first block for the three-channel model C3D2(n, 3) (constants.DERIVATIVE = True: train.py:197-205), replacing
+ * utils.py:325-348 (FeatureCube3C: static, delta and delta-delta features cropped into a (3, 20, 80, 40) cube) and
+ * model.py:110-117 + :141-150 with conv1_1 = Conv3d(3, 16, (3,1,5)).  Same arguments, checks and output as svk_c3d2_stage1 except:
+ *   d_feat   [n_utt][3][max_frames][40] f32, channel-planar (channel 0 static, 1 delta, 2 delta-delta; FeatureCube3C's transpose).
+ *            A (n, 3, 20, 80, 40) cube tensor is this layout with max_frames = 1 600 and crop starts 0, 80, ... 1 520.  The 20
+ *            crop starts of a cube apply to all three channels; a start outside the clip -> zero rows, as for svk_c3d2_stage1
+ *   d_w1blk  [3 ch][2][64][8 halves]: conv1_1 as three K = 32 blocks, one per input channel ch, each laid out as
+ *            svk_c3d2_stage1's d_w1blk: tap t = 8 (kk & 1) + e of channel ch (t = 5 kd + kw; t = 15 is a zero pad), block 0 = H
+ *            for every kk, block 1 = L for kk < 2 and 0 above.  (45 taps padded to 48: taps 16 ch + 15 are the pads)
+ *   d_w2blk  as svk_c3d2_stage1 (conv1_2 is the same layer)
+ * Half-pair domain as svk_c3d2_stage1: every feature value finite and below 65 504 in magnitude, an absolute floor of 2^-25.
+ * Returns SVK_ERR_BAD_ARG (NULL buffer, misalignment, bad flags, negative size, too many cubes), SVK_ERR_UNSUPPORTED (geometry
+ * other than 3 x 20 x 80 x 40, or a device with less LDS than svk_c3d2_stage1_c3_lds_bytes() + 64), SVK_ERR_HIP. */
+size_t svk_c3d2_stage1_c3_lds_bytes(void);
+int svk_c3d2_stage1_c3(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
+                       const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, const void* d_w1blk,
+                       const float* d_bias1, const float* d_slope1, const void* d_w2blk, const float* d_bias2,
+                       const float* d_slope2, int32_t flags, float* d_out);
 
 /* The second block, model.py:119-124 + :151-158: conv2_1 (16 -> 32, kernel (3,1,4)) -> BN -> PReLU -> conv2_2
  * (32 -> 32, kernel (3,8,1), stride (1,2,1)) -> BN -> PReLU -> MaxPool3d((1,1,2)), two kernels on v_mfma_f32_16x16x32_f16

@@ -145,6 +145,14 @@ __device__ __forceinline__ void dma_patch_w(const Stage1Params& p, ItemPos it, i
       patch_piece_issue(p, pc, lane);
     }
 }
+// the same for the item's feature matrix `plane` of a layout with several per cube: channel c of cube u is plane 3 u + c in the
+// three-channel layout [n][3][max_frames][40]
+__device__ __forceinline__ void dma_patch_plane(const Stage1Params& p, ItemPos it, int64_t plane, int starts_v, int pair, int lane,
+                                                float* patch) {
+  Stage1Params q = p;
+  q.feat = p.feat + (plane - it.u) * ((int64_t)p.max_frames * NCOEF);
+  dma_patch_w(q, it, starts_v, pair, lane, patch);
+}
 
 // prelu for 0 <= slope <= 1 straight off MFMA accumulators: fmaxf() on a value the compiler cannot prove canonical costs a
 // third instruction (v_max x, x in front of the real one) and the product is one v_mul per value; written as vectors it is one
@@ -227,7 +235,14 @@ __device__ __forceinline__ float max_with_lane_xor1(float x) {
   return d;
 }
 
-template <bool SLOPE01>
+// The three-channel first block (svk_c3d2_stage1_c3; utils.FeatureCube3C, model.py:110 with num_channels = 3) is the same kernel
+// with NCH = 3: feature rows [n][3][max_frames][40], conv1_1's K = 45 taps as three K = 32 blocks [h | l] of one channel's 15 taps
+// + a zero tap each (six MFMAs per tile instead of two), the accumulators of a wave's 13 tiles kept in registers across the three
+// channel passes.  Channel 0 comes through the patch buffer as before (fetched inside the previous item's conv1_2); channels 1
+// and 2 are fetched at the top of the item into the act1 tile, which is free until conv1_1's epilogue writes it, while channel 0
+// is multiplied.  conv1_2, the pool and the output layout are the one-channel kernel's.  (NCH = 1 is the code as it was: every
+// NCH = 3 step is under `if constexpr`.)
+template <bool SLOPE01, int NCH = 1>
 __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p) {
   extern __shared__ __attribute__((aligned(16))) float smem_c3d2[];
   unsigned* const act = reinterpret_cast<unsigned*>(smem_c3d2);   // [HACT_WORDS]
@@ -254,6 +269,7 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
   }
 
   int starts = 0;
+  int starts_cur = 0;   // NCH = 3: the current item's crop starts (`starts` is already the next item's by the top of the loop)
   __shared__ int q_item3;
   int item = blockIdx.x, item1 = item + (int)gridDim.x, item2 = item1 + (int)gridDim.x;
   ItemPos cur = ItemPos::of(item), nx = ItemPos::of(item1), nx2 = ItemPos::of(item2);
@@ -281,9 +297,37 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
       if (k % 3 < 2 || lane < 32) *reinterpret_cast<u32x4*>(patch + w) = o;
     }
   };
+  // (the same for a patch at `buf`: NCH = 3's channels 1 and 2, staged in the act1 tile; a separate lambda, so that the one-channel
+  // kernel's code stays what it was)
+  auto convert_own_at = [&](float* buf) {
+    f32x4 v[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      const int w = (pair + 4 * (k / 3)) * (NFRAME * WPW) + 256 * (k % 3) + 4 * lane;
+      if (k % 3 < 2 || lane < 32) v[k] = *reinterpret_cast<const f32x4*>(buf + w);
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      const int w = (pair + 4 * (k / 3)) * (NFRAME * WPW) + 256 * (k % 3) + 4 * lane;
+      unsigned h0, l0, h1, l1;
+      split2(__builtin_shufflevector(v[k], v[k], 0, 1), h0, l0);
+      split2(__builtin_shufflevector(v[k], v[k], 2, 3), h1, l1);
+      u32x4 o;   // word = the value's own pair: low half h, high half l
+      o[0] = __builtin_amdgcn_perm(l0, h0, 0x05040100u);
+      o[1] = __builtin_amdgcn_perm(l0, h0, 0x07060302u);
+      o[2] = __builtin_amdgcn_perm(l1, h1, 0x05040100u);
+      o[3] = __builtin_amdgcn_perm(l1, h1, 0x07060302u);
+      if (k % 3 < 2 || lane < 32) *reinterpret_cast<u32x4*>(buf + w) = o;
+    }
+  };
   if (item < n_items) {
     starts = fetch_starts(p, cur, lane);
-    if (part == 0) dma_patch_w(p, cur, starts, pair, lane, patch);
+    if constexpr (NCH == 1) {
+      if (part == 0) dma_patch_w(p, cur, starts, pair, lane, patch);
+    } else {
+      if (part == 0) dma_patch_plane(p, cur, (int64_t)NCH * cur.u, starts, pair, lane, patch);
+      starts_cur = starts;
+    }
     if (item1 < n_items) starts = fetch_starts(p, nx, lane);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -295,7 +339,7 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
     if (threadIdx.x == 0 && p.queue) q_ticket = atomicAdd(p.queue, 1u);
 
     // ---- (1) conv1_1 + PReLU -> act1 as (h, l): 100 tiles of 16 pixels, tile tt = wave + 8 m ----
-    {
+    if constexpr (NCH == 1) {
       // B = [h taps 0-7 | h taps 8-15 | l taps 0-7 | l taps 8-15] by kk; tap t = (kd, kw) = (t / 5, t % 5), t = 15: the zero column
       const unsigned* pw[8];
       const unsigned* const pbase = reinterpret_cast<const unsigned*>(patch) + 8 * WPW * wave + (i >> 1) * WPW;
@@ -343,6 +387,86 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
 #pragma unroll
       for (int m0 = 0; m0 < 12; m0 += 4) tile_group(std::integral_constant<int, 4>{}, m0);
       if (wave < 4) tile_group(std::integral_constant<int, 1>{}, 12);
+    } else {
+      // channels 1 and 2 of this item -> the act1 tile's first 2 x 30 KB (nobody reads act1 between the last item's final barrier
+      // and this item's epilogue), by the waves that fetch channel 0; they land while channel 0 is multiplied
+      float* const chan12 = reinterpret_cast<float*>(act);
+      if (part == 0) {
+#pragma unroll
+        for (int ch = 1; ch < NCH; ++ch)
+          dma_patch_plane(p, cur, (int64_t)NCH * cur.u + ch, starts_cur, pair, lane, chan12 + (ch - 1) * WP_FLOATS);
+      }
+      // the addresses of the one-channel kernel, as word offsets into a channel's patch
+      int po[8];
+      const int pbase = 8 * WPW * wave + (i >> 1) * WPW;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int t0 = e, t1 = 8 + e;
+        const int o0 = (t0 / 5) * (NFRAME * WPW), c0 = t0 % 5;
+        const int o1 = t1 < 15 ? (t1 / 5) * (NFRAME * WPW) : 0, c1 = t1 < 15 ? t1 % 5 : 0;
+        const int colA = (i & 1) + c0, colB = (i & 1) + c1;
+        const int offA = o0 + colA + (colA >= 3 ? 1 : 0), offB = o1 + colB + (colB >= 3 ? 1 : 0);
+        po[e] = pbase + ((kk & 1) ? offB : offA);
+      }
+      const unsigned sel = kk < 2 ? 0x05040100u : 0x07060302u;
+      unsigned* const aw = act + 4 * ((((kk >> 1) * 2 + ((i >> 1) & 1)) * HPLANE) + 8 * wave + 2 * (i >> 2) + (i & 1)) + 2 * (kk & 1);
+      f32x4 acc[13];   // tile wave + 8 m; m = 12 for waves 0 - 3 only
+      // one channel's K = 32 block [h | l] x [H | H], [L | 0] into the accumulators (the bias rides in with channel 0)
+      auto chan_pass = [&](auto first_tag, const unsigned* src, u32x4 WH, u32x4 WL) {
+        auto group = [&](auto nt_tag, auto m0_tag) {
+          constexpr int NT = decltype(nt_tag)::value, M0 = decltype(m0_tag)::value;
+          unsigned w[NT][8];
+#pragma unroll
+          for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) w[t][e] = src[po[e] + 64 * WPW * (M0 + t)];
+          u32x4 B[NT];
+#pragma unroll
+          for (int t = 0; t < NT; ++t) {
+#pragma unroll
+            for (int jx = 0; jx < 4; ++jx) B[t][jx] = __builtin_amdgcn_perm(w[t][2 * jx + 1], w[t][2 * jx], sel);
+            acc[M0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, WH), __builtin_bit_cast(f16x8, B[t]),
+                                                                 decltype(first_tag)::value ? b1v : acc[M0 + t], 0, 0, 0);
+          }
+#pragma unroll
+          for (int t = 0; t < NT; ++t)
+            acc[M0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, WL), __builtin_bit_cast(f16x8, B[t]), acc[M0 + t], 0, 0, 0);
+        };
+        group(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{});
+        group(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{});
+        group(std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});
+        group(std::integral_constant<int, 2>{}, std::integral_constant<int, 6>{});
+        group(std::integral_constant<int, 2>{}, std::integral_constant<int, 8>{});
+        group(std::integral_constant<int, 2>{}, std::integral_constant<int, 10>{});
+        if (wave < 4) group(std::integral_constant<int, 1>{}, std::integral_constant<int, 12>{});
+      };
+      // conv1_1's weight blocks are read per item (L1-resident, 48 B per lane per channel): held across the item loop as W1a / W1b
+      // are in the one-channel kernel, the six blocks and the 13 accumulators spill (256 VGPRs).  The opaque copy of the pointer
+      // keeps the compiler from hoisting the loads out of the loop.
+      const u32x4* w1blk = p.w1blk;
+      asm volatile("" : "+s"(w1blk));
+      chan_pass(std::true_type{}, reinterpret_cast<const unsigned*>(patch), w1blk[lane], w1blk[64 + lane]);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of channels 1 and 2 have landed
+      if (part == 0) {
+#pragma unroll
+        for (int ch = 1; ch < NCH; ++ch) convert_own_at(chan12 + (ch - 1) * WP_FLOATS);
+      }
+      __syncthreads();   // channels 1 and 2 are in place and converted
+#pragma unroll
+      for (int ch = 1; ch < NCH; ++ch)
+        chan_pass(std::false_type{}, reinterpret_cast<const unsigned*>(chan12 + (ch - 1) * WP_FLOATS), w1blk[2 * ch * 64 + lane],
+                  w1blk[(2 * ch + 1) * 64 + lane]);
+      __syncthreads();   // every wave has read channels 1 and 2: act1 may be written
+#pragma unroll
+      for (int m = 0; m < 13; ++m) {
+        if (m == 12 && wave >= 4) break;
+        const f32x4 y = prelu4<SLOPE01>(acc[m], sl1v);
+        unsigned h0, l0, h1, l1;
+        split2(__builtin_shufflevector(y, y, 0, 1), h0, l0);
+        split2(__builtin_shufflevector(y, y, 2, 3), h1, l1);
+        *reinterpret_cast<u32x2*>(aw + 4 * 64 * m) = (u32x2){h0, h1};
+        *reinterpret_cast<u32x2*>(aw + 4 * 64 * m + 4 * 4 * HPLANE) = (u32x2){l0, l1};
+      }
     }
     if (threadIdx.x == 0) q_item3 = p.queue ? (int)q_ticket + 3 * (int)gridDim.x : item2 + (int)gridDim.x;
     __syncthreads();   // act1 is complete; the patch buffer is free
@@ -351,7 +475,12 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
     // ---- (2) conv1_2 + PReLU + pool: 36 tiles of 16 positions, position P = 16 t + i -> (depth P / 72, row, column) ----
     {
       if (part == 0 && next < n_items) {
-        dma_patch_w(p, nx, starts, pair, lane, patch);
+        if constexpr (NCH == 1) {
+          dma_patch_w(p, nx, starts, pair, lane, patch);
+        } else {
+          dma_patch_plane(p, nx, (int64_t)NCH * nx.u, starts, pair, lane, patch);
+          starts_cur = starts;
+        }
         if (item2 < n_items) starts = fetch_starts(p, nx2, lane);
       }
       const int u = cur.u, q = cur.q(), j = cur.j();
@@ -421,6 +550,9 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
 extern "C" {
 
 size_t svk_c3d2_stage1_lds_bytes(void) { return sizeof(float) * (size_t)(HACT_WORDS + WP_FLOATS); }
+// channels 1 and 2 are staged inside the act1 tile: the one-channel kernel's footprint
+static_assert((3 - 1) * WP_FLOATS <= HACT_WORDS, "the staged channels must fit in the act1 tile");
+size_t svk_c3d2_stage1_c3_lds_bytes(void) { return svk_c3d2_stage1_lds_bytes(); }
 
 int svk_c3d2_stage1(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
                      const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, const void* d_w1blk,
@@ -457,6 +589,52 @@ int svk_c3d2_stage1(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t ma
   if (lds + 64 > (size_t)ctx->lds_per_cu)
     return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "svk_c3d2_stage1 needs %zu bytes of LDS per workgroup (device: %d)", lds, ctx->lds_per_cu);
   void (*kern)(const Stage1Params) = slope01 ? c3d2_stage1h_kernel<true> : c3d2_stage1h_kernel<false>;
+  SVK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const int64_t items = (int64_t)n_utt * 36;
+  const unsigned grid = (unsigned)std::min<int64_t>(items, ctx->num_cu);
+  p.queue = getenv("SVK_C3D2_STATIC_ITEMS") ? nullptr : reinterpret_cast<unsigned*>(static_cast<char*>(ctx->scratch) + 112);
+  if (p.queue) SVK_HIP(ctx, hipMemsetAsync(p.queue, 0, 4, ctx->stream));
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, ctx->stream, p);
+  SVK_LAUNCH_CHECK(ctx);
+  return SVK_OK;
+}
+
+int svk_c3d2_stage1_c3(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
+                       const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, const void* d_w1blk,
+                       const float* d_bias1, const float* d_slope1, const void* d_w2blk, const float* d_bias2,
+                       const float* d_slope2, int32_t flags, float* d_out) {
+  if (!ctx) return SVK_ERR_BAD_ARG;
+  const bool slope01 = (flags & 2) != 0;
+  SVK_REQUIRE(ctx, (flags & ~2) == 0, "flags: only bit 1 (slopes in [0, 1]) is defined");
+  SVK_REQUIRE(ctx, n_utt >= 0 && max_frames >= 1, "shape");
+  if (n_cols != NCOEF || n_crops != NCROP || crop_frames != NFRAME)
+    return svk_fail(ctx, SVK_ERR_UNSUPPORTED,
+                    "svk_c3d2_stage1_c3 is built for the 3 x 20 x 80 x 40 cube of utils.py:325-348 (got %d x %d x %d)", n_crops,
+                    crop_frames, n_cols);
+  if (n_utt == 0) return SVK_OK;
+  SVK_REQUIRE(ctx, d_feat && d_crop_idx && d_w1blk && d_bias1 && d_slope1 && d_w2blk && d_bias2 && d_slope2 && d_out,
+              "NULL buffer");
+  SVK_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(d_feat) & 7) == 0 && ((reinterpret_cast<uintptr_t>(d_w1blk) | reinterpret_cast<uintptr_t>(d_w2blk) |
+                                                                    reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
+              "d_feat must be 8-byte, the weight blocks and d_out 16-byte aligned");
+  SVK_REQUIRE(ctx, (int64_t)n_utt * 36 + 4 * (int64_t)ctx->num_cu < ((int64_t)1 << 31), "too many cubes for one launch");
+  Stage1Params p;
+  p.feat = d_feat;
+  p.crop = d_crop_idx;
+  p.n_utt = n_utt;
+  p.max_frames = max_frames;
+  p.w1blk = static_cast<const u32x4*>(d_w1blk);
+  p.bias1 = d_bias1;
+  p.slope1 = d_slope1;
+  p.w2blk = static_cast<const u32x4*>(d_w2blk);
+  p.bias2 = d_bias2;
+  p.slope2 = d_slope2;
+  p.out = d_out;
+  const size_t lds = svk_c3d2_stage1_c3_lds_bytes();
+  if (lds + 64 > (size_t)ctx->lds_per_cu)
+    return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "svk_c3d2_stage1_c3 needs %zu bytes of LDS per workgroup (device: %d)", lds,
+                    ctx->lds_per_cu);
+  void (*kern)(const Stage1Params) = slope01 ? c3d2_stage1h_kernel<true, 3> : c3d2_stage1h_kernel<false, 3>;
   SVK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int64_t items = (int64_t)n_utt * 36;
   const unsigned grid = (unsigned)std::min<int64_t>(items, ctx->num_cu);

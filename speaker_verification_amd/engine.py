@@ -472,6 +472,29 @@ class Engine:
                                        self._ptr(slope2), 2 if slope01 else 0, self._ptr(out)), self.ctx)
         return out
 
+    def c3d2_stage1_c3(self, feat3, crop_idx, tables, crop_frames=80):
+        """svk_c3d2_stage1_c3: the first block of the three-channel C3D2 (conv1_1 3 -> 16): feature rows [n, 3, T, 40]
+        (static, delta, delta-delta) + crop starts [n, 20] -> [n, 16, 36, 18, 16] f32, the layout of c3d2_stage1's output;
+        tables: `FusedEmbedder.stage1_tables()` of a three-channel model."""
+        torch = _torch()
+        feat3 = self.to_device(feat3, torch.float32)
+        idx = self.to_device(crop_idx, torch.int32)
+        if feat3.dim() != 4 or feat3.shape[1] != 3:
+            raise ValueError("c3d2_stage1_c3 wants feature rows [n, 3, T, cols], got %s" % (tuple(feat3.shape),))
+        n, _, T, Cc = feat3.shape
+        if idx.dim() != 2 or idx.shape[0] != n:
+            raise ValueError("crop_idx must be [n, n_crops] for the n = %d cubes, got %s" % (n, tuple(idx.shape)))
+        w1frag, bias1, slope1, w2frag, bias2, slope2 = tables[:6]
+        if w1frag.dtype != torch.float16 or w2frag.dtype != torch.float16 or tuple(w1frag.shape) != (3, 2, 64, 8) or tuple(w2frag.shape) != (14, 2, 64, 8):
+            raise ValueError("c3d2_stage1_c3 wants the half-pair weight blocks of a three-channel FusedEmbedder.stage1_tables()")
+        slope01 = bool(tables[6]) if len(tables) > 6 else False
+        out = torch.empty((n, 16, 36, 18, 16), dtype=torch.float32, device=self.device)
+        self._stream()
+        check(self.lib.svk_c3d2_stage1_c3(self.ctx, self._ptr(feat3), n, T, Cc, self._ptr(idx), idx.shape[1], crop_frames,
+                                          self._ptr(w1frag), self._ptr(bias1), self._ptr(slope1), self._ptr(w2frag),
+                                          self._ptr(bias2), self._ptr(slope2), 2 if slope01 else 0, self._ptr(out)), self.ctx)
+        return out
+
     def c3d2_stage2(self, act1, tables):
         """svk_c3d2_stage2: [n, 16, 36, 18, 16] (svk_c3d2_stage1's output) -> conv2_1 -> conv2_2 -> pool2 with their
         BN + PReLU -> [n, 12, 15, 7, 32] f32 (channels last), both convolutions through two-piece f16 products."""

@@ -173,7 +173,9 @@ def dataset_embeddings(dataset, model, batch=256):
     the per-item chain of the reference (load_data.py:50-87 `load_wav` -> `lmfe`; utils.py:382-397 CMVN;
     utils.py:351-379 FeatureCube with crop starts from the GLOBAL NumPy RNG, drawn in file order;
     `model(cube, development=False)`) run `batch` files at a time: one ragged front-end launch, one CMVN and the seven
-    libsvk network kernels per batch -- the cube is never built (`svk_c3d2_stage1` reads feature rows + crop starts)."""
+    libsvk network kernels per batch -- the cube is never built (`svk_c3d2_stage1` reads feature rows + crop starts).
+    With `constants.DERIVATIVE` (a `C3D2(n, 3)` model, utils.py:325-348 FeatureCube3C): the two derivative launches and a
+    CMVN per channel in front, `svk_c3d2_stage1_c3` on the three channel planes."""
     from . import _lib
     from . import constants as c
     from .engine import spec_from_seconds
@@ -181,13 +183,6 @@ def dataset_embeddings(dataset, model, batch=256):
     model = model.to(eng.device).eval()
     n = len(dataset)
     out = torch.empty((n, 128), dtype=torch.float32, device=eng.device)
-    if c.DERIVATIVE:
-        # three-channel cubes (utils.py:385-391): the per-item transform chain, the torch module's forward batched
-        for lo in range(0, n, batch):
-            cubes = np.stack([np.asarray(dataset[i][0], dtype=np.float32) for i in range(lo, min(n, lo + batch))])
-            with torch.no_grad():
-                out[lo:lo + len(cubes)] = model(eng.to_device(cubes), development=False)
-        return out
     specs = {plain: spec_from_seconds(c.SAMPLE_RATE, c.FRAME_LEN, c.FRAME_STEP, c.NUM_FFT, c.NUM_COEF, c.NUM_COEF, _lib.OUT_LMFE,
                                       input_scale=1.0 / 32768.0 if plain else 1.0) for plain in (True, False)}
     embed = model.fused_inference()
@@ -197,7 +192,16 @@ def dataset_embeddings(dataset, model, batch=256):
         spec = specs[plain]
         frames = [spec.num_frames(int(v)) for v in lens]
         feat, n_frames, _ = eng.features(buf, spec, lengths=lens, offsets=offs, max_frames=max(frames))
-        if c.NORMALIZE:
+        if c.DERIVATIVE:
+            # utils.py:385-391: static, delta and the delta of delta (extract_derivative_feature, Q11 included), then CMVN per
+            # channel; [n, 3, T, 40] is the layout svk_c3d2_stage1_c3 reads (FeatureCube3C's crops of it)
+            chans = [feat, eng.derivative(feat, 2)]
+            chans.append(eng.derivative(chans[1], 2))
+            if c.NORMALIZE:
+                for ch in chans:
+                    eng.cmvn_(ch, n_frames, variance=True)
+            feat = torch.stack(chans, 1)
+        elif c.NORMALIZE:
             eng.cmvn_(feat, n_frames, variance=True)
         # utils.py:372, one draw per file in file order (numpy raises for clips of <= 80 frames, as there)
         idx = np.stack([np.random.randint(T - c.CUBE_FRAMES, size=c.CUBE_CROPS) for T in frames]).astype(np.int32)

@@ -5,13 +5,18 @@ f16 products; `svk_c3d2_conv42`, `svk_c3d2_fc5`: csrc/c3d2_tail.hip, f32).
 
 Same constructor arguments, same sub-module names (a reference-format checkpoint's `state_dict` loads unchanged), same
 `forward(x, development=True)`, `load_checkpoint(d)` and `create_Speaker_Model(u)` as the reference.  Input convention
-`(batch, 1, 20, 80, 40)` (`/root/reference/utils.py:368-379`).
+`(batch, 1, 20, 80, 40)` (`/root/reference/utils.py:368-379`), or `(batch, 3, 20, 80, 40)` for `C3D2(n, 3)` (static, delta and
+delta-delta features: `utils.FeatureCube3C`, `/root/reference/utils.py:325-348`).
 
 Which code runs a forward:
   * eval mode, input on the GPU, one-channel 20 x 80 x 40 cubes, no gradient asked of the input -- what
     `evaluation.py:67-84,113-121` and `model.py:188-191,374-388` do -- : the libsvk kernels.  A cube IS a feature
     matrix of 1 600 rows with crop starts 0, 80, 160 ...: `svk_c3d2_stage1` reads it as such, nothing is copied;
-  * training mode, gradients, three-channel cubes (`utils.FeatureCube3C`), tensors on the host: the torch layers
+  * the same for three-channel cubes of a `C3D2(n, 3)` when `model.three_channel_kernels = True` (on the instance or the
+    class): `svk_c3d2_stage1_c3` reads the cube as three planes of 1 600 rows.  Off by default, so that forward's routing
+    stays what it was; `FusedEmbedder(model)` and `evaluation.dataset_embeddings` take the kernels for three channels as
+    they do for one;
+  * training mode, gradients, other channel counts, tensors on the host: the torch layers
     (autograd needs them; the north-star leaves the training forward on PyTorch-ROCm).
 `model.inference_kernels = False` keeps an instance on the torch layers (A/B comparisons in tools).
 """
@@ -40,6 +45,7 @@ _EMBEDDERS = weakref.WeakKeyDictionary()   # model -> (state key, FusedEmbedder)
 
 class C3D2(nn.Module):
     inference_kernels = True          # False on an instance: forward stays on the torch layers whatever the mode
+    three_channel_kernels = False     # True on an instance (or the class): forward runs three-channel cubes on the kernels too
 
     def __init__(self, n_labels, num_channels):
         super().__init__()
@@ -59,7 +65,7 @@ class C3D2(nn.Module):
 
     def torch_layers(self, x):
         """conv -> BatchNorm -> PReLU (-> pool) x 8 -> FC5 on torch operators (model.py:141-169): training, autograd,
-        host tensors, three-channel cubes."""
+        host tensors, three-channel cubes unless `three_channel_kernels`."""
         for tag, _, _, _, _, pool in _LAYERS:
             x = getattr(self, "conv" + tag)(x)
             x = getattr(self, "batch_norm" + tag)(x)
@@ -71,8 +77,9 @@ class C3D2(nn.Module):
     def runs_on_kernels(self, x):
         """True when forward(x) is an inference call the libsvk network covers (see the module docstring)."""
         return bool(self.inference_kernels and not self.training and isinstance(x, torch.Tensor) and x.is_cuda
-                    and x.dim() == 5 and tuple(x.shape[1:]) == CUBE_SHAPE and x.dtype == torch.float32
-                    and self.num_channels == 1 and not (torch.is_grad_enabled() and x.requires_grad))
+                    and x.dim() == 5 and (self.num_channels == 1 or (self.num_channels == 3 and self.three_channel_kernels))
+                    and tuple(x.shape[1:]) == (self.num_channels,) + CUBE_SHAPE[1:] and x.dtype == torch.float32
+                    and not (torch.is_grad_enabled() and x.requires_grad))
 
     def forward(self, x, development=True):
         if self.runs_on_kernels(x):
@@ -121,11 +128,12 @@ class C3D2(nn.Module):
 
 class FusedEmbedder:
     """C3D2's forward(development=False) as seven libsvk kernels; the weights are a snapshot of the model at build time.
-    Built for C3D2's layer shapes on one-channel cubes only: anything else raises (no framework fallback here -- the torch
-    module itself is the path for other shapes)."""
+    Built for C3D2's layer shapes on one- or three-channel cubes only: anything else raises (no framework fallback here -- the
+    torch module itself is the path for other shapes)."""
 
     def __init__(self, model):
         self.device = model.conv1_1.weight.device       # tables are built where the weights live; kernels need the GPU
+        self.num_channels = int(model.conv1_1.weight.shape[1])
         self._eng = None
         self.stages = []
         self.act_scale = []     # per layer: the power of two per channel its output is carried in (all ones for an ordinary checkpoint)
@@ -167,7 +175,7 @@ class FusedEmbedder:
         tables = (self.stage1_tables(), self.stage2_tables(), self.conv31_tables(), self.conv32t_tables(),
                   self.conv41_tables(), self.conv42_tables(), self.fc5_tables())
         if any(t is None for t in tables):
-            raise ValueError("libsvk's network kernels are built for C3D2's layers on one-channel 20 x 80 x 40 cubes "
+            raise ValueError("libsvk's network kernels are built for C3D2's layers on one- or three-channel 20 x 80 x 40 cubes "
                              "(model.py:110-139); this model's layers differ")
         self._starts = {}
 
@@ -193,12 +201,18 @@ class FusedEmbedder:
 
     @torch.no_grad()
     def embed_features(self, feat, crop_idx, timed=None):
-        """feature rows [n, T, 40] + crop starts [n, 20] -> embeddings [n, 128].  The cube (utils.py:351-379) is never
-        materialised: the first-block kernel gathers its patches from the feature rows.  `timed(name, fn)`: the
-        pipeline's HIP-event hook around each kernel (bench.py)."""
+        """feature rows [n, T, 40] (one-channel model) or [n, 3, T, 40] (three-channel: static, delta, delta-delta) + crop
+        starts [n, 20] -> embeddings [n, 128].  The cube (utils.py:351-379, :325-348) is never materialised: the first-block
+        kernel gathers its patches from the feature rows.  `timed(name, fn)`: the pipeline's HIP-event hook around each
+        kernel (bench.py)."""
         run = timed or (lambda name, fn: fn())
         eng = self.eng
-        y = run("stage1", lambda: eng.c3d2_stage1(feat, crop_idx, self.stage1_tables()))
+        want = 3 if self.num_channels == 1 else 4
+        if feat.dim() != want or (want == 4 and feat.shape[1] != self.num_channels):
+            raise ValueError("this %d-channel model embeds feature rows of shape %s, got %s"
+                             % (self.num_channels, "[n, T, 40]" if want == 3 else "[n, 3, T, 40]", tuple(feat.shape)))
+        stage1 = eng.c3d2_stage1 if self.num_channels == 1 else eng.c3d2_stage1_c3
+        y = run("stage1", lambda: stage1(feat, crop_idx, self.stage1_tables()))
         z = run("stage2", lambda: eng.c3d2_stage2(y, self.stage2_tables()))
         y = run("conv3_1", lambda: eng.c3d2_conv31(z, self.conv31_tables()))
         y = run("conv3_2", lambda: eng.c3d2_conv32t(y, self.conv32t_tables()))
@@ -208,10 +222,12 @@ class FusedEmbedder:
 
     @torch.no_grad()
     def __call__(self, cubes, batch=4096):
-        """cubes [n, 1, 20, 80, 40] f32 on the device -> [n, 128]: the cube's memory is read as [n, 1 600, 40] feature rows
-        with crop starts 0, 80, ... (a view: nothing is copied or re-gathered)."""
-        if cubes.dim() != 5 or tuple(cubes.shape[1:]) != CUBE_SHAPE:
-            raise ValueError("expected cubes of shape (n, 1, 20, 80, 40), got %s" % (tuple(cubes.shape),))
+        """cubes [n, C, 20, 80, 40] f32 on the device (C = the model's 1 or 3 channels) -> [n, 128]: the cube's memory is read
+        as [n, 1 600, 40] (or [n, 3, 1 600, 40]) feature rows with crop starts 0, 80, ... (a view: nothing is copied or
+        re-gathered)."""
+        shape = (self.num_channels,) + CUBE_SHAPE[1:]
+        if cubes.dim() != 5 or tuple(cubes.shape[1:]) != shape:
+            raise ValueError("expected cubes of shape (n, %d, 20, 80, 40), got %s" % (self.num_channels, tuple(cubes.shape)))
         x = self.eng.to_device(cubes, torch.float32)
         n = x.shape[0]
         if n:       # (this per-call surface only: the batched pipeline feeds its own features; aminmax: no temporary, NaN propagates)
@@ -219,7 +235,7 @@ class FusedEmbedder:
         if n and not (lo > -65504.0 and hi < 65504.0):
             raise ValueError("cube values must be finite and below 65 504 in magnitude (the half-pair kernels' domain, include/svk.h); "
                              "the reference's features are log energies / MFCCs within +-100")
-        rows = x.view(n, CUBE_SHAPE[1] * CUBE_SHAPE[2], CUBE_SHAPE[3])
+        rows = x.view((n,) + ((self.num_channels,) if self.num_channels != 1 else ()) + (CUBE_SHAPE[1] * CUBE_SHAPE[2], CUBE_SHAPE[3]))
         if n <= batch:
             return self.embed_features(rows, self.crop_starts(n, x.device)) if n else x.new_empty((0, EMBED_DIM))
         out = torch.empty((n, EMBED_DIM), dtype=torch.float32, device=x.device)
@@ -233,8 +249,10 @@ class FusedEmbedder:
         """Operand blocks of `svk_c3d2_stage1` (two-piece f16 products; include/svk.h): the BN-folded weights of conv1_1 /
         conv1_2 split into halves H = f16(w), L = f16(w - H) and laid out in the lane order of v_mfma_f32_16x16x32_f16's A
         operand (lane l = (co = l & 15, kk = l >> 4), eight halves: K = 8 kk + e), or None when the first block is not C3D2's
-        (1 -> 16 k(3,1,5); 16 -> 16 k(3,9,1) stride (1,2,1); pool).
+        (1 or 3 -> 16 k(3,1,5); 16 -> 16 k(3,9,1) stride (1,2,1); pool).
           w1blk [2][64][8]      : conv1_1, tap t = 8 (kk & 1) + e (t = 5 kd + kw; 15 -> 0): H for every kk | L for kk < 2, 0 above
+                 [3][2][64][8]  : the three-channel conv1_1 (`svk_c3d2_stage1_c3`): that block for each input channel -- the 45
+                                  taps padded to 48, tap 15 of every channel the zero pad
           w2blk [14][2][64][8]  : conv1_2, tap pairs (a | b): ci = 8 (kk & 1) + e at tap a (kk < 2) / b (kk >= 2); H | L;
                                   pair 13 is tap (2, 8) alone against an [h | l] fragment: H at every kk | L for kk < 2, 0 above"""
         hit = getattr(self, "_stage1", False)
@@ -242,7 +260,7 @@ class FusedEmbedder:
             return hit
         self._stage1 = None
         (w1, b1, s1, st1, p1, _), (w2, b2, s2, st2, p2, _) = self.stages[0], self.stages[1]
-        if (tuple(w1.shape) != (16, 1, 3, 1, 5) or tuple(w2.shape) != (16, 16, 3, 9, 1) or tuple(st1) != (1, 1, 1)
+        if (tuple(w1.shape) not in ((16, 1, 3, 1, 5), (16, 3, 3, 1, 5)) or tuple(w2.shape) != (16, 16, 3, 9, 1) or tuple(st1) != (1, 1, 1)
                 or tuple(st2) != (1, 2, 1) or p1 or not p2):
             return None
         dev = w1.device
@@ -254,10 +272,13 @@ class FusedEmbedder:
         lane = torch.arange(64, device=dev)
         co, kk = lane & 15, lane >> 4
         e = torch.arange(8, device=dev)
-        w1c = torch.cat([w1.contiguous().view(16, 15), torch.zeros((16, 1), device=dev)], 1)     # [co][t], t = 15: zero
         t = 8 * (kk & 1)[:, None] + e[None, :]                                                    # [64][8]
-        h1, l1 = halves(w1c[co[:, None], t])
-        w1blk = torch.stack([h1, torch.where((kk < 2)[:, None], l1, torch.zeros_like(l1))])       # [2][64][8]
+        blocks = []
+        for ch in range(w1.shape[1]):
+            w1c = torch.cat([w1[:, ch].contiguous().view(16, 15), torch.zeros((16, 1), device=dev)], 1)   # [co][t], t = 15: zero
+            h1, l1 = halves(w1c[co[:, None], t])
+            blocks.append(torch.stack([h1, torch.where((kk < 2)[:, None], l1, torch.zeros_like(l1))]))  # [2][64][8]
+        w1blk = blocks[0] if len(blocks) == 1 else torch.stack(blocks)
         w2c = w2.contiguous()[:, :, :, :, 0]                                                      # [co][ci][kd][kh]
         pairs = [((p // 4, 2 * (p % 4)), (p // 4, 2 * (p % 4) + 1)) for p in range(12)] + [((0, 8), (1, 8)), ((2, 8), None)]
         ci = 8 * (kk & 1)[:, None] + e[None, :]
