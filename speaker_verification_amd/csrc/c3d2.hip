@@ -24,8 +24,7 @@
 //      the act1 tile in LDS: 10 depths x 80 rows x 2 columns x 16 channels;
 //   3. conv1_2 as an implicit GEMM in the direct form, two taps per K = 32 block, the weights of all 27 taps in 112 VGPRs;
 //   4. bias (in the accumulator), PReLU, max over the column pair (adjacent lanes: one DPP instruction), 16-byte stores.
-#include <algorithm>
-#include <cstdlib>
+#include <climits>
 #include <vector>
 
 #include "svk_internal.h"
@@ -545,6 +544,45 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
   }
 }
 
+// svk_c3d2_stage1 (NCH = 1) and svk_c3d2_stage1_c3 (NCH = 3): the same arguments, checks and launch
+template <int NCH>
+int stage1(svk_ctx* ctx, const char* name, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
+           const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, const void* d_w1blk, const float* d_bias1,
+           const float* d_slope1, const void* d_w2blk, const float* d_bias2, const float* d_slope2, int32_t flags, float* d_out) {
+  if (!ctx) return SVK_ERR_BAD_ARG;
+  SVK_REQUIRE(ctx, (flags & ~2) == 0, "flags: only bit 1 (slopes in [0, 1]) is defined");
+  SVK_REQUIRE(ctx, n_utt >= 0 && max_frames >= 1, "shape");
+  if (n_cols != NCOEF || n_crops != NCROP || crop_frames != NFRAME)
+    return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "%s is built for the %s20 x 80 x 40 cube of utils.py:%s (got %d x %d x %d)", name,
+                    NCH == 3 ? "3 x " : "", NCH == 3 ? "325-348" : "20-21", n_crops, crop_frames, n_cols);
+  if (n_utt == 0) return SVK_OK;
+  SVK_REQUIRE(ctx, d_feat && d_crop_idx && d_w1blk && d_bias1 && d_slope1 && d_w2blk && d_bias2 && d_slope2 && d_out,
+              "NULL buffer");
+  SVK_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(d_feat) & 7) == 0 && ((reinterpret_cast<uintptr_t>(d_w1blk) | reinterpret_cast<uintptr_t>(d_w2blk) |
+                                                                    reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
+              "d_feat must be 8-byte, the weight blocks and d_out 16-byte aligned");
+  SVK_REQUIRE(ctx, (int64_t)n_utt * 36 + 4 * (int64_t)ctx->num_cu < ((int64_t)1 << 31), "too many cubes for one launch");
+  Stage1Params p;
+  p.feat = d_feat;
+  p.crop = d_crop_idx;
+  p.n_utt = n_utt;
+  p.max_frames = max_frames;
+  p.w1blk = static_cast<const u32x4*>(d_w1blk);
+  p.bias1 = d_bias1;
+  p.slope1 = d_slope1;
+  p.w2blk = static_cast<const u32x4*>(d_w2blk);
+  p.bias2 = d_bias2;
+  p.slope2 = d_slope2;
+  p.out = d_out;
+  void (*kern)(const Stage1Params) = (flags & 2) ? c3d2_stage1h_kernel<true, NCH> : c3d2_stage1h_kernel<false, NCH>;
+  unsigned grid;
+  if (int rc = svk_persistent_grid(ctx, name, kern, svk_c3d2_stage1_lds_bytes(), 512, 1, (int64_t)n_utt * 36, &grid)) return rc;
+  if (int rc = svk_work_queue(ctx, SVK_SLOT_STAGE1, 1, &p.queue)) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), svk_c3d2_stage1_lds_bytes(), ctx->stream, p);
+  SVK_LAUNCH_CHECK(ctx);
+  return SVK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -558,91 +596,16 @@ int svk_c3d2_stage1(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t ma
                      const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, const void* d_w1blk,
                      const float* d_bias1, const float* d_slope1, const void* d_w2blk, const float* d_bias2,
                      const float* d_slope2, int32_t flags, float* d_out) {
-  if (!ctx) return SVK_ERR_BAD_ARG;
-  const bool slope01 = (flags & 2) != 0;
-  SVK_REQUIRE(ctx, (flags & ~2) == 0, "flags: only bit 1 (slopes in [0, 1]) is defined");
-  SVK_REQUIRE(ctx, n_utt >= 0 && max_frames >= 1, "shape");
-  if (n_cols != NCOEF || n_crops != NCROP || crop_frames != NFRAME)
-    return svk_fail(ctx, SVK_ERR_UNSUPPORTED,
-                    "svk_c3d2_stage1 is built for the 20 x 80 x 40 cube of utils.py:20-21 (got %d x %d x %d)", n_crops,
-                    crop_frames, n_cols);
-  if (n_utt == 0) return SVK_OK;
-  SVK_REQUIRE(ctx, d_feat && d_crop_idx && d_w1blk && d_bias1 && d_slope1 && d_w2blk && d_bias2 && d_slope2 && d_out,
-              "NULL buffer");
-  SVK_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(d_feat) & 7) == 0 && ((reinterpret_cast<uintptr_t>(d_w1blk) | reinterpret_cast<uintptr_t>(d_w2blk) |
-                                                                    reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
-              "d_feat must be 8-byte, the weight blocks and d_out 16-byte aligned");
-  SVK_REQUIRE(ctx, (int64_t)n_utt * 36 + 4 * (int64_t)ctx->num_cu < ((int64_t)1 << 31), "too many cubes for one launch");
-  Stage1Params p;
-  p.feat = d_feat;
-  p.crop = d_crop_idx;
-  p.n_utt = n_utt;
-  p.max_frames = max_frames;
-  p.w1blk = static_cast<const u32x4*>(d_w1blk);
-  p.bias1 = d_bias1;
-  p.slope1 = d_slope1;
-  p.w2blk = static_cast<const u32x4*>(d_w2blk);
-  p.bias2 = d_bias2;
-  p.slope2 = d_slope2;
-  p.out = d_out;
-  const size_t lds = svk_c3d2_stage1_lds_bytes();
-  if (lds + 64 > (size_t)ctx->lds_per_cu)
-    return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "svk_c3d2_stage1 needs %zu bytes of LDS per workgroup (device: %d)", lds, ctx->lds_per_cu);
-  void (*kern)(const Stage1Params) = slope01 ? c3d2_stage1h_kernel<true> : c3d2_stage1h_kernel<false>;
-  SVK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t items = (int64_t)n_utt * 36;
-  const unsigned grid = (unsigned)std::min<int64_t>(items, ctx->num_cu);
-  p.queue = getenv("SVK_C3D2_STATIC_ITEMS") ? nullptr : reinterpret_cast<unsigned*>(static_cast<char*>(ctx->scratch) + 112);
-  if (p.queue) SVK_HIP(ctx, hipMemsetAsync(p.queue, 0, 4, ctx->stream));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, ctx->stream, p);
-  SVK_LAUNCH_CHECK(ctx);
-  return SVK_OK;
+  return stage1<1>(ctx, "svk_c3d2_stage1", d_feat, n_utt, max_frames, n_cols, d_crop_idx, n_crops, crop_frames, d_w1blk, d_bias1,
+                   d_slope1, d_w2blk, d_bias2, d_slope2, flags, d_out);
 }
 
 int svk_c3d2_stage1_c3(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
                        const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, const void* d_w1blk,
                        const float* d_bias1, const float* d_slope1, const void* d_w2blk, const float* d_bias2,
                        const float* d_slope2, int32_t flags, float* d_out) {
-  if (!ctx) return SVK_ERR_BAD_ARG;
-  const bool slope01 = (flags & 2) != 0;
-  SVK_REQUIRE(ctx, (flags & ~2) == 0, "flags: only bit 1 (slopes in [0, 1]) is defined");
-  SVK_REQUIRE(ctx, n_utt >= 0 && max_frames >= 1, "shape");
-  if (n_cols != NCOEF || n_crops != NCROP || crop_frames != NFRAME)
-    return svk_fail(ctx, SVK_ERR_UNSUPPORTED,
-                    "svk_c3d2_stage1_c3 is built for the 3 x 20 x 80 x 40 cube of utils.py:325-348 (got %d x %d x %d)", n_crops,
-                    crop_frames, n_cols);
-  if (n_utt == 0) return SVK_OK;
-  SVK_REQUIRE(ctx, d_feat && d_crop_idx && d_w1blk && d_bias1 && d_slope1 && d_w2blk && d_bias2 && d_slope2 && d_out,
-              "NULL buffer");
-  SVK_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(d_feat) & 7) == 0 && ((reinterpret_cast<uintptr_t>(d_w1blk) | reinterpret_cast<uintptr_t>(d_w2blk) |
-                                                                    reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
-              "d_feat must be 8-byte, the weight blocks and d_out 16-byte aligned");
-  SVK_REQUIRE(ctx, (int64_t)n_utt * 36 + 4 * (int64_t)ctx->num_cu < ((int64_t)1 << 31), "too many cubes for one launch");
-  Stage1Params p;
-  p.feat = d_feat;
-  p.crop = d_crop_idx;
-  p.n_utt = n_utt;
-  p.max_frames = max_frames;
-  p.w1blk = static_cast<const u32x4*>(d_w1blk);
-  p.bias1 = d_bias1;
-  p.slope1 = d_slope1;
-  p.w2blk = static_cast<const u32x4*>(d_w2blk);
-  p.bias2 = d_bias2;
-  p.slope2 = d_slope2;
-  p.out = d_out;
-  const size_t lds = svk_c3d2_stage1_c3_lds_bytes();
-  if (lds + 64 > (size_t)ctx->lds_per_cu)
-    return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "svk_c3d2_stage1_c3 needs %zu bytes of LDS per workgroup (device: %d)", lds,
-                    ctx->lds_per_cu);
-  void (*kern)(const Stage1Params) = slope01 ? c3d2_stage1h_kernel<true, 3> : c3d2_stage1h_kernel<false, 3>;
-  SVK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t items = (int64_t)n_utt * 36;
-  const unsigned grid = (unsigned)std::min<int64_t>(items, ctx->num_cu);
-  p.queue = getenv("SVK_C3D2_STATIC_ITEMS") ? nullptr : reinterpret_cast<unsigned*>(static_cast<char*>(ctx->scratch) + 112);
-  if (p.queue) SVK_HIP(ctx, hipMemsetAsync(p.queue, 0, 4, ctx->stream));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, ctx->stream, p);
-  SVK_LAUNCH_CHECK(ctx);
-  return SVK_OK;
+  return stage1<3>(ctx, "svk_c3d2_stage1_c3", d_feat, n_utt, max_frames, n_cols, d_crop_idx, n_crops, crop_frames, d_w1blk,
+                   d_bias1, d_slope1, d_w2blk, d_bias2, d_slope2, flags, d_out);
 }
 
 }  // extern "C"
@@ -1319,42 +1282,26 @@ extern "C" int svk_c3d2_stage2(svk_ctx* ctx, const float* d_in, int32_t n_utt, c
                      reinterpret_cast<uintptr_t>(d_w21blk) | reinterpret_cast<uintptr_t>(d_w22blk) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
               "buffers must be 16-byte aligned");
   SVK_REQUIRE(ctx, (int64_t)n_utt * 21 < ((int64_t)1 << 31), "too many cubes for one launch");
-  // work-item counters of the kernels that share a CU between workgroups (slots of the handle's 256-byte scratch; svk_log_power
-  // owns the first word): zeroed in stream order before the launches.  SVK_C3D2_STATIC_ITEMS: items at a fixed stride instead
-  // (the determinism test: the same results bit for bit whichever workgroup takes an item)
-  const bool static_items = getenv("SVK_C3D2_STATIC_ITEMS") != nullptr;
-  unsigned* const queues = static_items ? nullptr : reinterpret_cast<unsigned*>(static_cast<char*>(ctx->scratch) + 64);
-  if (queues) SVK_HIP(ctx, hipMemsetAsync(queues, 0, 16, ctx->stream));
-  const bool slope01 = (flags & 2) != 0;
+  // conv2_1 and conv2_2 share a CU between workgroups: as many as the occupancy calculator allows
+  unsigned* queues;
+  if (int rc = svk_work_queue(ctx, SVK_SLOT_STAGE2, 2, &queues)) return rc;
   {
     Conv21hParams p{d_in, reinterpret_cast<const u32x4*>(d_w21blk), d_bias21, d_slope21, d_act2, n_utt, queues};
-    void (*kern)(const Conv21hParams) = slope01 ? c3d2_conv21h_kernel<true> : c3d2_conv21h_kernel<false>;
+    void (*kern)(const Conv21hParams) = (flags & 2) ? c3d2_conv21h_kernel<true> : c3d2_conv21h_kernel<false>;
     const size_t lds = sizeof(unsigned) * (size_t)C21H_LDS_WORDS;
-    if (lds > (size_t)ctx->lds_per_cu)
-      return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "svk_c3d2_stage2 (conv2_1) needs %zu bytes of LDS per workgroup (device: %d)",
-                      lds, ctx->lds_per_cu);
-    SVK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t items = (int64_t)n_utt * (S2_H / 4);
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 256, lds) != hipSuccess ||
-        per_cu < 1)
-      per_cu = 2;
-    hipLaunchKernelGGL(kern, dim3((unsigned)std::min<int64_t>(items, (int64_t)per_cu * ctx->num_cu)), dim3(256), lds,
-                       ctx->stream, p);
+    unsigned grid;
+    if (int rc = svk_persistent_grid(ctx, "svk_c3d2_stage2 (conv2_1)", kern, lds, 256, INT_MAX, (int64_t)n_utt * (S2_H / 4), &grid))
+      return rc;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx->stream, p);
     SVK_LAUNCH_CHECK(ctx);
   }
   {
     Conv22hParams p{d_act2, reinterpret_cast<const u32x4*>(d_w22blk), d_bias22, d_slope22, d_out, n_utt, queues ? queues + 1 : nullptr};
-    void (*kern)(const Conv22hParams) = slope01 ? c3d2_conv22h_kernel<true> : c3d2_conv22h_kernel<false>;
+    void (*kern)(const Conv22hParams) = (flags & 2) ? c3d2_conv22h_kernel<true> : c3d2_conv22h_kernel<false>;
     const size_t lds = sizeof(unsigned) * (size_t)C22H_LDS_WORDS;
-    SVK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t items = (int64_t)n_utt * 21;
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 256, lds) != hipSuccess ||
-        per_cu < 1)
-      per_cu = 2;
-    hipLaunchKernelGGL(kern, dim3((unsigned)std::min<int64_t>(items, (int64_t)per_cu * ctx->num_cu)), dim3(256), lds,
-                       ctx->stream, p);
+    unsigned grid;
+    if (int rc = svk_persistent_grid(ctx, "svk_c3d2_stage2 (conv2_2)", kern, lds, 256, INT_MAX, (int64_t)n_utt * 21, &grid)) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx->stream, p);
     SVK_LAUNCH_CHECK(ctx);
   }
   return SVK_OK;
@@ -1370,23 +1317,13 @@ extern "C" int svk_c3d2_conv31(svk_ctx* ctx, const float* d_in, int32_t n_utt, c
   SVK_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_wblk) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
               "buffers must be 16-byte aligned");
   SVK_REQUIRE(ctx, (int64_t)n_utt * 5 < ((int64_t)1 << 31), "too many cubes for one launch");
-  const bool static_items31 = getenv("SVK_C3D2_STATIC_ITEMS") != nullptr;
-  unsigned* const queue31 = static_items31 ? nullptr : reinterpret_cast<unsigned*>(static_cast<char*>(ctx->scratch) + 80);
-  if (queue31) SVK_HIP(ctx, hipMemsetAsync(queue31, 0, 4, ctx->stream));
-  Conv31Params p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, queue31};
+  Conv31Params p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, nullptr};
   void (*kern)(const Conv31Params) = (flags & 2) ? c3d2_conv31h_kernel<true> : c3d2_conv31h_kernel<false>;
   const size_t lds = sizeof(unsigned) * (size_t)C31H_LDS_WORDS;
-  if (lds > (size_t)ctx->lds_per_cu)
-    return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "svk_c3d2_conv31 needs %zu bytes of LDS per workgroup (device: %d)", lds,
-                    ctx->lds_per_cu);
-  SVK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t items = (int64_t)n_utt * 5;
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 256, lds) != hipSuccess ||
-      per_cu < 1)
-    per_cu = 2;
-  hipLaunchKernelGGL(kern, dim3((unsigned)std::min<int64_t>(items, (int64_t)per_cu * ctx->num_cu)), dim3(256), lds, ctx->stream,
-                     p);
+  unsigned grid;
+  if (int rc = svk_work_queue(ctx, SVK_SLOT_CONV31, 1, &p.queue)) return rc;
+  if (int rc = svk_persistent_grid(ctx, "svk_c3d2_conv31", kern, lds, 256, INT_MAX, (int64_t)n_utt * 5, &grid)) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx->stream, p);
   SVK_LAUNCH_CHECK(ctx);
   return SVK_OK;
 }
@@ -1401,16 +1338,13 @@ extern "C" int svk_c3d2_conv32t(svk_ctx* ctx, const float* d_in, int32_t n_utt, 
   SVK_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_wblk) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
               "buffers must be 16-byte aligned");
   SVK_REQUIRE(ctx, (int64_t)n_utt * 5 + 2 * (int64_t)ctx->num_cu < ((int64_t)1 << 31), "too many cubes for one launch");
-  unsigned* const queue = getenv("SVK_C3D2_STATIC_ITEMS") ? nullptr : reinterpret_cast<unsigned*>(static_cast<char*>(ctx->scratch) + 96);
-  if (queue) SVK_HIP(ctx, hipMemsetAsync(queue, 0, 4, ctx->stream));
-  Conv32hParams p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, queue};
+  Conv32hParams p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, nullptr};
   void (*kern)(const Conv32hParams) = (flags & 2) ? c3d2_conv32h_kernel<true> : c3d2_conv32h_kernel<false>;
   const size_t lds = sizeof(float) * (size_t)(C32H_LDS_WORDS + C32H_XCH_FLOATS);
-  if (lds + 64 > (size_t)ctx->lds_per_cu)
-    return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "svk_c3d2_conv32t needs %zu bytes of LDS per workgroup (device: %d)", lds, ctx->lds_per_cu);
-  SVK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t items = (int64_t)n_utt * 5;
-  hipLaunchKernelGGL(kern, dim3((unsigned)std::min<int64_t>(items, ctx->num_cu)), dim3(512), lds, ctx->stream, p);
+  unsigned grid;
+  if (int rc = svk_work_queue(ctx, SVK_SLOT_CONV32_42, 1, &p.queue)) return rc;
+  if (int rc = svk_persistent_grid(ctx, "svk_c3d2_conv32t", kern, lds, 512, 1, (int64_t)n_utt * 5, &grid)) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, ctx->stream, p);
   SVK_LAUNCH_CHECK(ctx);
   return SVK_OK;
 }
@@ -1425,15 +1359,13 @@ extern "C" int svk_c3d2_conv41(svk_ctx* ctx, const float* d_in, int32_t n_utt, c
   SVK_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_wblk) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
               "buffers must be 16-byte aligned");
   SVK_REQUIRE(ctx, (int64_t)n_utt + 2 * (int64_t)ctx->num_cu < ((int64_t)1 << 31), "too many cubes for one launch");
-  unsigned* const queue = getenv("SVK_C3D2_STATIC_ITEMS") ? nullptr : reinterpret_cast<unsigned*>(static_cast<char*>(ctx->scratch) + 100);
-  if (queue) SVK_HIP(ctx, hipMemsetAsync(queue, 0, 4, ctx->stream));
-  Conv41hParams p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, queue};
+  Conv41hParams p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, nullptr};
   void (*kern)(const Conv41hParams) = (flags & 2) ? c3d2_conv41h_kernel<true> : c3d2_conv41h_kernel<false>;
   const size_t lds = sizeof(unsigned) * (size_t)C41H_LDS_WORDS;
-  if (lds + 64 > (size_t)ctx->lds_per_cu)
-    return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "svk_c3d2_conv41 needs %zu bytes of LDS per workgroup (device: %d)", lds, ctx->lds_per_cu);
-  SVK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)std::min<int64_t>(n_utt, ctx->num_cu)), dim3(512), lds, ctx->stream, p);
+  unsigned grid;
+  if (int rc = svk_work_queue(ctx, SVK_SLOT_CONV41, 1, &p.queue)) return rc;
+  if (int rc = svk_persistent_grid(ctx, "svk_c3d2_conv41", kern, lds, 512, 1, n_utt, &grid)) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, ctx->stream, p);
   SVK_LAUNCH_CHECK(ctx);
   return SVK_OK;
 }

@@ -319,24 +319,15 @@ int launch_tail(svk_ctx* ctx, const char* name, const float* d_in, int32_t n_utt
               "buffers must be 16-byte aligned");
   SVK_REQUIRE(ctx, (int64_t)n_utt < ((int64_t)1 << 24), "too many cubes for one launch");
   const size_t lds = sizeof(float) * (size_t)(2 * G::BUF);
-  if (lds > (size_t)ctx->lds_per_cu)
-    return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "%s needs %zu bytes of LDS per workgroup (device: %d)", name, lds, ctx->lds_per_cu);
   void (*kern)(const TailParams) = (flags & 2) ? c3d2_tail_kernel<L, true> : c3d2_tail_kernel<L, false>;
-  SVK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int64_t items = (int64_t)((n_utt + GROUP - 1) / GROUP) * G::ITEMS_PER_GROUP;
-  int per_cu = 1;
-  if (L::NWAVES < 8) {   // four-wave workgroups share a CU
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), G::THREADS, lds) != hipSuccess || per_cu < 1)
-      per_cu = 1;
-    per_cu = std::min(per_cu, 2);
+  const bool shares_cu = L::NWAVES < 8;   // four-wave workgroups share a CU, two at most
+  TailParams p{d_in, reinterpret_cast<const f32x2*>(d_wfrag), d_bias, d_slope, d_out, n_utt, nullptr, nullptr};
+  unsigned grid;
+  if (int rc = svk_persistent_grid(ctx, name, kern, lds, G::THREADS, shares_cu ? 2 : 1, items, &grid)) return rc;
+  if (shares_cu) {
+    if (int rc = svk_work_queue(ctx, SVK_SLOT_CONV32_42, 1, &p.queue)) return rc;
   }
-  unsigned* queue = nullptr;
-  if (per_cu > 1 && !getenv("SVK_C3D2_STATIC_ITEMS")) {   // a slot of the handle's 256-byte scratch, zeroed in stream order
-    queue = reinterpret_cast<unsigned*>(static_cast<char*>(ctx->scratch) + 96);
-    SVK_HIP(ctx, hipMemsetAsync(queue, 0, 4, ctx->stream));
-  }
-  TailParams p{d_in, reinterpret_cast<const f32x2*>(d_wfrag), d_bias, d_slope, d_out, n_utt, queue, nullptr};
-  const unsigned grid = (unsigned)std::min<int64_t>(items, (int64_t)per_cu * ctx->num_cu);
 #ifdef SVK_TUNING
   const bool want_stamps = getenv("SVK_C3D2_STAMPS") != nullptr;
   const size_t stamp_bytes = (size_t)grid * L::NWAVES * 4 * sizeof(unsigned long long);

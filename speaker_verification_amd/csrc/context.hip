@@ -22,7 +22,7 @@ int svk_create(int device_id, svk_ctx** out) {
   ctx->num_cu = prop.multiProcessorCount;
   ctx->clock_khz = prop.clockRate;
   ctx->lds_per_cu = (int)prop.maxSharedMemoryPerMultiProcessor;
-  if (hipMalloc(&ctx->scratch, 256) != hipSuccess) {
+  if (hipMalloc(&ctx->scratch, SVK_SCRATCH_BYTES) != hipSuccess) {
     delete ctx;
     return SVK_ERR_OOM;
   }

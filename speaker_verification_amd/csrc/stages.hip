@@ -1185,7 +1185,7 @@ int svk_log_power(svk_ctx* ctx, float* d_power, int64_t n, int32_t normalize) {
   SVK_REQUIRE(ctx, n >= 0, "n negative");
   if (n == 0) return SVK_OK;
   SVK_REQUIRE(ctx, d_power, "NULL buffer");
-  unsigned* gmax = normalize ? reinterpret_cast<unsigned*>(ctx->scratch) : nullptr;
+  unsigned* gmax = normalize ? reinterpret_cast<unsigned*>(static_cast<char*>(ctx->scratch) + SVK_SLOT_LOG_POWER) : nullptr;
   if (gmax) SVK_HIP(ctx, hipMemsetAsync(gmax, 0, sizeof(unsigned), ctx->stream));  // flip() of anything is > 0
   hipLaunchKernelGGL(log_power_kernel, dim3(capped_grid(ctx, n, 256)), dim3(256), 0, ctx->stream, d_power, n, gmax);
   SVK_LAUNCH_CHECK(ctx);

@@ -2,8 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 #include "../../include/svk.h"
@@ -14,13 +16,25 @@ struct svk_ctx {
   int num_cu = 256;
   int clock_khz = 0;
   int lds_per_cu = 160 * 1024;
-  void* scratch = nullptr;  // 256 bytes of device memory for tiny reductions (svk_log_power)
+  void* scratch = nullptr;  // SVK_SCRATCH_BYTES of device memory: counters that one launch zeroes and uses (map below)
   void* work = nullptr;     // grow-only device workspace owned by the handle (row norms of svk_cosine_scores)
   size_t work_bytes = 0;
   void* comm = nullptr;     // RCCL communicator (svk_comm_init), or NULL
   int comm_ranks = 0, comm_rank = 0;
   char err[512] = {0};
 };
+
+// ctx->scratch, by byte offset.  Each slot is zeroed in stream order by the launch that uses it, so two entry points may share
+// one as long as they run on the handle's stream (conv3_2 and conv4_2 do).
+constexpr size_t SVK_SCRATCH_BYTES = 256;
+constexpr size_t SVK_SLOT_LOG_POWER = 0;       // svk_log_power: the running maximum (1 word)
+constexpr size_t SVK_SLOT_STAGE2 = 64;         // svk_c3d2_stage2: the work-item counters of conv2_1, conv2_2 (2 words)
+constexpr size_t SVK_SLOT_CONV31 = 80;         // svk_c3d2_conv31 (1 word)
+constexpr size_t SVK_SLOT_CONV32_42 = 96;      // svk_c3d2_conv32t; svk_c3d2_conv42 when its workgroups share a CU (1 word)
+constexpr size_t SVK_SLOT_CONV41 = 100;        // svk_c3d2_conv41 (1 word)
+constexpr size_t SVK_SLOT_STAGE1 = 112;        // svk_c3d2_stage1 / svk_c3d2_stage1_c3 (1 word)
+static_assert(SVK_SLOT_STAGE2 + 8 <= SVK_SLOT_CONV31 && SVK_SLOT_STAGE1 + 4 <= SVK_SCRATCH_BYTES,
+              "the scratch slots overlap or do not fit the handle's scratch");
 
 inline int svk_fail(svk_ctx* ctx, int code, const char* fmt, ...) {
   if (ctx) {
@@ -69,6 +83,36 @@ inline int svk_ensure_work(svk_ctx* ctx, size_t bytes) {
       return svk_fail((ctx), SVK_ERR_HIP, "kernel launch failed: %s (%s:%d)",                  \
                       hipGetErrorString(e_), __FILE__, __LINE__);                              \
   } while (0)
+
+// The work-item counters of a persistent network kernel: `words` counters at byte `slot` of the handle's scratch, zeroed in
+// stream order -- or nullptr (items at a fixed stride) while SVK_C3D2_STATIC_ITEMS is set, read at every call: the determinism
+// tests set it at run time.
+inline int svk_work_queue(svk_ctx* ctx, size_t slot, int words, unsigned** queue) {
+  *queue = nullptr;
+  if (getenv("SVK_C3D2_STATIC_ITEMS")) return SVK_OK;
+  *queue = reinterpret_cast<unsigned*>(static_cast<char*>(ctx->scratch) + slot);
+  SVK_HIP(ctx, hipMemsetAsync(*queue, 0, sizeof(unsigned) * words, ctx->stream));
+  return SVK_OK;
+}
+
+// Launch width of a persistent network kernel: checks that `lds` bytes of dynamic LDS fit a CU beside the kernel's static LDS,
+// raises the kernel's limit to them, and returns in *grid the `items` clamped to the workgroups resident at once -- one per CU
+// when max_per_cu is 1, else what the occupancy calculator allows for `threads`-wide workgroups, at most max_per_cu.
+template <class P>
+int svk_persistent_grid(svk_ctx* ctx, const char* name, void (*kern)(P), size_t lds, int threads, int max_per_cu, int64_t items,
+                        unsigned* grid) {
+  if (lds + 64 > (size_t)ctx->lds_per_cu)
+    return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "%s needs %zu bytes of LDS per workgroup (device: %d)", name, lds, ctx->lds_per_cu);
+  const void* f = reinterpret_cast<const void*>(kern);
+  SVK_HIP(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  int per_cu = 1;
+  if (max_per_cu > 1) {
+    SVK_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, threads, lds));
+    per_cu = std::max(1, std::min(per_cu, max_per_cu));
+  }
+  *grid = (unsigned)std::min<int64_t>(items, (int64_t)per_cu * ctx->num_cu);
+  return SVK_OK;
+}
 
 // 64-lane wave sum; every lane gets the total.
 __device__ __forceinline__ float wave_sum(float v) {

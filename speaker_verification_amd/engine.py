@@ -453,118 +453,94 @@ class Engine:
         return out
 
     def c3d2_stage1(self, feat, crop_idx, tables, crop_frames=80):
-        """svk_c3d2_stage1: feature rows + crop starts -> the activation after C3D2's first block (conv1_1, conv1_2,
-        pool1 with their BN + PReLU): [n, 16, 36, 18, 16] f32, channels last.  Two-piece f16 products on
+        """svk_c3d2_stage1: feature rows [n, T, 40] + crop starts [n, 20] -> the activation after C3D2's first block (conv1_1,
+        conv1_2, pool1 with their BN + PReLU): [n, 16, 36, 18, 16] f32, channels last.  Two-piece f16 products on
         v_mfma_f32_16x16x32_f16 (x = h + l, three piece products per f32 product, f32 accumulation: ~1e-6 of the scale from the
-        f32 form); tables: `FusedEmbedder.stage1_tables()`."""
+        f32 form); tables: `FusedEmbedder.stage1_tables()`.  The tables of a three-channel model (conv1_1 block [3, 2, 64, 8])
+        run svk_c3d2_stage1_c3 on feature rows [n, 3, T, 40] (static, delta, delta-delta) instead: the same output layout."""
         torch = _torch()
         feat = self.to_device(feat, torch.float32)
         idx = self.to_device(crop_idx, torch.int32)
-        n, T, Cc = feat.shape
-        w1frag, bias1, slope1, w2frag, bias2, slope2 = tables[:6]
-        if w1frag.dtype != torch.float16 or w2frag.dtype != torch.float16 or tuple(w1frag.shape) != (2, 64, 8) or tuple(w2frag.shape) != (14, 2, 64, 8):
-            raise ValueError("c3d2_stage1 wants the half-pair weight blocks of FusedEmbedder.stage1_tables()")
-        slope01 = bool(tables[6]) if len(tables) > 6 else False          # every slope in [0, 1]: the two-instruction PReLU
-        out = torch.empty((n, 16, 36, 18, 16), dtype=torch.float32, device=self.device)
-        self._stream()
-        check(self.lib.svk_c3d2_stage1(self.ctx, self._ptr(feat), n, T, Cc, self._ptr(idx), idx.shape[1], crop_frames,
-                                       self._ptr(w1frag), self._ptr(bias1), self._ptr(slope1), self._ptr(w2frag), self._ptr(bias2),
-                                       self._ptr(slope2), 2 if slope01 else 0, self._ptr(out)), self.ctx)
-        return out
-
-    def c3d2_stage1_c3(self, feat3, crop_idx, tables, crop_frames=80):
-        """svk_c3d2_stage1_c3: the first block of the three-channel C3D2 (conv1_1 3 -> 16): feature rows [n, 3, T, 40]
-        (static, delta, delta-delta) + crop starts [n, 20] -> [n, 16, 36, 18, 16] f32, the layout of c3d2_stage1's output;
-        tables: `FusedEmbedder.stage1_tables()` of a three-channel model."""
-        torch = _torch()
-        feat3 = self.to_device(feat3, torch.float32)
-        idx = self.to_device(crop_idx, torch.int32)
-        if feat3.dim() != 4 or feat3.shape[1] != 3:
-            raise ValueError("c3d2_stage1_c3 wants feature rows [n, 3, T, cols], got %s" % (tuple(feat3.shape),))
-        n, _, T, Cc = feat3.shape
+        three = tuple(tables[0].shape) == (3, 2, 64, 8)
+        if feat.dim() != (4 if three else 3) or (three and feat.shape[1] != 3):
+            raise ValueError("these stage-1 tables take feature rows %s, got %s"
+                             % ("[n, 3, T, cols]" if three else "[n, T, cols]", tuple(feat.shape)))
+        n, T, Cc = feat.shape[0], feat.shape[-2], feat.shape[-1]
         if idx.dim() != 2 or idx.shape[0] != n:
             raise ValueError("crop_idx must be [n, n_crops] for the n = %d cubes, got %s" % (n, tuple(idx.shape)))
-        w1frag, bias1, slope1, w2frag, bias2, slope2 = tables[:6]
-        if w1frag.dtype != torch.float16 or w2frag.dtype != torch.float16 or tuple(w1frag.shape) != (3, 2, 64, 8) or tuple(w2frag.shape) != (14, 2, 64, 8):
-            raise ValueError("c3d2_stage1_c3 wants the half-pair weight blocks of a three-channel FusedEmbedder.stage1_tables()")
-        slope01 = bool(tables[6]) if len(tables) > 6 else False
+        layers = self._c3d2_layers(tables, ((3, 2, 64, 8) if three else (2, 64, 8), (14, 2, 64, 8)), torch.float16, 16)
         out = torch.empty((n, 16, 36, 18, 16), dtype=torch.float32, device=self.device)
         self._stream()
-        check(self.lib.svk_c3d2_stage1_c3(self.ctx, self._ptr(feat3), n, T, Cc, self._ptr(idx), idx.shape[1], crop_frames,
-                                          self._ptr(w1frag), self._ptr(bias1), self._ptr(slope1), self._ptr(w2frag),
-                                          self._ptr(bias2), self._ptr(slope2), 2 if slope01 else 0, self._ptr(out)), self.ctx)
+        fn = self.lib.svk_c3d2_stage1_c3 if three else self.lib.svk_c3d2_stage1
+        check(fn(self.ctx, self._ptr(feat), n, T, Cc, self._ptr(idx), idx.shape[1], crop_frames, *layers, self._ptr(out)), self.ctx)
+        return out
+
+    def _c3d2_layers(self, tables, w_shapes, w_dtype, co):
+        """The operand tables of a network entry point -- (weight blocks, bias, slope) per layer, then optionally whether every
+        slope lies in [0, 1] -- checked against the blocks' shapes and the `co` output channels of each layer (the kernels read
+        them unchecked); -> their pointers and the flags, in C-ABI order."""
+        f32, ptr = _torch().float32, self._ptr
+        args = []
+        for i, w_shape in enumerate(w_shapes):
+            wfrag, bias, slope = tables[3 * i], tables[3 * i + 1], tables[3 * i + 2]
+            if wfrag.shape != w_shape or wfrag.dtype != w_dtype or not wfrag.is_contiguous():
+                raise ValueError("weight blocks: want %s of %s, got %s of %s" % (w_shape, w_dtype, tuple(wfrag.shape), wfrag.dtype))
+            if bias.numel() != co or slope.numel() != co or bias.dtype != f32 or slope.dtype != f32:
+                raise ValueError("bias / slope: want %d float32 values each" % co)
+            args += (ptr(wfrag), ptr(bias), ptr(slope))
+        k = 3 * len(w_shapes)
+        args.append(2 if len(tables) > k and tables[k] else 0)      # bit 1: every slope in [0, 1], the two-instruction PReLU
+        return args
+
+    def _c3d2_block(self, fn, act, tables, out_shape, w_shapes, co, w_dtype=None, scratch_shape=None):
+        """fn(ctx, act, n, (weight blocks, bias, slope) per layer, flags[, scratch], out) -> out [n, *out_shape] f32
+        (weight blocks of f16 unless `w_dtype`)."""
+        torch = _torch()
+        n = act.shape[0]
+        args = self._c3d2_layers(tables, w_shapes, w_dtype or torch.float16, co)
+        if scratch_shape is not None:      # held until the launch is enqueued: `out` must not reuse its memory
+            scratch = torch.empty((n,) + scratch_shape, dtype=torch.float32, device=self.device)
+            args.append(self._ptr(scratch))
+        out = torch.empty((n,) + out_shape, dtype=torch.float32, device=self.device)
+        self._stream()
+        check(fn(self.ctx, self._ptr(act), n, *args, self._ptr(out)), self.ctx)
         return out
 
     def c3d2_stage2(self, act1, tables):
         """svk_c3d2_stage2: [n, 16, 36, 18, 16] (svk_c3d2_stage1's output) -> conv2_1 -> conv2_2 -> pool2 with their
         BN + PReLU -> [n, 12, 15, 7, 32] f32 (channels last), both convolutions through two-piece f16 products."""
-        torch = _torch()
-        n = act1.shape[0]
         if tuple(act1.shape[1:]) != (16, 36, 18, 16) or not act1.is_contiguous():
             raise ValueError("c3d2_stage2 wants the activation [n, 16, 36, 18, 16]")
-        w21, b21, s21, w22, b22, s22 = tables[:6]
-        if w21.dtype != torch.float16 or w22.dtype != torch.float16 or tuple(w21.shape) != (2, 6, 2, 64, 8) or tuple(w22.shape) != (2, 24, 2, 64, 8):
-            raise ValueError("c3d2_stage2 wants the half-pair weight blocks of FusedEmbedder.stage2_tables()")
-        slope01 = bool(tables[6]) if len(tables) > 6 else False
-        act2 = torch.empty((n, 14, 36, 14, 32), dtype=torch.float32, device=self.device)   # scratch: the 14 columns of conv2_1 that pool2 leaves alive
-        out = torch.empty((n, 12, 15, 7, 32), dtype=torch.float32, device=self.device)
-        self._stream()
-        check(self.lib.svk_c3d2_stage2(self.ctx, self._ptr(act1), n, self._ptr(w21), self._ptr(b21), self._ptr(s21),
-                                       self._ptr(w22), self._ptr(b22), self._ptr(s22),
-                                       2 if slope01 else 0,
-                                       self._ptr(act2), self._ptr(out)), self.ctx)
-        return out
+        # scratch: the 14 columns of conv2_1 that pool2 leaves alive
+        return self._c3d2_block(self.lib.svk_c3d2_stage2, act1, tables, (12, 15, 7, 32), ((2, 6, 2, 64, 8), (2, 24, 2, 64, 8)), 32,
+                                scratch_shape=(14, 36, 14, 32))
 
     def c3d2_conv31(self, act, tables):
         """svk_c3d2_conv31: [n, 12, 15, 7, 32] (svk_c3d2_stage2's output) -> conv3_1 + BN + PReLU -> chunked, column-major
         [n, 10 d, 8 chunks, 5 w, 15 h, 8] f32: what svk_c3d2_conv32t stages from."""
-        torch = _torch()
-        n = act.shape[0]
         if tuple(act.shape[1:]) != (12, 15, 7, 32) or not act.is_contiguous():
             raise ValueError("c3d2_conv31 wants the activation [n, 12, 15, 7, 32]")
-        wfrag, bias, slope = tables[:3]
-        slope01 = bool(tables[3]) if len(tables) > 3 else False
-        out = torch.empty((n, 10, 8, 5, 15, 8), dtype=torch.float32, device=self.device)
-        self._stream()
-        check(self.lib.svk_c3d2_conv31(self.ctx, self._ptr(act), n, self._ptr(wfrag), self._ptr(bias), self._ptr(slope),
-                                       2 if slope01 else 0, self._ptr(out)), self.ctx)
-        return out
+        return self._c3d2_block(self.lib.svk_c3d2_conv31, act, tables, (10, 8, 5, 15, 8), ((4, 9, 2, 64, 8),), 64)
 
     def c3d2_conv32t(self, act, tables):
         """svk_c3d2_conv32t: chunked, column-major [n, 10, 8, 5, 15, 8] (svk_c3d2_conv31's output) -> conv3_2 + BN + PReLU ->
         chunked [n, 8 d, 8 chunks, 45 = 9 h x 5 w, 8] (the shape of the last block: M tile = one position of 16 cubes)."""
         if tuple(act.shape[1:]) != (10, 8, 5, 15, 8) or not act.is_contiguous():
             raise ValueError("c3d2_conv32t wants the chunked activation [n, 10, 8, 5, 15, 8]")
-        return self._c3d2_tail_conv(self.lib.svk_c3d2_conv32t, act, tables, (8, 8, 45, 8), (4, 2, 21, 2, 64, 8), "float16")
-
-    def _c3d2_tail_conv(self, fn, act, tables, out_shape, w_shape, w_dtype):
-        torch = _torch()
-        n = act.shape[0]
-        wfrag, bias, slope = tables[:3]
-        if tuple(wfrag.shape) != w_shape or wfrag.dtype != getattr(torch, w_dtype) or not wfrag.is_contiguous():
-            raise ValueError("weight blocks: want %s of %s, got %s of %s" % (w_shape, w_dtype, tuple(wfrag.shape), wfrag.dtype))
-        co = out_shape[1] * 8
-        if bias.numel() != co or slope.numel() != co or bias.dtype != torch.float32 or slope.dtype != torch.float32:
-            raise ValueError("bias / slope: want %d float32 values each" % co)
-        slope01 = bool(tables[3]) if len(tables) > 3 else False
-        out = torch.empty((n,) + out_shape, dtype=torch.float32, device=self.device)
-        self._stream()
-        check(fn(self.ctx, self._ptr(act), n, self._ptr(wfrag), self._ptr(bias), self._ptr(slope), 2 if slope01 else 0,
-                 self._ptr(out)), self.ctx)
-        return out
+        return self._c3d2_block(self.lib.svk_c3d2_conv32t, act, tables, (8, 8, 45, 8), ((4, 2, 21, 2, 64, 8),), 64)
 
     def c3d2_conv41(self, act, tables):
         """svk_c3d2_conv41: chunked [n, 8 d, 8 chunks, 45, 8] (svk_c3d2_conv32t's output) -> conv4_1 + BN + PReLU
         -> chunked [n, 6 d, 16 chunks, 27 = 9 h x 3 w, 8]."""
         if tuple(act.shape[1:]) != (8, 8, 45, 8) or not act.is_contiguous():
             raise ValueError("c3d2_conv41 wants the chunked activation [n, 8, 8, 45, 8]")
-        return self._c3d2_tail_conv(self.lib.svk_c3d2_conv41, act, tables, (6, 16, 27, 8), (8, 9, 2, 2, 64, 8), "float16")
+        return self._c3d2_block(self.lib.svk_c3d2_conv41, act, tables, (6, 16, 27, 8), ((8, 9, 2, 2, 64, 8),), 128)
 
     def c3d2_conv42(self, act, tables):
         """svk_c3d2_conv42: chunked [n, 6, 16, 27, 8] -> conv4_2 + BN + PReLU -> chunked [n, 4 d, 16 chunks, 9 = 3 h x 3 w, 8]."""
         if tuple(act.shape[1:]) != (6, 16, 27, 8) or not act.is_contiguous():
             raise ValueError("c3d2_conv42 wants the chunked activation [n, 6, 16, 27, 8]")
-        return self._c3d2_tail_conv(self.lib.svk_c3d2_conv42, act, tables, (4, 16, 9, 8), (8, 16, 7, 4, 64, 2), "float32")
+        return self._c3d2_block(self.lib.svk_c3d2_conv42, act, tables, (4, 16, 9, 8), ((8, 16, 7, 4, 64, 2),), 128, _torch().float32)
 
     def c3d2_fc5(self, act, tables):
         """svk_c3d2_fc5: chunked [n, 4, 16, 9, 8] (= [n, 4 608]) -> FC5 -> [n, 128] embeddings."""

@@ -134,6 +134,11 @@ class FusedEmbedder:
     def __init__(self, model):
         self.device = model.conv1_1.weight.device       # tables are built where the weights live; kernels need the GPU
         self.num_channels = int(model.conv1_1.weight.shape[1])
+        if self.num_channels not in (1, 3) or tuple(model.FC5.weight.shape) != (EMBED_DIM, _FLAT) or any(
+                tuple(getattr(model, "conv" + tag).weight.shape) != (cout, self.num_channels if cin is None else cin) + kernel
+                or tuple(getattr(model, "conv" + tag).stride) != stride for tag, cin, cout, kernel, stride, _ in _LAYERS):
+            raise ValueError("libsvk's network kernels are built for C3D2's layers on one- or three-channel 20 x 80 x 40 cubes "
+                             "(model.py:110-139); this model's layers differ")
         self._eng = None
         self.stages = []
         self.act_scale = []     # per layer: the power of two per channel its output is carried in (all ones for an ordinary checkpoint)
@@ -161,22 +166,21 @@ class FusedEmbedder:
                 b = b * s_out
                 if s_in is not None:
                     w = w / s_in.view(1, -1, 1, 1, 1)
-                self.stages.append((w.contiguous(), b.contiguous(), act.weight.detach().clone(), tuple(conv.stride), pool, False))
+                self.stages.append((w.contiguous(), b.contiguous(), act.weight.detach().clone(), tuple(conv.stride), pool))
                 self.act_scale.append(s_out)
                 s_in = s_out
-            self.fc_w = model.FC5.weight.detach().clone()
-            if self.fc_w.shape[1] % s_in.numel() == 0:       # model.py:168 flattens NCDHW: column = channel * positions + position
-                self.fc_w = (self.fc_w.view(self.fc_w.shape[0], s_in.numel(), -1) / s_in.view(1, -1, 1)).reshape(self.fc_w.shape).contiguous()
+            # model.py:168 flattens NCDHW: column = channel * positions + position
+            fc_w = model.FC5.weight.detach()
+            self.fc_w = (fc_w.view(EMBED_DIM, s_in.numel(), -1) / s_in.view(1, -1, 1)).reshape(fc_w.shape).contiguous()
             self.fc_b = model.FC5.bias.detach().clone()
             for w, b, *_ in self.stages:
                 if not (bool(torch.isfinite(w).all()) and bool(torch.isfinite(b).all()) and float(w.abs().max()) < 65504.0):
                     raise ValueError("a BatchNorm-folded weight of this checkpoint is not finite or exceeds 65 504: outside what "
                                      "libsvk's half-pair operands represent")
-        tables = (self.stage1_tables(), self.stage2_tables(), self.conv31_tables(), self.conv32t_tables(),
-                  self.conv41_tables(), self.conv42_tables(), self.fc5_tables())
-        if any(t is None for t in tables):
-            raise ValueError("libsvk's network kernels are built for C3D2's layers on one- or three-channel 20 x 80 x 40 cubes "
-                             "(model.py:110-139); this model's layers differ")
+            st = self.stages
+            self._tables = {"stage1": _stage1_tables(st[0], st[1]), "stage2": _stage2_tables(st[2], st[3]),
+                            "conv31": _conv31_tables(st[4]), "conv32t": _conv32t_tables(st[5]), "conv41": _conv41_tables(st[6]),
+                            "conv42": _conv42_tables(st[7]), "fc5": _fc5_tables(self.fc_w, self.fc_b)}
         self._starts = {}
 
     @property
@@ -211,8 +215,7 @@ class FusedEmbedder:
         if feat.dim() != want or (want == 4 and feat.shape[1] != self.num_channels):
             raise ValueError("this %d-channel model embeds feature rows of shape %s, got %s"
                              % (self.num_channels, "[n, T, 40]" if want == 3 else "[n, 3, T, 40]", tuple(feat.shape)))
-        stage1 = eng.c3d2_stage1 if self.num_channels == 1 else eng.c3d2_stage1_c3
-        y = run("stage1", lambda: stage1(feat, crop_idx, self.stage1_tables()))
+        y = run("stage1", lambda: eng.c3d2_stage1(feat, crop_idx, self.stage1_tables()))
         z = run("stage2", lambda: eng.c3d2_stage2(y, self.stage2_tables()))
         y = run("conv3_1", lambda: eng.c3d2_conv31(z, self.conv31_tables()))
         y = run("conv3_2", lambda: eng.c3d2_conv32t(y, self.conv32t_tables()))
@@ -244,263 +247,143 @@ class FusedEmbedder:
             out[lo:hi] = self.embed_features(rows[lo:hi], self.crop_starts(hi - lo, x.device))
         return out
 
-    # ---- the first block (conv1_1 .. pool1) as one libsvk kernel ------------------------------------
+    # ---- the operand tables of the seven entry points, built once in __init__ (layouts: the builders below) --------------
     def stage1_tables(self):
-        """Operand blocks of `svk_c3d2_stage1` (two-piece f16 products; include/svk.h): the BN-folded weights of conv1_1 /
-        conv1_2 split into halves H = f16(w), L = f16(w - H) and laid out in the lane order of v_mfma_f32_16x16x32_f16's A
-        operand (lane l = (co = l & 15, kk = l >> 4), eight halves: K = 8 kk + e), or None when the first block is not C3D2's
-        (1 or 3 -> 16 k(3,1,5); 16 -> 16 k(3,9,1) stride (1,2,1); pool).
-          w1blk [2][64][8]      : conv1_1, tap t = 8 (kk & 1) + e (t = 5 kd + kw; 15 -> 0): H for every kk | L for kk < 2, 0 above
-                 [3][2][64][8]  : the three-channel conv1_1 (`svk_c3d2_stage1_c3`): that block for each input channel -- the 45
-                                  taps padded to 48, tap 15 of every channel the zero pad
-          w2blk [14][2][64][8]  : conv1_2, tap pairs (a | b): ci = 8 (kk & 1) + e at tap a (kk < 2) / b (kk >= 2); H | L;
-                                  pair 13 is tap (2, 8) alone against an [h | l] fragment: H at every kk | L for kk < 2, 0 above"""
-        hit = getattr(self, "_stage1", False)
-        if hit is not False:
-            return hit
-        self._stage1 = None
-        (w1, b1, s1, st1, p1, _), (w2, b2, s2, st2, p2, _) = self.stages[0], self.stages[1]
-        if (tuple(w1.shape) not in ((16, 1, 3, 1, 5), (16, 3, 3, 1, 5)) or tuple(w2.shape) != (16, 16, 3, 9, 1) or tuple(st1) != (1, 1, 1)
-                or tuple(st2) != (1, 2, 1) or p1 or not p2):
-            return None
-        dev = w1.device
-
-        def halves(w):
-            h = w.to(torch.float16)
-            return h, (w - h.to(torch.float32)).to(torch.float16)
-
-        lane = torch.arange(64, device=dev)
-        co, kk = lane & 15, lane >> 4
-        e = torch.arange(8, device=dev)
-        t = 8 * (kk & 1)[:, None] + e[None, :]                                                    # [64][8]
-        blocks = []
-        for ch in range(w1.shape[1]):
-            w1c = torch.cat([w1[:, ch].contiguous().view(16, 15), torch.zeros((16, 1), device=dev)], 1)   # [co][t], t = 15: zero
-            h1, l1 = halves(w1c[co[:, None], t])
-            blocks.append(torch.stack([h1, torch.where((kk < 2)[:, None], l1, torch.zeros_like(l1))]))  # [2][64][8]
-        w1blk = blocks[0] if len(blocks) == 1 else torch.stack(blocks)
-        w2c = w2.contiguous()[:, :, :, :, 0]                                                      # [co][ci][kd][kh]
-        pairs = [((p // 4, 2 * (p % 4)), (p // 4, 2 * (p % 4) + 1)) for p in range(12)] + [((0, 8), (1, 8)), ((2, 8), None)]
-        ci = 8 * (kk & 1)[:, None] + e[None, :]
-        w2blk = torch.zeros((14, 2, 64, 8), dtype=torch.float16, device=dev)
-        for p, (ta, tb) in enumerate(pairs):
-            wa = w2c[co[:, None], ci, ta[0], ta[1]]
-            if tb is None:       # the last tap alone: the kernel reads it as [h | l], so H for every kk and L against the h half only
-                h, l = halves(wa)
-                l = torch.where((kk < 2)[:, None], l, torch.zeros_like(l))
-            else:
-                h, l = halves(torch.where((kk < 2)[:, None], wa, w2c[co[:, None], ci, tb[0], tb[1]]))
-            w2blk[p, 0], w2blk[p, 1] = h, l
-        slope01 = bool(((s1 >= 0) & (s1 <= 1)).all() and ((s2 >= 0) & (s2 <= 1)).all())   # one host read per checkpoint
-        self._stage1 = (w1blk.contiguous(), b1.contiguous(),
-                        s1.expand(16).contiguous() if s1.numel() == 1 else s1.contiguous(),
-                        w2blk.contiguous(), b2.contiguous(),
-                        s2.expand(16).contiguous() if s2.numel() == 1 else s2.contiguous(), slope01)
-        return self._stage1
+        return self._tables["stage1"]
 
     def stage2_tables(self):
-        """Operand fragments of `svk_c3d2_stage2` (conv2_1 16 -> 32 k(3,1,4); conv2_2 32 -> 32 k(3,8,1) stride
-        (1,2,1) + pool), BN folded, or None when the layers differ:
-          w21blk  [2 nt][6][2][64][8] halves: conv2_1 through two-piece f16 products (H | L blocks of tap pairs; see the code)
-          w22blk  [2 nt][24][2][64][8] halves: conv2_2, one tap per K = 32 block (H | L)"""
-        hit = getattr(self, "_stage2", False)
-        if hit is not False:
-            return hit
-        self._stage2 = None
-        (w1, b1, s1, st1, p1, _), (w2, b2, s2, st2, p2, _) = self.stages[2], self.stages[3]
-        if (tuple(w1.shape) != (32, 16, 3, 1, 4) or tuple(w2.shape) != (32, 32, 3, 8, 1) or tuple(st1) != (1, 1, 1)
-                or tuple(st2) != (1, 2, 1) or p1 or not p2):
-            return None
-        dev = w1.device
-        lane = torch.arange(64, device=dev)
-        ch, kq = lane & 15, lane >> 4
-        a = w1.contiguous()[:, :, :, 0, :]                                   # [co][ci][kd][kw]
-        # conv2_1 runs two-piece f16 products (see stage1_tables): [2 nt][6 pairs][2: H | L][64 lanes][8 halves], pair = 2 kd + kw / 2,
-        # lane (co = 16 nt + (l & 15), kk = l >> 4): element e = W[co][ci = 8 (kk & 1) + e][kd][kw + (kk >= 2)]
-        e8 = torch.arange(8, device=dev)
-        ci8 = 8 * (kq & 1)[:, None] + e8[None, :]
-        f21 = torch.empty((2, 6, 2, 64, 8), dtype=torch.float16, device=dev)
-        for nt in range(2):
-            for kd in range(3):
-                for kw2 in range(2):
-                    kw = 2 * kw2 + (kq >= 2).long()
-                    w = a[(16 * nt + ch)[:, None], ci8, kd, kw[:, None]]
-                    h = w.to(torch.float16)
-                    f21[nt, 2 * kd + kw2, 0] = h
-                    f21[nt, 2 * kd + kw2, 1] = (w - h.to(torch.float32)).to(torch.float16)
-        bmat = w2.contiguous()[:, :, :, :, 0]                                # [co][ci][kd][kh]
-        # conv2_2: [2 nt][24 taps][2: H | L][64 lanes][8 halves], tap = 8 kd + kh, element e = W[co][ci = 8 kk + e][kd][kh] (K = 32 = one tap)
-        ci32 = 8 * kq[:, None] + e8[None, :]
-        f22 = torch.empty((2, 24, 2, 64, 8), dtype=torch.float16, device=dev)
-        for nt in range(2):
-            for kd in range(3):
-                for kh in range(8):
-                    w = bmat[(16 * nt + ch)[:, None], ci32, kd, kh]
-                    h = w.to(torch.float16)
-                    f22[nt, 8 * kd + kh, 0] = h
-                    f22[nt, 8 * kd + kh, 1] = (w - h.to(torch.float32)).to(torch.float16)
-
-        def per_channel(t, n):
-            return t.expand(n).contiguous() if t.numel() == 1 else t.contiguous()
-        slope01 = bool(((s1 >= 0) & (s1 <= 1)).all() and ((s2 >= 0) & (s2 <= 1)).all())   # one host read per checkpoint
-        self._stage2 = (f21.contiguous(), b1.contiguous(), per_channel(s1, 32), f22.contiguous(), b2.contiguous(),
-                        per_channel(s2, 32), slope01)
-        return self._stage2
+        return self._tables["stage2"]
 
     def conv31_tables(self):
-        """Operand fragments of `svk_c3d2_conv31` (conv3_1: 32 -> 64, k(3,1,3), stride 1, no pool), BN folded, or None
-        when the layer differs:  wblk [4 nt][9][2: H | L][64][8 halves]: lane (co = 16 nt + (l & 15), kk = l >> 4):
-        W[co][8 kk + e][kd][kw], tap 3 kd + kw (two-piece f16 products, see stage1_tables)."""
-        hit = getattr(self, "_conv31", False)
-        if hit is not False:
-            return hit
-        self._conv31 = None
-        if len(self.stages) < 5:
-            return None
-        w, b, sl, st, pool, _ = self.stages[4]
-        if tuple(w.shape) != (64, 32, 3, 1, 3) or tuple(st) != (1, 1, 1) or pool:
-            return None
-        dev = w.device
-        lane = torch.arange(64, device=dev)
-        ch, kq = lane & 15, lane >> 4
-        a = w.contiguous()[:, :, :, 0, :]                                    # [co][ci][kd][kw]
-        ci = 8 * kq[:, None] + torch.arange(8, device=dev)[None, :]          # K = 32 = the 32 input channels of one tap
-        frag = torch.empty((4, 9, 2, 64, 8), dtype=torch.float16, device=dev)
-        for nt in range(4):
-            for kd in range(3):
-                for kw in range(3):
-                    wv = a[(16 * nt + ch)[:, None], ci, kd, kw]
-                    h = wv.to(torch.float16)
-                    frag[nt, 3 * kd + kw, 0] = h
-                    frag[nt, 3 * kd + kw, 1] = (wv - h.to(torch.float32)).to(torch.float16)
-        slope = sl.expand(64).contiguous() if sl.numel() == 1 else sl.contiguous()
-        self._conv31 = (frag.contiguous(), b.contiguous(), slope, bool(((sl >= 0) & (sl <= 1)).all()))
-        return self._conv31
-
-    @staticmethod
-    def _depth_transformed(w):
-        """Winograd F(2, 3) weight transform along depth of a BN-folded Conv3d weight [co][ci][3][kh][kw] ->
-        [4 k][co][ci][kh][kw]: G0 = g0, G1 = ((g0 + g2) + g1) / 2, G2 = ((g0 + g2) - g1) / 2, G3 = g2 (f32, the same
-        expressions the kernels of csrc/c3d2.hip evaluate in their prologues)."""
-        g0, g1, g2 = w[:, :, 0], w[:, :, 1], w[:, :, 2]
-        return torch.stack((g0, 0.5 * ((g0 + g2) + g1), 0.5 * ((g0 + g2) - g1), g2))
-
-    def _tail_conv_tables(self, li, shape, taps_axis):
-        """Operand fragments of `svk_c3d2_conv42` from stage `li`, or None when the layer differs:
-        wfrag [8 nt][chunks of 8 input channels][taps][4 k][64 lanes][2]: lane (co = 16 nt + (l & 15), kk = l >> 4),
-        element e = G_k[co][8 chunk + 2 kk + e][tap]."""
-        if len(self.stages) <= li:
-            return None
-        w, b, sl, st, pool, _ = self.stages[li]
-        if tuple(w.shape) != shape or tuple(st) != (1, 1, 1) or pool:
-            return None
-        dev = w.device
-        co, ci = shape[0], shape[1]
-        g = self._depth_transformed(w.contiguous())                          # [4][co][ci][kh][kw]
-        g = g[:, :, :, :, 0] if taps_axis == "h" else g[:, :, :, 0, :]        # [4][co][ci][taps]
-        taps = g.shape[3]
-        lane = torch.arange(64, device=dev)
-        n_, kq = lane & 15, lane >> 4
-        # frag[nt][chunk][tap][k][lane][e] = g[k][16 nt + n_][8 chunk + 2 kq + e][tap]
-        frag = torch.empty((co // 16, ci // 8, taps, 4, 64, 2), dtype=torch.float32, device=dev)
-        gg = g.view(4, co // 16, 16, ci // 8, 4, 2, taps)                    # [k][nt][n][chunk][kq][e][tap]
-        frag.copy_(gg[:, :, n_, :, kq].permute(2, 3, 5, 1, 0, 4))            # advanced indices (n, kq) -> leading lane axis
-        slope = sl.expand(co).contiguous() if sl.numel() == 1 else sl.contiguous()
-        return (frag.contiguous(), b.contiguous(), slope, bool(((sl >= 0) & (sl <= 1)).all()))
+        return self._tables["conv31"]
 
     def conv32t_tables(self):
-        """`svk_c3d2_conv32t` (conv3_2: 64 -> 64, k(3,7,1)), two-piece f16 products (see stage1_tables):
-        wblk [4 nt][2 kb][21 taps][2: H | L][64 lanes][8 halves], element e = W[co = 16 nt + (l & 15)][32 kb + 8 kk + e][kd][kh],
-        tap 7 kd + kh; bias, slope [64].  None when the layer differs."""
-        hit = getattr(self, "_conv32t", False)
-        if hit is not False:
-            return hit
-        self._conv32t = None
-        if len(self.stages) < 6:
-            return None
-        w, b, sl, st, pool, _ = self.stages[5]
-        if tuple(w.shape) != (64, 64, 3, 7, 1) or tuple(st) != (1, 1, 1) or pool:
-            return None
-        dev = w.device
-        lane = torch.arange(64, device=dev)
-        ch, kq = lane & 15, lane >> 4
-        a = w.contiguous()[:, :, :, :, 0]                                    # [co][ci][kd][kh]
-        e8 = torch.arange(8, device=dev)[None, :]
-        blk = torch.empty((4, 2, 21, 2, 64, 8), dtype=torch.float16, device=dev)
-        for nt in range(4):
-            for kb in range(2):
-                ci = 32 * kb + 8 * kq[:, None] + e8
-                for kd in range(3):
-                    for kh in range(7):
-                        wv = a[(16 * nt + ch)[:, None], ci, kd, kh]
-                        h = wv.to(torch.float16)
-                        blk[nt, kb, 7 * kd + kh, 0] = h
-                        blk[nt, kb, 7 * kd + kh, 1] = (wv - h.to(torch.float32)).to(torch.float16)
-        slope = sl.expand(64).contiguous() if sl.numel() == 1 else sl.contiguous()
-        self._conv32t = (blk.contiguous(), b.contiguous(), slope, bool(((sl >= 0) & (sl <= 1)).all()))
-        return self._conv32t
+        return self._tables["conv32t"]
 
     def conv41_tables(self):
-        """`svk_c3d2_conv41` (conv4_1: 64 -> 128, k(3,1,3), stride 1, no pool), two-piece f16 products (see stage1_tables):
-        wblk [8 nt][9 taps][2 kb][2: H | L][64 lanes][8 halves], element e = W[co = 16 nt + (l & 15)][32 kb + 8 kk + e][kd][kw],
-        tap 3 kd + kw; bias, slope [128].  None when the layer differs."""
-        hit = getattr(self, "_conv41", False)
-        if hit is not False:
-            return hit
-        self._conv41 = None
-        if len(self.stages) < 7:
-            return None
-        w, b, sl, st, pool, _ = self.stages[6]
-        if tuple(w.shape) != (128, 64, 3, 1, 3) or tuple(st) != (1, 1, 1) or pool:
-            return None
-        dev = w.device
-        lane = torch.arange(64, device=dev)
-        ch, kq = lane & 15, lane >> 4
-        a = w.contiguous()[:, :, :, 0, :]                                    # [co][ci][kd][kw]
-        e8 = torch.arange(8, device=dev)[None, :]
-        blk = torch.empty((8, 9, 2, 2, 64, 8), dtype=torch.float16, device=dev)
-        for nt in range(8):
-            for kb in range(2):
-                ci = 32 * kb + 8 * kq[:, None] + e8
-                for kd in range(3):
-                    for kw in range(3):
-                        wv = a[(16 * nt + ch)[:, None], ci, kd, kw]
-                        h = wv.to(torch.float16)
-                        blk[nt, 3 * kd + kw, kb, 0] = h
-                        blk[nt, 3 * kd + kw, kb, 1] = (wv - h.to(torch.float32)).to(torch.float16)
-        slope = sl.expand(128).contiguous() if sl.numel() == 1 else sl.contiguous()
-        self._conv41 = (blk.contiguous(), b.contiguous(), slope, bool(((sl >= 0) & (sl <= 1)).all()))
-        return self._conv41
+        return self._tables["conv41"]
 
     def conv42_tables(self):
-        """`svk_c3d2_conv42` (conv4_2: 128 -> 128, k(3,7,1), stride 1, no pool)."""
-        hit = getattr(self, "_conv42", False)
-        if hit is False:
-            hit = self._conv42 = self._tail_conv_tables(7, (128, 128, 3, 7, 1), "h")
-        return hit
+        return self._tables["conv42"]
 
     def fc5_tables(self):
-        """`svk_c3d2_fc5`: wfrag [4 d][8 nt][72 steps][64 lanes][4]: lane (j = 16 nt + (l & 15), kk = l >> 4), e:
-        W5[j][c * 36 + d * 9 + pixel] for the K index 1 152 d + 16 step + 4 kk + e = ((d * 16 + chunk) * 9 + pixel) * 8 + c % 8
-        (conv4_2's chunked output order; model.py:168 flattens NCDHW), and the bias.  None when FC5 is not 4 608 -> 128."""
-        hit = getattr(self, "_fc5", False)
-        if hit is not False:
-            return hit
-        self._fc5 = None
-        if tuple(self.fc_w.shape) != (EMBED_DIM, _FLAT) or EMBED_DIM != 128:
-            return None
-        dev = self.fc_w.device
-        # columns of the chunked order: [d][chunk][pixel][c8] -> torch column (8 chunk + c8) * 36 + d * 9 + pixel
-        d, ch, px, c8 = torch.meshgrid(torch.arange(4, device=dev), torch.arange(16, device=dev),
-                                       torch.arange(9, device=dev), torch.arange(8, device=dev), indexing="ij")
-        col = ((8 * ch + c8) * 36 + d * 9 + px).reshape(-1)                  # [4608] in K order
-        wk = self.fc_w[:, col]                                               # [128 j][4608 K]
-        lane = torch.arange(64, device=dev)
-        n_, kq = lane & 15, lane >> 4
-        wv = wk.view(8, 16, 4, 72, 4, 4)                                     # [nt][n][d][step][kq][e]
-        frag = wv[:, n_, :, :, kq].permute(2, 1, 3, 0, 4).contiguous()       # lane axis first -> [d][nt][step][lane][e]
-        self._fc5 = (frag, self.fc_b.contiguous())
-        return self._fc5
+        return self._tables["fc5"]
+
+
+# Two-piece f16 products (include/svk.h): a weight w is H = f16(w), L = f16(w - H), laid out in the lane order of
+# v_mfma_f32_16x16x32_f16's A operand: lane l holds output channel co = 16 nt + (l & 15) and K index 8 kk + e (kk = l >> 4) in its
+# eight halves e.  Each builder gathers the f32 weights of every (block, lane, e) at once through an index grid, then splits them.
+def _grid(dev, *sizes):
+    """Index tensors over the axes of the given sizes, each of the full shape `sizes`."""
+    return torch.meshgrid(*(torch.arange(n, device=dev) for n in sizes), indexing="ij")
+
+
+def _halves(w):
+    """Gathered f32 weights [..., 64 lanes, 8] -> f16 [..., 2: H | L, 64, 8]."""
+    h = w.to(torch.float16)
+    return torch.stack((h, (w - h.to(torch.float32)).to(torch.float16)), dim=-3)
+
+
+def _prelu(sl, co):
+    """A PReLU's slope per output channel, and whether every slope lies in [0, 1] (the two-instruction form; one host read)."""
+    return (sl.expand(co).contiguous() if sl.numel() == 1 else sl.contiguous()), bool(((sl >= 0) & (sl <= 1)).all())
+
+
+def _stage1_tables(st1, st2):
+    """Operand blocks of `svk_c3d2_stage1` / `svk_c3d2_stage1_c3` (conv1_1 1 or 3 -> 16 k(3,1,5); conv1_2 16 -> 16 k(3,9,1) stride
+    (1,2,1); pool), two-piece f16 products:
+      w1blk [2][64][8]      : conv1_1, tap t = 8 (kk & 1) + e (t = 5 kd + kw; 15 -> 0): H for every kk | L for kk < 2, 0 above
+             [3][2][64][8]  : the three-channel conv1_1 (`svk_c3d2_stage1_c3`): that block for each input channel -- the 45
+                              taps padded to 48, tap 15 of every channel the zero pad
+      w2blk [14][2][64][8]  : conv1_2, tap pairs (a | b): ci = 8 (kk & 1) + e at tap a (kk < 2) / b (kk >= 2); H | L;
+                              pair 13 is tap (2, 8) alone against an [h | l] fragment: H at every kk | L for kk < 2, 0 above
+    -> (w1blk, bias1, slope1, w2blk, bias2, slope2, every slope in [0, 1])."""
+    (w1, b1, s1, *_), (w2, b2, s2, *_) = st1, st2
+    dev = w1.device
+    w1t = torch.cat([w1.reshape(16, -1, 15), torch.zeros((16, w1.shape[1], 1), device=dev)], 2)      # [co][ch][t], t = 15: zero
+    ch, l, e = _grid(dev, w1.shape[1], 64, 8)
+    w1blk = _halves(w1t[l & 15, ch, 8 * ((l >> 4) & 1) + e])                                          # [ch][2][64][8]
+    w1blk[..., 1, 32:, :] = 0           # lanes kk >= 2 meet the h half of the patch only: no L there
+    # conv1_2's tap pairs: taps (kd, kh) a for kk < 2 | b for kk >= 2; pair 13's b is its a (the lone tap: H at every kk)
+    pairs = torch.tensor([((p // 4, 2 * (p % 4)), (p // 4, 2 * (p % 4) + 1)) for p in range(12)]
+                         + [((0, 8), (1, 8)), ((2, 8), (2, 8))], device=dev)                          # [14][a | b][kd, kh]
+    p, l, e = _grid(dev, 14, 64, 8)
+    tap = pairs[p, (l >> 5)]
+    w2blk = _halves(w2[l & 15, 8 * ((l >> 4) & 1) + e, tap[..., 0], tap[..., 1], 0])                  # [14][2][64][8]
+    w2blk[13, 1, 32:, :] = 0            # the lone tap is read as [h | l]: L against the h half only
+    slope1, in01_1 = _prelu(s1, 16)
+    slope2, in01_2 = _prelu(s2, 16)
+    return (w1blk[0] if w1.shape[1] == 1 else w1blk, b1, slope1, w2blk, b2, slope2, in01_1 and in01_2)
+
+
+def _stage2_tables(st1, st2):
+    """Operand blocks of `svk_c3d2_stage2` (conv2_1 16 -> 32 k(3,1,4); conv2_2 32 -> 32 k(3,8,1) stride (1,2,1) + pool), two-piece
+    f16 products:
+      w21blk [2 nt][6 pairs][2][64][8]: conv2_1, pair = 2 kd + kw / 2: element e = W[co][ci = 8 (kk & 1) + e][kd][kw + (kk >= 2)]
+      w22blk [2 nt][24 taps][2][64][8]: conv2_2, tap = 8 kd + kh: element e = W[co][ci = 8 kk + e][kd][kh] (K = 32 = one tap)
+    -> (w21blk, bias21, slope21, w22blk, bias22, slope22, every slope in [0, 1])."""
+    (w1, b1, s1, *_), (w2, b2, s2, *_) = st1, st2
+    nt, pr, l, e = _grid(w1.device, 2, 6, 64, 8)
+    kk = l >> 4
+    w21blk = _halves(w1[16 * nt + (l & 15), 8 * (kk & 1) + e, pr // 2, 0, 2 * (pr % 2) + (kk >= 2).long()])
+    nt, tap, l, e = _grid(w2.device, 2, 24, 64, 8)
+    w22blk = _halves(w2[16 * nt + (l & 15), 8 * (l >> 4) + e, tap // 8, tap % 8, 0])
+    slope1, in01_1 = _prelu(s1, 32)
+    slope2, in01_2 = _prelu(s2, 32)
+    return (w21blk, b1, slope1, w22blk, b2, slope2, in01_1 and in01_2)
+
+
+def _conv31_tables(st):
+    """`svk_c3d2_conv31` (conv3_1: 32 -> 64, k(3,1,3)), two-piece f16 products: wblk [4 nt][9 taps][2: H | L][64][8], element
+    e = W[co][8 kk + e][kd][kw], tap 3 kd + kw -> (wblk, bias, slope [64], every slope in [0, 1])."""
+    w, b, sl, *_ = st
+    nt, tap, l, e = _grid(w.device, 4, 9, 64, 8)
+    return (_halves(w[16 * nt + (l & 15), 8 * (l >> 4) + e, tap // 3, 0, tap % 3]), b) + _prelu(sl, 64)
+
+
+def _conv32t_tables(st):
+    """`svk_c3d2_conv32t` (conv3_2: 64 -> 64, k(3,7,1)), two-piece f16 products: wblk [4 nt][2 kb][21 taps][2: H | L][64][8],
+    element e = W[co][32 kb + 8 kk + e][kd][kh], tap 7 kd + kh -> (wblk, bias, slope [64], every slope in [0, 1])."""
+    w, b, sl, *_ = st
+    nt, kb, tap, l, e = _grid(w.device, 4, 2, 21, 64, 8)
+    return (_halves(w[16 * nt + (l & 15), 32 * kb + 8 * (l >> 4) + e, tap // 7, tap % 7, 0]), b) + _prelu(sl, 64)
+
+
+def _conv41_tables(st):
+    """`svk_c3d2_conv41` (conv4_1: 64 -> 128, k(3,1,3)), two-piece f16 products: wblk [8 nt][9 taps][2 kb][2: H | L][64][8],
+    element e = W[co][32 kb + 8 kk + e][kd][kw], tap 3 kd + kw -> (wblk, bias, slope [128], every slope in [0, 1])."""
+    w, b, sl, *_ = st
+    nt, tap, kb, l, e = _grid(w.device, 8, 9, 2, 64, 8)
+    return (_halves(w[16 * nt + (l & 15), 32 * kb + 8 * (l >> 4) + e, tap // 3, 0, tap % 3]), b) + _prelu(sl, 128)
+
+
+def _conv42_tables(st):
+    """`svk_c3d2_conv42` (conv4_2: 128 -> 128, k(3,7,1)), f32 through Winograd F(2, 3) along depth: the BN-folded weight g is
+    transformed to G0 = g0, G1 = ((g0 + g2) + g1) / 2, G2 = ((g0 + g2) - g1) / 2, G3 = g2 (the expressions the kernel's prologue
+    evaluates) and laid out as wfrag [8 nt][16 chunks of 8 input channels][7 taps][4 k][64 lanes][2]: lane (co = 16 nt + (l & 15),
+    kk = l >> 4), element e = G_k[co][8 chunk + 2 kk + e][tap] -> (wfrag, bias, slope [128], every slope in [0, 1])."""
+    w, b, sl, *_ = st
+    g0, g1, g2 = w[:, :, 0, :, 0], w[:, :, 1, :, 0], w[:, :, 2, :, 0]                               # [co][ci][kh]
+    g = torch.stack((g0, 0.5 * ((g0 + g2) + g1), 0.5 * ((g0 + g2) - g1), g2))                         # [4 k][co][ci][taps]
+    lane = torch.arange(64, device=w.device)
+    gg = g.view(4, 8, 16, 16, 4, 2, 7)                                                                # [k][nt][n][chunk][kq][e][tap]
+    frag = gg[:, :, lane & 15, :, lane >> 4].permute(2, 3, 5, 1, 0, 4).contiguous()                   # lane axis first -> [nt][chunk][tap][k][lane][e]
+    return (frag, b) + _prelu(sl, 128)
+
+
+def _fc5_tables(fc_w, fc_b):
+    """`svk_c3d2_fc5`: wfrag [4 d][8 nt][72 steps][64 lanes][4]: lane (j = 16 nt + (l & 15), kk = l >> 4), e:
+    W5[j][c * 36 + d * 9 + pixel] for the K index 1 152 d + 16 step + 4 kk + e = ((d * 16 + chunk) * 9 + pixel) * 8 + c % 8
+    (conv4_2's chunked output order; model.py:168 flattens NCDHW) -> (wfrag, bias)."""
+    dev = fc_w.device
+    # columns of the chunked order: [d][chunk][pixel][c8] -> torch column (8 chunk + c8) * 36 + d * 9 + pixel
+    d, ch, px, c8 = _grid(dev, 4, 16, 9, 8)
+    col = ((8 * ch + c8) * 36 + d * 9 + px).reshape(-1)                  # [4608] in K order
+    lane = torch.arange(64, device=dev)
+    wv = fc_w[:, col].view(8, 16, 4, 72, 4, 4)                           # [nt][n][d][step][kq][e]
+    frag = wv[:, lane & 15, :, :, lane >> 4].permute(2, 1, 3, 0, 4).contiguous()   # lane axis first -> [d][nt][step][lane][e]
+    return frag, fc_b.contiguous()
+
 
 def seeded_model(seed, n_labels=1211, num_channels=1):
     """Random-init C3D2 under a fixed torch seed (the reference's checkpoint

@@ -1720,8 +1720,8 @@ def test_network_is_indifferent_to_a_checkpoints_channel_scales(eng):
 
 
 def test_c3d2_second_block_kernels(eng):
-    """svk_c3d2_stage2 (conv2_1 -> BN -> PReLU -> conv2_2 -> BN -> PReLU -> pool2, model.py:119-124,151-158, both through the
-    depth transform) against the same layers on torch-CPU with unfolded BatchNorm, on a random activation in stage 1's
+    """svk_c3d2_stage2 (conv2_1 -> BN -> PReLU -> conv2_2 -> BN -> PReLU -> pool2, model.py:119-124,151-158, both direct-form
+    kernels on two-piece f16 products) against the same layers on torch-CPU with unfolded BatchNorm, on a random activation in stage 1's
     output layout."""
     model, emb, state = _net(eng, 51, 52)
     tables = emb.stage2_tables()
@@ -1749,8 +1749,8 @@ def _conv31_unchunk(y):
 
 
 def test_c3d2_conv31_kernel(eng):
-    """svk_c3d2_conv31 (conv3_1 -> BN -> PReLU, model.py:126-128,159-161, Winograd F(2,3) along depth) against the same
-    layer on torch-CPU with unfolded BatchNorm; per-channel and negative slopes."""
+    """svk_c3d2_conv31 (conv3_1 -> BN -> PReLU, model.py:126-128,159-161, a direct-form kernel on two-piece f16
+    products) against the same layer on torch-CPU with unfolded BatchNorm; per-channel and negative slopes."""
     model, emb, state = _net(eng, 61, 62)
     tables = emb.conv31_tables()
     assert tables is not None and tables[3]
@@ -1787,7 +1787,8 @@ def _from_chunked(y, H, W):
 
 def test_c3d2_tail_kernels(eng):
     """svk_c3d2_conv41, svk_c3d2_conv42, svk_c3d2_fc5 (model.py:132-139,165-170: conv4_1 -> BN -> PReLU -> conv4_2 -> BN ->
-    PReLU -> flatten -> FC5 as GEMMs over the batch, Winograd F(2,3) along depth, host-transformed weights) each against
+    PReLU -> flatten -> FC5 as GEMMs over the batch; conv4_1 direct-form on two-piece f16 products, conv4_2 Winograd F(2,3) along
+    depth with host-transformed weights) each against
     the same layer on torch-CPU with unfolded BatchNorm: batches of 1, 3 (one partial group of 16 cubes), 37 (2 full + 1
     partial), 70 (several items per workgroup for FC5's 64-cube groups) and 520 cubes; the 2 100-cube case of conv4_2
     (several items per workgroup); negative / per-channel slopes."""

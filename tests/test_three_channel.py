@@ -178,7 +178,7 @@ def test_three_channel_first_block_against_f32(eng, g3):
     # (a) the golden cubes, as feature rows with crop starts 0, 80, ...
     cubes = _golden_cubes(g3)
     rows = eng.to_device(cubes).view(3, 3, 1600, 40)
-    got = eng.c3d2_stage1_c3(rows, emb.crop_starts(3, eng.device), tables).cpu().numpy()
+    got = eng.c3d2_stage1(rows, emb.crop_starts(3, eng.device), tables).cpu().numpy()
     want = _cpu_block1(state, torch.from_numpy(cubes))
     scale = np.abs(want).max()
     print("three-channel first block (N(-6, 2) cubes): max |diff| / scale %.2e" % (np.abs(got.transpose(0, 4, 1, 2, 3) - want).max() / scale))
@@ -194,7 +194,7 @@ def test_three_channel_first_block_against_f32(eng, g3):
     crops[4, 19] = frames[4] - 40                           # half inside the clip: the rest are the zero padding rows
     cubes = _cubes_from_rows(feat3, crops)
     want = _cpu_block1(state, torch.from_numpy(cubes))
-    got = eng.c3d2_stage1_c3(feat3, crops, tables).cpu().numpy()
+    got = eng.c3d2_stage1(feat3, crops, tables).cpu().numpy()
     scale = np.abs(want).max()
     print("three-channel first block (CMVN'd features): max |diff| / scale %.2e" % (np.abs(got.transpose(0, 4, 1, 2, 3) - want).max() / scale))
     np.testing.assert_allclose(got.transpose(0, 4, 1, 2, 3), want, rtol=1e-4, atol=4e-6 * scale)
@@ -228,7 +228,7 @@ def test_three_channel_layouts_and_bad_arguments(eng, g3):
     assert lib.svk_c3d2_stage1_c3(ctx, None, 0, 100, 40, None, 20, 80, None, None, None, None, None, None, 0, None) == 0
     assert lib.svk_c3d2_stage1_c3_lds_bytes() == lib.svk_c3d2_stage1_lds_bytes() <= eng.lds_per_cu
     with pytest.raises(ValueError):
-        eng.c3d2_stage1_c3(torch.zeros((2, 3, 100, 40), device=eng.device), np.zeros((1, 20), np.int32), emb.stage1_tables())
+        eng.c3d2_stage1(torch.zeros((2, 3, 100, 40), device=eng.device), np.zeros((1, 20), np.int32), emb.stage1_tables())
     torch.cuda.synchronize()
 
 

@@ -49,7 +49,7 @@ def main():
     e1, e3 = models[1].fused_inference(), models[3].fused_inference()
     r = {"n_cubes": n}
     r["stage1_1ch_ms"] = timed(lambda: eng.c3d2_stage1(feat1, crops, e1.stage1_tables()), a.reps)
-    r["stage1_3ch_ms"] = timed(lambda: eng.c3d2_stage1_c3(feat3, crops, e3.stage1_tables()), a.reps)
+    r["stage1_3ch_ms"] = timed(lambda: eng.c3d2_stage1(feat3, crops, e3.stage1_tables()), a.reps)
     r["stage1_ratio"] = r["stage1_3ch_ms"] / r["stage1_1ch_ms"]
     r["embed_3ch_kernels_ms"] = timed(lambda: e3.embed_features(feat3, crops), a.reps)
     r["embed_1ch_kernels_ms"] = timed(lambda: e1.embed_features(feat1, crops), a.reps)
