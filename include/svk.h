@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SVK_VERSION 112 /* 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
+#define SVK_VERSION 113 /* 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
 
 typedef enum svk_status {
   SVK_OK = 0,
@@ -236,13 +236,35 @@ int svk_l2_dist(svk_ctx* ctx, const float* d_a, const float* d_b, int32_t n, int
 
 /* ---- ROC / EER / AUC on the device ------------------------------------------------------------
  * evaluation.py:47-52 (sklearn roc_curve + roc_auc_score + brentq on interp1d) for pair sets too
- * large for the host: stable sort of the scores (descending), scan of the labels, one point per
- * distinct score, trapezoid AUC and the linear root of 1 - fpr - tpr.  d_labels: uint8, 1 = positive.
- * d_workspace: svk_roc_workspace_bytes(n) bytes.  h_out[4] (HOST) = {eer, auc, positives, ROC points};
- * the call synchronises the stream (its result is a host scalar). */
+ * large for the host: LSD radix sort of the scores (descending, 8-bit digits, the label riding along;
+ * -0.0 sorts as +0.0), scan of the labels, one point per distinct score, trapezoid AUC and the linear
+ * root of 1 - fpr - tpr.  Every step is a reduce-then-scan over per-workgroup spans: no workgroup waits
+ * on another.  d_labels: uint8, non-zero = positive.  n < 2^32.
+ * d_workspace: svk_roc_workspace_bytes(n) bytes (about 18 B per pair).  h_out[4] (HOST) = {eer, auc,
+ * positives, ROC points (distinct scores)}; the call synchronises the stream (its result is a host scalar). */
 size_t svk_roc_workspace_bytes(int64_t n);
 int svk_roc_eer(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, int64_t n, void* d_workspace,
                 size_t workspace_bytes, double* h_out);
+
+/* evaluation.py:11-33 (get_and_plot_k_eer_auc) in one call: with step = n / k, split s is the pairs
+ * [s * step, (s + 1) * step); the last n - k * step pairs are ignored, as there.  Per split, as svk_roc_eer,
+ * plus roc_curve(drop_intermediate=True) in counts: the distinct-score points, then (more than two of
+ * them) only the first, the last and those where a second difference of fps or tps is non-zero, then the
+ * prepended origin.  d_curve: NULL, or uint32 [2][k][step + 1] -- the fps plane, then the tps plane; fpr =
+ * fps / fps[-1], tpr = tps / tps[-1] in float64 is sklearn's own arithmetic.  h_out (HOST) [k][4] = {eer, auc,
+ * positives, curve points}.  SVK_ERR_BAD_ARG (the message names the split) for a split with one class or a
+ * non-finite score, and for k < 1 or step < 2.  d_workspace: svk_roc_k_workspace_bytes(n, k) bytes (0 for
+ * arguments svk_roc_k rejects); the splits run one after another through it.  Synchronises the stream. */
+size_t svk_roc_k_workspace_bytes(int64_t n, int32_t k);
+int svk_roc_k(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, int64_t n, int32_t k, void* d_workspace,
+              size_t workspace_bytes, uint32_t* d_curve, double* h_out);
+
+/* evaluation.py:112-134 (top-1 of each test utterance) in one streaming pass over d_scores [n_rows][n_cols]:
+ * d_argmax[r] = np.argmax(row r) (the first maximum; a NaN is the maximum, the first NaN wins); d_true[r] = the
+ * enrolled column of row r's speaker, -1 = not enrolled; d_labels: NULL, or uint8 [n_rows][n_cols], the one-hot
+ * rows of d_true (all zeros for -1).  *h_correct (HOST) = rows with argmax == d_true.  Synchronises the stream. */
+int svk_top1(svk_ctx* ctx, const float* d_scores, int64_t n_rows, int32_t n_cols, const int32_t* d_true,
+             int32_t* d_argmax, uint8_t* d_labels, int64_t* h_correct);
 
 /* ---- the first block of the embedding network ----------------------------------------------------
  * model.py:110-117 + :141-150 (C3D2): cube (utils.py:351-379) -> conv1_1 (1 -> 16, kernel (3,1,5)) -> BN -> PReLU

@@ -1,45 +1,386 @@
-// ROC / EER / AUC on the device: what /root/reference/evaluation.py:47-52 gets from
+// ROC / EER / AUC on the device: what /root/reference/evaluation.py:11-52 gets from
 // sklearn.roc_curve + roc_auc_score + brentq(interp1d) -- one sort of all (label, score) pairs --
-// for score sets too large to bring back to the host (148 642 x 1 211 = 1.8e8 pairs).
+// for score sets too large to bring back to the host (148 642 x 1 211 = 1.8e8 pairs), and the top-1
+// pass of evaluation.py:112-134 (argmax per row, hits, one-hot labels).
 //
-//   1. stable radix sort of the scores, descending, labels riding along   (rocPRIM via hipCUB)
-//   2. inclusive scan of the labels            -> tps[i] = positives among the i+1 best scores
-//   3. distinct-score boundaries               -> the ROC's threshold points (roc_curve keeps one
-//      point per distinct score; its drop_intermediate only removes collinear points)
-//   4. one pass over the points: trapezoid area (AUC) and the segment where 1 - fpr - tpr
-//      changes sign, solved linearly (the root brentq finds on the linear interpolant).
-// Sort and scan are library primitives; steps 3-4 are the kernels below.  Bit-level equality with
-// sklearn is not expected (float64 accumulation order), |d| ~ 1e-15.
-#include <hipcub/hipcub.hpp>
-
+// Every kernel is this file's own; nothing waits on another workgroup.  Per split of m pairs:
+//   1. hist_kernel: the four 8-bit digit histograms of the keys, the non-finite scores and the positives,
+//      read back to the host (argument checks; a pass whose digit is the same for every key is skipped).
+//   2. LSD radix sort, descending, the 0/1 label riding along: per pass count_kernel (digit counts of
+//      each workgroup's contiguous span), offsets_kernel (each digit's row of the [256][grid] count matrix
+//      scanned by one workgroup, on top of the keys of lower digits) and scatter_kernel (the span again, tile by tile, stable: wave-level digit match
+//      + per-(item, wave) counts give each key its rank; the tile is ordered in LDS and written out
+//      in digit runs at running per-digit offsets).  Keys: f32 -> u32 order-preserving map, inverted;
+//      -0.0 is +0.0 first (one tie group, as sklearn and the float compare below see them).
+//   3. the ROC's threshold points (one per distinct score, roc_curve before drop_intermediate) by the
+//      same reduce-then-scan: span sums of (label, boundary flag), a scan, then a pass that writes
+//      (fps, tps) at every boundary.
+//   4. roc_points_kernel: trapezoid area (AUC) and the segment where 1 - fpr - tpr changes sign,
+//      solved linearly (the root brentq finds on the linear interpolant).
+//   5. svk_roc_k only: roc_curve's drop_intermediate (second differences of fps, tps) and its
+//      prepended origin, compacted by the same pattern into the caller's curve planes.
+// Bit-level equality of eer / auc with sklearn is not expected (float64 accumulation order), |d| ~ 1e-15;
+// the curve counts are exact.  Element indices are u32 (n < 2^32), every address is 64-bit.
 #include "svk_internal.h"
 
 namespace {
 
-struct ToU32 {
-  __host__ __device__ __forceinline__ unsigned operator()(const uint8_t& v) const { return v ? 1u : 0u; }
-};
+constexpr int RT = 256;                  // threads per workgroup (all but scan_kernel and offsets_kernel)
+constexpr int WAVES = RT / 64;
+constexpr int ITEMS = 8;                 // keys per thread per scatter tile
+constexpr int TILE = RT * ITEMS;         // 2048 keys
+constexpr int GROUPS = ITEMS * WAVES;    // (item, wave) groups of a tile, in stable order
+constexpr int SPAN_ITEMS = 4;            // elements per thread per step of the point / curve passes
+constexpr unsigned GMAX = 1024;          // workgroups of a span-parallel kernel (count matrix [256][GMAX])
+constexpr int SCAN_T = 1024;
 
-__global__ __launch_bounds__(256) void boundary_kernel(const float* __restrict__ keys, int64_t n,
-                                                       uint8_t* __restrict__ flags) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    flags[i] = (i == n - 1 || keys[i] != keys[i + 1]) ? 1 : 0;
+__device__ __forceinline__ unsigned desc_key(unsigned u) {
+  if (u == 0x80000000u) u = 0u;                      // -0.0 -> +0.0
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);    // ascending order-preserving map
+  return ~u;                                         // descending
+}
+__device__ __forceinline__ float key_value(unsigned k) {
+  const unsigned a = ~k;
+  return __uint_as_float((a & 0x80000000u) ? (a & 0x7fffffffu) : ~a);
 }
 
-// out[0] = eer, out[1] = auc (accumulated), out[2] = positives, out[3] = number of ROC points
-__global__ __launch_bounds__(256) void roc_points_kernel(const unsigned* __restrict__ idx, const unsigned* __restrict__ m_ptr,
-                                                         const unsigned* __restrict__ tps, int64_t n,
-                                                         double* __restrict__ out) {
-  __shared__ double red[4];
-  const unsigned m = *m_ptr;
-  const double P = (double)tps[n - 1], N = (double)n - P;
+// Lanes of this wave holding the same 8-bit digit (only meaningful for valid lanes).
+__device__ __forceinline__ unsigned long long match_digit(unsigned d, bool valid) {
+  unsigned long long peers = __ballot(valid);
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    const bool bit = (d >> b) & 1u;
+    const unsigned long long m = __ballot(bit);
+    peers &= bit ? m : ~m;
+  }
+  return peers;
+}
+__device__ __forceinline__ unsigned long long lanes_below() { return (1ull << __lane_id()) - 1ull; }
+
+// Exclusive scan of one value per thread over an NT-wide workgroup; *total gets the sum.  lds: NT / 64 words.
+template <int NT = RT>
+__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned* lds, unsigned* total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  unsigned x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  if (lane == 63) lds[w] = x;
+  __syncthreads();
+  unsigned base = 0, tot = 0;
+#pragma unroll
+  for (int i = 0; i < NT / 64; ++i) {
+    const unsigned c = lds[i];
+    base += i < w ? c : 0u;
+    tot += c;
+  }
+  __syncthreads();
+  *total = tot;
+  return base + x - v;
+}
+
+// ---- 1. digit histograms + argument counts -------------------------------------------------------------------
+// hist[p * 256 + d] for the four digits p, hist[1024] = non-finite scores, hist[1025] = positives.
+__global__ __launch_bounds__(RT) void hist_kernel(const unsigned* __restrict__ bits, const uint8_t* __restrict__ lab, size_t n,
+                                                  unsigned* __restrict__ hist) {
+  __shared__ unsigned h[4 * 256];
+  for (int i = threadIdx.x; i < 4 * 256; i += RT) h[i] = 0;
+  __syncthreads();
+  unsigned bad = 0, pos = 0;
+  const size_t stride = (size_t)gridDim.x * RT;
+  for (size_t b = (size_t)blockIdx.x * RT; b < n; b += stride) {   // wave-uniform trip count
+    const size_t i = b + threadIdx.x;
+    const bool valid = i < n;
+    unsigned k = 0;
+    if (valid) {
+      const unsigned u = bits[i];
+      bad += (u & 0x7f800000u) == 0x7f800000u;
+      pos += lab[i] != 0;
+      k = desc_key(u);
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const unsigned d = (k >> (8 * p)) & 255u;
+      // a digit the whole wave shares (clustered scores) is one add, not 64 conflicting ones
+      const unsigned d0 = __shfl(d, 0, 64);
+      const unsigned long long same = __ballot(valid && d == d0), act = __ballot(valid);
+      if (same == act) {
+        if (__lane_id() == 0 && act) atomicAdd(&h[p * 256 + d0], (unsigned)__popcll(act));
+      } else if (valid) {
+        atomicAdd(&h[p * 256 + d], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 4 * 256; i += RT)
+    if (h[i]) atomicAdd(&hist[i], h[i]);
+  __shared__ unsigned red[2 * WAVES];
+  bad = (unsigned)wave_sum((long long)bad);
+  pos = (unsigned)wave_sum((long long)pos);
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = bad;
+    red[WAVES + (threadIdx.x >> 6)] = pos;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned b = 0, q = 0;
+    for (int i = 0; i < WAVES; ++i) {
+      b += red[i];
+      q += red[WAVES + i];
+    }
+    if (b) atomicAdd(&hist[1024], b);
+    atomicAdd(&hist[1025], q);
+  }
+}
+
+// ---- 2. one radix pass: count, scan, scatter -------------------------------------------------------------------
+// counts[d * G + g] = keys of workgroup g's span [g * span, (g + 1) * span) whose digit is d.  raw: the source is the
+// caller's f32 scores (the first pass that runs), else keys already mapped.
+__global__ __launch_bounds__(RT) void count_kernel(const unsigned* __restrict__ src, int raw, size_t n, size_t span, int shift,
+                                                   unsigned* __restrict__ counts) {
+  __shared__ unsigned h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const size_t lo = (size_t)blockIdx.x * span, hi = std::min(n, lo + span);
+  constexpr int U = 8;
+  for (size_t b = lo; b < hi; b += (size_t)RT * U) {
+    unsigned k[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const size_t i = b + (size_t)u * RT + threadIdx.x;
+      k[u] = i < hi ? src[i] : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool valid = b + (size_t)u * RT + threadIdx.x < hi;
+      const unsigned d = ((raw ? desc_key(k[u]) : k[u]) >> shift) & 255u;
+      const unsigned long long peers = match_digit(d, valid);
+      if (valid && !(peers & lanes_below())) atomicAdd(&h[d], (unsigned)__popcll(peers));
+    }
+  }
+  __syncthreads();
+  counts[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = h[threadIdx.x];
+}
+
+// In-place exclusive scan of data[0, len) (the [grid] partial sums of a span pass) by one workgroup; *total (if given) =
+// the sum.  Each thread owns a contiguous chunk.
+__global__ __launch_bounds__(SCAN_T) void scan_kernel(unsigned* __restrict__ data, unsigned len, unsigned* __restrict__ total) {
+  __shared__ unsigned part[SCAN_T];
+  const unsigned per = (len + SCAN_T - 1) / SCAN_T;
+  const unsigned lo = std::min(len, threadIdx.x * per), hi = std::min(len, lo + per);
+  unsigned s = 0;
+  for (unsigned i = lo; i < hi; ++i) s += data[i];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (unsigned o = 1; o < SCAN_T; o <<= 1) {   // Hillis-Steele, inclusive
+    const unsigned y = threadIdx.x >= o ? part[threadIdx.x - o] : 0u;
+    __syncthreads();
+    part[threadIdx.x] += y;
+    __syncthreads();
+  }
+  unsigned base = part[threadIdx.x] - s;
+  for (unsigned i = lo; i < hi; ++i) {
+    const unsigned v = data[i];
+    data[i] = base;
+    base += v;
+  }
+  if (total && threadIdx.x == SCAN_T - 1) *total = part[SCAN_T - 1];
+}
+
+// offs[d * G + g] = keys whose digit is below d (the pass's global histogram dh, from hist_kernel) + keys of digit d in
+// the spans before g: one workgroup per digit, one span per thread (G <= GMAX).
+__global__ __launch_bounds__(GMAX) void offsets_kernel(unsigned* __restrict__ counts, unsigned G, const unsigned* __restrict__ dh) {
+  __shared__ unsigned red[GMAX / 64];
+  const unsigned d = blockIdx.x, t = threadIdx.x;
+  unsigned below, tot;
+  block_excl_scan<GMAX>(t < d ? dh[t] : 0u, red, &below);
+  const unsigned v = t < G ? counts[(size_t)d * G + t] : 0u;
+  const unsigned ex = block_excl_scan<GMAX>(v, red, &tot);
+  if (t < G) counts[(size_t)d * G + t] = below + ex;
+}
+
+// Stable scatter of workgroup g's span to dst at offs[d * G + g] (the scanned counts), tile by tile.
+__global__ __launch_bounds__(RT) void scatter_kernel(const unsigned* __restrict__ src, const uint8_t* __restrict__ vsrc, int raw,
+                                                     size_t n, size_t span, int shift, const unsigned* __restrict__ offs,
+                                                     unsigned* __restrict__ dst, uint8_t* __restrict__ vdst) {
+  __shared__ unsigned short cnt[GROUPS][256];   // per (item, wave) group and digit: count, then exclusive offset
+  __shared__ unsigned sk[TILE];
+  __shared__ uint8_t sv[TILE];
+  __shared__ unsigned run[256], tstart[256], red[WAVES];
+  const int t = threadIdx.x, w = t >> 6;
+  run[t] = offs[(size_t)t * gridDim.x + blockIdx.x];
+  const size_t lo = (size_t)blockIdx.x * span, hi = std::min(n, lo + span);
+  for (size_t base = lo; base < hi; base += TILE) {
+    const unsigned tn = (unsigned)std::min((size_t)TILE, hi - base);
+#pragma unroll
+    for (int g = 0; g < GROUPS; ++g) cnt[g][t] = 0;
+    unsigned key[ITEMS], rank[ITEMS];
+    uint8_t val[ITEMS];
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+      const unsigned e = it * RT + t;
+      key[it] = 0;
+      val[it] = 0;
+      if (e < tn) {
+        key[it] = src[base + e];
+        val[it] = vsrc[base + e];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+      const bool valid = it * RT + t < (int)tn;
+      if (raw) {
+        key[it] = desc_key(key[it]);
+        val[it] = val[it] != 0;
+      }
+      const unsigned d = (key[it] >> shift) & 255u;
+      const unsigned long long peers = match_digit(d, valid);
+      rank[it] = (unsigned)__popcll(peers & lanes_below());
+      if (valid && rank[it] == 0) cnt[it * WAVES + w][d] = (unsigned short)__popcll(peers);
+    }
+    __syncthreads();
+    unsigned s = 0;   // thread t = digit t: offsets of the groups in stable order
+#pragma unroll
+    for (int g = 0; g < GROUPS; ++g) {
+      const unsigned c = cnt[g][t];
+      cnt[g][t] = (unsigned short)s;
+      s += c;
+    }
+    unsigned tot;
+    tstart[t] = block_excl_scan(s, red, &tot);
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+      if (it * RT + t < (int)tn) {
+        const unsigned d = (key[it] >> shift) & 255u;
+        const unsigned lp = tstart[d] + cnt[it * WAVES + w][d] + rank[it];
+        sk[lp] = key[it];
+        sv[lp] = val[it];
+      }
+    }
+    __syncthreads();
+    for (unsigned i = t; i < tn; i += RT) {
+      const unsigned k = sk[i], d = (k >> shift) & 255u;
+      const size_t gp = (size_t)run[d] + (i - tstart[d]);
+      dst[gp] = k;
+      vdst[gp] = sv[i];
+    }
+    __syncthreads();
+    run[t] += s;
+  }
+}
+
+// ---- 3 / 5. span reduce-then-scan over the sorted pairs and over the ROC points ---------------------------------
+// An Op yields two 0/1 values per element, (a, b); part_kernel sums them over each workgroup's span, emit_kernel
+// walks the span again and hands each element its global inclusive prefix sums.
+struct PointsOp {   // sorted pairs -> one point per distinct score: a = label, b = last of its tie group
+  const unsigned* keys;
+  const uint8_t* vals;
+  size_t n;
+  unsigned *pf, *pt;
+  __device__ void get(size_t i, unsigned& a, unsigned& b) const {
+    a = vals[i];
+    // equal keys are equal scores (-0.0 was mapped to +0.0); a NaN, unequal to itself, is a point of its own
+    const unsigned k = keys[i];
+    b = (i + 1 == n || k != keys[i + 1] || key_value(k) != key_value(k)) ? 1u : 0u;
+  }
+  __device__ void emit(size_t i, unsigned a_incl, unsigned b_incl) const {
+    pf[b_incl - 1] = (unsigned)(i + 1) - a_incl;
+    pt[b_incl - 1] = a_incl;
+  }
+};
+
+struct CurveOp {    // ROC points -> roc_curve(drop_intermediate=True) after the origin: b = point kept
+  const unsigned *pf, *pt;
+  size_t n;
+  unsigned *cf, *ct;
+  __device__ void get(size_t i, unsigned& a, unsigned& b) const {
+    a = 0;
+    b = 1;
+    if (n > 2 && i > 0 && i + 1 < n) {   // len(fps) > 2: keep where a second difference of fps or tps is non-zero
+      const unsigned f0 = pf[i - 1], f1 = pf[i], f2 = pf[i + 1], t0 = pt[i - 1], t1 = pt[i], t2 = pt[i + 1];
+      b = (f2 - f1 != f1 - f0 || t2 - t1 != t1 - t0) ? 1u : 0u;
+    }
+  }
+  __device__ void emit(size_t i, unsigned, unsigned b_incl) const {
+    cf[b_incl] = pf[i];   // [0] is the origin
+    ct[b_incl] = pt[i];
+  }
+};
+
+template <class Op>
+__global__ __launch_bounds__(RT) void part_kernel(Op op, size_t span, unsigned* __restrict__ pa, unsigned* __restrict__ pb) {
+  const size_t lo = (size_t)blockIdx.x * span, hi = std::min(op.n, lo + span);
+  unsigned sa = 0, sb = 0;
+  for (size_t i = lo + threadIdx.x; i < hi; i += RT) {
+    unsigned a, b;
+    op.get(i, a, b);
+    sa += a;
+    sb += b;
+  }
+  __shared__ unsigned red[2 * WAVES];
+  sa = (unsigned)wave_sum((long long)sa);
+  sb = (unsigned)wave_sum((long long)sb);
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = sa;
+    red[WAVES + (threadIdx.x >> 6)] = sb;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned a = 0, b = 0;
+    for (int i = 0; i < WAVES; ++i) {
+      a += red[i];
+      b += red[WAVES + i];
+    }
+    pa[blockIdx.x] = a;
+    pb[blockIdx.x] = b;
+  }
+}
+
+template <class Op>
+__global__ __launch_bounds__(RT) void emit_kernel(Op op, size_t span, const unsigned* __restrict__ pa,
+                                                  const unsigned* __restrict__ pb) {
+  __shared__ unsigned red[WAVES];
+  const size_t lo = (size_t)blockIdx.x * span, hi = std::min(op.n, lo + span);
+  unsigned ca = pa[blockIdx.x], cb = pb[blockIdx.x];
+  for (size_t base = lo; base < hi; base += (size_t)RT * SPAN_ITEMS) {
+    const size_t i0 = base + (size_t)threadIdx.x * SPAN_ITEMS;   // SPAN_ITEMS consecutive elements per thread
+    unsigned a[SPAN_ITEMS], b[SPAN_ITEMS], x = 0;
+#pragma unroll
+    for (int j = 0; j < SPAN_ITEMS; ++j) {
+      a[j] = b[j] = 0;
+      if (i0 + j < hi) op.get(i0 + j, a[j], b[j]);
+      x += (a[j] << 16) | b[j];   // both sums of a step are <= RT * SPAN_ITEMS < 2^16
+    }
+    unsigned tot;
+    unsigned pre = block_excl_scan(x, red, &tot);
+    unsigned ia = ca + (pre >> 16), ib = cb + (pre & 0xffffu);
+#pragma unroll
+    for (int j = 0; j < SPAN_ITEMS; ++j) {
+      ia += a[j];
+      ib += b[j];
+      if (b[j]) op.emit(i0 + j, ia, ib);
+    }
+    ca += tot >> 16;
+    cb += tot & 0xffffu;
+  }
+}
+
+// ---- 4. AUC and EER over the points ---------------------------------------------------------------------------
+// out[0] = eer, out[1] = auc (accumulated; zeroed before)
+__global__ __launch_bounds__(RT) void roc_points_kernel(const unsigned* __restrict__ pf, const unsigned* __restrict__ pt,
+                                                        size_t m, double P, double N, double* __restrict__ out) {
+  __shared__ double red[WAVES];
   double area = 0.0;
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < (int64_t)m; j += (int64_t)gridDim.x * blockDim.x) {
-    const double t1 = (double)tps[idx[j]], f1 = (double)idx[j] + 1.0 - t1;
+  for (size_t j = (size_t)blockIdx.x * RT + threadIdx.x; j < m; j += (size_t)gridDim.x * RT) {
+    const double t1 = (double)pt[j], f1 = (double)pf[j];
     double t0 = 0.0, f0 = 0.0;  // roc_curve prepends the point (0, 0)
     if (j > 0) {
-      t0 = (double)tps[idx[j - 1]];
-      f0 = (double)idx[j - 1] + 1.0 - t0;
+      t0 = (double)pt[j - 1];
+      f0 = (double)pf[j - 1];
     }
     const double x0 = f0 / N, x1 = f1 / N, y0 = t0 / P, y1 = t1 / P;
     area += (x1 - x0) * (y0 + y1) * 0.5;
@@ -50,46 +391,205 @@ __global__ __launch_bounds__(256) void roc_points_kernel(const unsigned* __restr
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = area;
   __syncthreads();
   if (threadIdx.x == 0) {
-    atomicAdd(&out[1], red[0] + red[1] + red[2] + red[3]);
-    if (blockIdx.x == 0) {
-      out[2] = P;
-      out[3] = (double)m;
-    }
+    double s = 0.0;
+    for (int i = 0; i < WAVES; ++i) s += red[i];
+    atomicAdd(&out[1], s);
   }
 }
 
+// ---- top-1 ----------------------------------------------------------------------------------------------------
+// (v, i) beats (bv, bi) as np.argmax orders them: a NaN first, then the larger value, then the smaller index.
+__device__ __forceinline__ void top1_take(float& bv, unsigned& bi, float v, unsigned i) {
+  const bool vn = v != v, bn = bv != bv;
+  const bool take = (vn || bn) ? (vn && (!bn || i < bi)) : (v > bv || (v == bv && i < bi));
+  if (take) {
+    bv = v;
+    bi = i;
+  }
+}
+
+// One wave per row: the row's maximum, the hit against the enrolled column, the one-hot row.
+__global__ __launch_bounds__(RT) void top1_kernel(const float* __restrict__ s, int64_t rows, int cols, const int32_t* __restrict__ tru,
+                                                  int32_t* __restrict__ amax, uint8_t* __restrict__ lab,
+                                                  unsigned long long* __restrict__ correct) {
+  const int lane = threadIdx.x & 63;
+  long long hits = 0;
+  for (int64_t r = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * WAVES) {
+    const float* row = s + (size_t)r * cols;
+    float bv = -INFINITY;
+    unsigned bi = 0xffffffffu;
+#pragma unroll 4
+    for (int c = lane; c < cols; c += 64) top1_take(bv, bi, row[c], (unsigned)c);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      const float ov = __shfl_xor(bv, m, 64);
+      const unsigned oi = __shfl_xor(bi, m, 64);
+      top1_take(bv, bi, ov, oi);
+    }
+    const int32_t want = tru[r];
+    if (lane == 0) {
+      amax[r] = (int32_t)bi;
+      hits += want >= 0 && (int32_t)bi == want;
+    }
+    if (lab) {
+      uint8_t* lr = lab + (size_t)r * cols;
+      for (int c = lane; c < cols; c += 64) lr[c] = c == want ? 1 : 0;
+    }
+  }
+  __shared__ long long red[WAVES];
+  hits = wave_sum(hits);
+  if (lane == 0) red[threadIdx.x >> 6] = hits;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    long long h = 0;
+    for (int i = 0; i < WAVES; ++i) h += red[i];
+    if (h) atomicAdd(correct, (unsigned long long)h);
+  }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------
 struct RocLayout {
-  size_t keys, vals, tps, flags, idx, misc, cub, total, cub_bytes;
+  size_t keys[2], vals[2], pf, pt, counts, parts, hist, misc, total;
 };
 
-RocLayout roc_layout(int64_t n) {
+// Workspace of one split of m pairs (splits run one after another through it).
+RocLayout roc_layout(size_t m) {
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   RocLayout l;
-  size_t sort_b = 0, scan_b = 0, sel_b = 0;
-  (void)hipcub::DeviceRadixSort::SortPairsDescending(nullptr, sort_b, (const float*)nullptr, (float*)nullptr,
-                                               (const uint8_t*)nullptr, (uint8_t*)nullptr, n);
-  hipcub::TransformInputIterator<unsigned, ToU32, const uint8_t*> it((const uint8_t*)nullptr, ToU32());
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan_b, it, (unsigned*)nullptr, n);
-  hipcub::CountingInputIterator<unsigned> cnt(0);
-  (void)hipcub::DeviceSelect::Flagged(nullptr, sel_b, cnt, (const uint8_t*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr, n);
-  l.cub_bytes = std::max(sort_b, std::max(scan_b, sel_b));
   size_t o = 0;
-  l.keys = o;  o += up((size_t)n * 4);
-  l.vals = o;  o += up((size_t)n);
-  l.tps = o;   o += up((size_t)n * 4);
-  l.flags = o; o += up((size_t)n);
-  l.idx = o;   o += up((size_t)n * 4);
-  l.misc = o;  o += 256;  // [0..3] doubles out, then the selected-count word
-  l.cub = o;   o += up(l.cub_bytes);
+  for (int b = 0; b < 2; ++b) {
+    l.keys[b] = o;
+    o += up(m * 4);
+  }
+  for (int b = 0; b < 2; ++b) {
+    l.vals[b] = o;
+    o += up(m);
+  }
+  l.pf = o;     o += up(m * 4);
+  l.pt = o;     o += up(m * 4);
+  l.counts = o; o += up((size_t)256 * GMAX * 4);
+  l.parts = o;  o += up((size_t)4 * GMAX * 4);   // four [GMAX] partial-sum rows: (a, b) of the points, of the curve
+  l.hist = o;   o += up(1026 * 4);
+  l.misc = o;   o += 256;                       // [0..1] doubles eer, auc; then u32 totals at +64
   l.total = o;
   return l;
+}
+
+// span (a multiple of `unit`) and grid so that at most GMAX workgroups cover n elements
+void spans(size_t n, size_t unit, size_t* span, unsigned* grid) {
+  const size_t units = std::max<size_t>(1, (n + unit - 1) / unit);
+  *span = (units + GMAX - 1) / GMAX * unit;
+  *grid = (unsigned)std::max<size_t>(1, (n + *span - 1) / *span);
+}
+
+template <class Op>
+int span_pass(svk_ctx* ctx, const Op& op, unsigned* pa, unsigned* pb, unsigned* tot_a, unsigned* tot_b, bool emit) {
+  size_t span;
+  unsigned grid;
+  spans(op.n, (size_t)RT * SPAN_ITEMS, &span, &grid);
+  hipStream_t st = ctx->stream;
+  hipLaunchKernelGGL(part_kernel<Op>, dim3(grid), dim3(RT), 0, st, op, span, pa, pb);
+  SVK_LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SCAN_T), 0, st, pa, grid, tot_a);
+  SVK_LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SCAN_T), 0, st, pb, grid, tot_b);
+  SVK_LAUNCH_CHECK(ctx);
+  if (emit) {
+    hipLaunchKernelGGL(emit_kernel<Op>, dim3(grid), dim3(RT), 0, st, op, span, pa, pb);
+    SVK_LAUNCH_CHECK(ctx);
+  }
+  return SVK_OK;
+}
+
+// One split of m pairs.  strict (svk_roc_k): non-finite scores and a single class are errors found before the
+// sort, named by `split`.  cf / ct: the split's curve planes, or NULL.  h4 = {eer, auc, positives, points}: points =
+// distinct scores (curve == false) or the length of roc_curve's output (curve == true).
+int roc_split(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, size_t m, char* w, const RocLayout& l,
+              bool strict, int split, bool curve, unsigned* cf, unsigned* ct, double* h4) {
+  hipStream_t st = ctx->stream;
+  unsigned* keys[2] = {reinterpret_cast<unsigned*>(w + l.keys[0]), reinterpret_cast<unsigned*>(w + l.keys[1])};
+  uint8_t* vals[2] = {reinterpret_cast<uint8_t*>(w + l.vals[0]), reinterpret_cast<uint8_t*>(w + l.vals[1])};
+  unsigned* pf = reinterpret_cast<unsigned*>(w + l.pf);
+  unsigned* pt = reinterpret_cast<unsigned*>(w + l.pt);
+  unsigned* counts = reinterpret_cast<unsigned*>(w + l.counts);
+  unsigned* parts = reinterpret_cast<unsigned*>(w + l.parts);
+  unsigned* hist = reinterpret_cast<unsigned*>(w + l.hist);
+  double* out = reinterpret_cast<double*>(w + l.misc);
+  unsigned* totals = reinterpret_cast<unsigned*>(w + l.misc + 64);   // [0] pos, [1] points, [2] -, [3] curve points
+  const unsigned* bits = reinterpret_cast<const unsigned*>(d_scores);
+
+  SVK_HIP(ctx, hipMemsetAsync(hist, 0, 1026 * 4, st));
+  SVK_HIP(ctx, hipMemsetAsync(out, 0, 64, st));
+  const unsigned hgrid = (unsigned)std::max<size_t>(1, std::min<size_t>((m + RT - 1) / RT, (size_t)ctx->num_cu * 4));
+  hipLaunchKernelGGL(hist_kernel, dim3(hgrid), dim3(RT), 0, st, bits, d_labels, m, hist);
+  SVK_LAUNCH_CHECK(ctx);
+  unsigned h[1026];
+  SVK_HIP(ctx, hipMemcpyAsync(h, hist, sizeof(h), hipMemcpyDeviceToHost, st));
+  SVK_HIP(ctx, hipStreamSynchronize(st));
+  const unsigned P = h[1025];
+  if (strict && h[1024])
+    return svk_fail(ctx, SVK_ERR_BAD_ARG, "split %d: %u non-finite scores (NaN or inf): roc_curve rejects them", split, h[1024]);
+  if (P == 0 || (size_t)P == m) {
+    if (strict)
+      return svk_fail(ctx, SVK_ERR_BAD_ARG, "split %d has only one class: %u positives of %zu pairs", split, P, m);
+    return svk_fail(ctx, SVK_ERR_BAD_ARG, "ROC needs both classes: %u positives of %lld", P, (long long)m);
+  }
+
+  // the sort: passes whose digit is the same for every key are skipped; at least one pass runs (it maps the keys)
+  size_t span;
+  unsigned grid;
+  spans(m, TILE, &span, &grid);
+  const unsigned* src = bits;
+  const uint8_t* vsrc = d_labels;
+  int raw = 1, cur = 0;
+  for (int p = 0; p < 4; ++p) {
+    bool constant = false;
+    for (int d = 0; d < 256; ++d) constant |= (size_t)h[p * 256 + d] == m;
+    if (constant && !(p == 3 && raw)) continue;
+    hipLaunchKernelGGL(count_kernel, dim3(grid), dim3(RT), 0, st, src, raw, m, span, 8 * p, counts);
+    SVK_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(offsets_kernel, dim3(256), dim3(GMAX), 0, st, counts, grid, hist + 256 * p);
+    SVK_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(scatter_kernel, dim3(grid), dim3(RT), 0, st, src, vsrc, raw, m, span, 8 * p, counts, keys[cur],
+                       vals[cur]);
+    SVK_LAUNCH_CHECK(ctx);
+    src = keys[cur];
+    vsrc = vals[cur];
+    raw = 0;
+    cur ^= 1;
+  }
+
+  // the distinct-score points, then AUC / EER
+  const PointsOp pop{src, vsrc, m, pf, pt};
+  if (int rc = span_pass(ctx, pop, parts, parts + GMAX, totals, totals + 1, true)) return rc;
+  unsigned M = 0;
+  SVK_HIP(ctx, hipMemcpyAsync(&M, totals + 1, 4, hipMemcpyDeviceToHost, st));
+  SVK_HIP(ctx, hipStreamSynchronize(st));
+  const unsigned pgrid = (unsigned)std::max<size_t>(1, std::min<size_t>((M + RT - 1) / RT, (size_t)ctx->num_cu * 8));
+  hipLaunchKernelGGL(roc_points_kernel, dim3(pgrid), dim3(RT), 0, st, pf, pt, (size_t)M, (double)P, (double)m - (double)P, out);
+  SVK_LAUNCH_CHECK(ctx);
+  unsigned C = M;
+  if (curve) {
+    const CurveOp cop{pf, pt, M, cf, ct};
+    if (int rc = span_pass(ctx, cop, parts + 2 * GMAX, parts + 3 * GMAX, totals + 2, totals + 3, cf != nullptr)) return rc;
+    if (cf) {
+      SVK_HIP(ctx, hipMemsetAsync(cf, 0, 4, st));   // the prepended origin
+      SVK_HIP(ctx, hipMemsetAsync(ct, 0, 4, st));
+    }
+    SVK_HIP(ctx, hipMemcpyAsync(&C, totals + 3, 4, hipMemcpyDeviceToHost, st));
+  }
+  SVK_HIP(ctx, hipMemcpyAsync(h4, out, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  SVK_HIP(ctx, hipStreamSynchronize(st));
+  h4[2] = (double)P;
+  h4[3] = curve ? (double)C + 1.0 : (double)M;
+  return SVK_OK;
 }
 
 }  // namespace
 
 extern "C" {
 
-size_t svk_roc_workspace_bytes(int64_t n) { return n > 0 ? roc_layout(n).total : 0; }
+size_t svk_roc_workspace_bytes(int64_t n) { return n > 0 ? roc_layout((size_t)n).total : 0; }
 
 int svk_roc_eer(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, int64_t n, void* d_workspace,
                 size_t workspace_bytes, double* h_out) {
@@ -97,37 +597,56 @@ int svk_roc_eer(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, in
   SVK_REQUIRE(ctx, n >= 2, "need at least two (label, score) pairs");
   SVK_REQUIRE(ctx, n < ((int64_t)1 << 32), "at most 2^32 - 1 pairs");
   SVK_REQUIRE(ctx, d_scores && d_labels && d_workspace, "NULL buffer");
-  const RocLayout l = roc_layout(n);
+  const RocLayout l = roc_layout((size_t)n);
   SVK_REQUIRE(ctx, workspace_bytes >= l.total, "workspace smaller than svk_roc_workspace_bytes(n)");
-  char* w = reinterpret_cast<char*>(d_workspace);
-  float* keys = reinterpret_cast<float*>(w + l.keys);
-  uint8_t* vals = reinterpret_cast<uint8_t*>(w + l.vals);
-  unsigned* tps = reinterpret_cast<unsigned*>(w + l.tps);
-  uint8_t* flags = reinterpret_cast<uint8_t*>(w + l.flags);
-  unsigned* idx = reinterpret_cast<unsigned*>(w + l.idx);
-  double* out = reinterpret_cast<double*>(w + l.misc);
-  unsigned* m_ptr = reinterpret_cast<unsigned*>(w + l.misc + 64);
-  void* cub = w + l.cub;
-  size_t cub_bytes = l.cub_bytes;
-  hipStream_t st = ctx->stream;
+  return roc_split(ctx, d_scores, d_labels, (size_t)n, reinterpret_cast<char*>(d_workspace), l, false, 0, false, nullptr,
+                   nullptr, h_out);
+}
 
-  SVK_HIP(ctx, hipMemsetAsync(out, 0, 128, st));
-  SVK_HIP(ctx, hipcub::DeviceRadixSort::SortPairsDescending(cub, cub_bytes, d_scores, keys, d_labels, vals, n, 0, 32, st));
-  hipcub::TransformInputIterator<unsigned, ToU32, const uint8_t*> it(vals, ToU32());
-  cub_bytes = l.cub_bytes;
-  SVK_HIP(ctx, hipcub::DeviceScan::InclusiveSum(cub, cub_bytes, it, tps, n, st));
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)ctx->num_cu * 8));
-  hipLaunchKernelGGL(boundary_kernel, dim3(grid), dim3(256), 0, st, keys, n, flags);
+size_t svk_roc_k_workspace_bytes(int64_t n, int32_t k) {
+  if (n < 2 || k < 1 || n / k < 2) return 0;
+  return roc_layout((size_t)(n / k)).total;
+}
+
+int svk_roc_k(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, int64_t n, int32_t k, void* d_workspace,
+              size_t workspace_bytes, uint32_t* d_curve, double* h_out) {
+  if (!ctx || !h_out) return SVK_ERR_BAD_ARG;
+  SVK_REQUIRE(ctx, k >= 1, "k < 1");
+  SVK_REQUIRE(ctx, n >= 0 && n < ((int64_t)1 << 32), "n outside [0, 2^32)");
+  const int64_t step = n / k;   // = int(n / float(k)) of evaluation.py:13 for n < 2^32
+  if (step < 2)
+    return svk_fail(ctx, SVK_ERR_BAD_ARG, "bad argument: %lld pairs in %d splits leave %lld per split (need >= 2)", (long long)n,
+                    k, (long long)step);
+  SVK_REQUIRE(ctx, d_scores && d_labels && d_workspace, "NULL buffer");
+  const RocLayout l = roc_layout((size_t)step);
+  SVK_REQUIRE(ctx, workspace_bytes >= l.total, "workspace smaller than svk_roc_k_workspace_bytes(n, k)");
+  const size_t plane = (size_t)k * (size_t)(step + 1);
+  for (int s = 0; s < k; ++s) {
+    const size_t lo = (size_t)s * (size_t)step;
+    uint32_t* cf = d_curve ? d_curve + (size_t)s * (size_t)(step + 1) : nullptr;
+    uint32_t* ct = d_curve ? cf + plane : nullptr;
+    if (int rc = roc_split(ctx, d_scores + lo, d_labels + lo, (size_t)step, reinterpret_cast<char*>(d_workspace), l, true, s,
+                           true, cf, ct, h_out + 4 * (size_t)s))
+      return rc;
+  }
+  return SVK_OK;
+}
+
+int svk_top1(svk_ctx* ctx, const float* d_scores, int64_t n_rows, int32_t n_cols, const int32_t* d_true, int32_t* d_argmax,
+             uint8_t* d_labels, int64_t* h_correct) {
+  if (!ctx || !h_correct) return SVK_ERR_BAD_ARG;
+  SVK_REQUIRE(ctx, n_rows >= 1 && n_cols >= 1, "empty score matrix");
+  SVK_REQUIRE(ctx, d_scores && d_true && d_argmax, "NULL buffer");
+  hipStream_t st = ctx->stream;
+  auto* hits = reinterpret_cast<unsigned long long*>(static_cast<char*>(ctx->scratch) + SVK_SLOT_TOP1);
+  SVK_HIP(ctx, hipMemsetAsync(hits, 0, 8, st));
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_rows + WAVES - 1) / WAVES, (int64_t)ctx->num_cu * 8));
+  hipLaunchKernelGGL(top1_kernel, dim3(grid), dim3(RT), 0, st, d_scores, n_rows, (int)n_cols, d_true, d_argmax, d_labels, hits);
   SVK_LAUNCH_CHECK(ctx);
-  hipcub::CountingInputIterator<unsigned> cnt(0);
-  cub_bytes = l.cub_bytes;
-  SVK_HIP(ctx, hipcub::DeviceSelect::Flagged(cub, cub_bytes, cnt, flags, idx, m_ptr, n, st));
-  hipLaunchKernelGGL(roc_points_kernel, dim3(grid), dim3(256), 0, st, idx, m_ptr, tps, n, out);
-  SVK_LAUNCH_CHECK(ctx);
-  SVK_HIP(ctx, hipMemcpyAsync(h_out, out, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+  unsigned long long h = 0;
+  SVK_HIP(ctx, hipMemcpyAsync(&h, hits, 8, hipMemcpyDeviceToHost, st));
   SVK_HIP(ctx, hipStreamSynchronize(st));
-  if (h_out[2] <= 0.0 || h_out[2] >= (double)n)
-    return svk_fail(ctx, SVK_ERR_BAD_ARG, "ROC needs both classes: %.0f positives of %lld", h_out[2], (long long)n);
+  *h_correct = (int64_t)h;
   return SVK_OK;
 }
 

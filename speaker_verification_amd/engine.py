@@ -65,6 +65,12 @@ def spec_from_seconds(fs, frame_length, frame_stride, nfft, num_filters, num_cep
     return FrontendSpec(fs, flen, stride, nfft, num_filters, num_ceps, out_kind, **kw)
 
 
+def split_step(n, k):
+    """Pairs per split of get_and_plot_k_eer_auc (evaluation.py:13, `int(n / float(k))`): n // k, the same number for
+    every n < 2^53 (svk_roc_k computes it so); the last n - k * step pairs belong to no split."""
+    return int(n) // int(k)
+
+
 class Engine:
     def __init__(self, device=None):
         torch = _torch()
@@ -583,6 +589,52 @@ class Engine:
         check(self.lib.svk_roc_eer(self.ctx, self._ptr(sc), self._ptr(lb), n, self._ptr(work), work.numel(), out),
               self.ctx)
         return float(out[0]), float(out[1])
+
+    def roc_k(self, scores, labels, k=1, curve=False):
+        """svk_roc_k: per split of `split_step(n, k)` consecutive pairs (evaluation.py:11-33), (eer, auc), or with
+        curve=True (eer, auc, fpr, tpr): sklearn's roc_curve(drop_intermediate=True) as float64 NumPy arrays, fps / fps[-1]
+        and tps / tps[-1] on the device's integer counts.  Raises for a split with one class or a non-finite score."""
+        torch = _torch()
+        sc = self.to_device(scores, torch.float32).reshape(-1)
+        lb = self.to_device(labels).reshape(-1)
+        lb = (lb != 0).to(torch.uint8) if lb.dtype != torch.uint8 else lb
+        n, k = sc.numel(), int(k)
+        if lb.numel() != n:
+            raise ValueError("scores and labels differ in length")
+        step = split_step(n, k) if k >= 1 else 0
+        work = torch.empty((max(1, int(self.lib.svk_roc_k_workspace_bytes(n, k))),), dtype=torch.uint8, device=self.device)
+        planes = torch.empty((2, k, step + 1), dtype=torch.int32, device=self.device) if curve and step >= 2 else None
+        out = (C.c_double * (4 * max(k, 1)))()
+        self._stream()
+        check(self.lib.svk_roc_k(self.ctx, self._ptr(sc), self._ptr(lb), n, k, self._ptr(work), work.numel(),
+                                 self._ptr(planes), out), self.ctx)
+        res = []
+        for s in range(k):
+            eer, auc, length = float(out[4 * s]), float(out[4 * s + 1]), int(out[4 * s + 3])
+            if planes is None:
+                res.append((eer, auc))
+                continue
+            fps, tps = (planes[p, s, :length].cpu().numpy().view(np.uint32).astype(np.float64) for p in (0, 1))
+            res.append((eer, auc, fps / fps[-1], tps / tps[-1]))
+        return res
+
+    def top1(self, scores, true_idx, want_labels=False):
+        """svk_top1 on a [n_rows, n_cols] score matrix: (argmax int32 [n_rows], correct, [labels uint8 [n_rows, n_cols]]),
+        tensors on the device.  true_idx[r]: the enrolled column of row r's speaker, -1 = not enrolled; argmax is
+        np.argmax's (first maximum, NaN first); correct counts the rows whose argmax is their true column."""
+        torch = _torch()
+        sc = self.to_device(scores, torch.float32)
+        tr = self.to_device(true_idx, torch.int32).reshape(-1)
+        if sc.dim() != 2 or tr.numel() != sc.shape[0]:
+            raise ValueError("top1 wants scores (n_rows, n_cols) and one true index per row")
+        n_rows, n_cols = int(sc.shape[0]), int(sc.shape[1])
+        amax = torch.empty((n_rows,), dtype=torch.int32, device=self.device)
+        labels = torch.empty((n_rows, n_cols), dtype=torch.uint8, device=self.device) if want_labels else None
+        correct = C.c_int64()
+        self._stream()
+        check(self.lib.svk_top1(self.ctx, self._ptr(sc), n_rows, n_cols, self._ptr(tr), self._ptr(amax), self._ptr(labels),
+                                C.byref(correct)), self.ctx)
+        return (amax, int(correct.value), labels) if want_labels else (amax, int(correct.value))
 
     def l2_dist(self, a, b):
         torch = _torch()

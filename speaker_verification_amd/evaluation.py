@@ -6,9 +6,12 @@ The reference scores one (utterance, speaker) pair per sklearn call inside a
 Python double loop (evaluation.py:67-84, 112-134); here the whole score matrix
 is one MFMA kernel launch (`svk_cosine_scores`), and the embeddings behind it
 come from the libsvk network kernels (`model.C3D2.forward` in eval mode on the
-device; `dataset_embeddings` for the file-driven entry points).  ROC / EER / AUC
-stay on the host exactly as the reference computes them (sklearn + scipy,
-evaluation.py:47-52); `get_eer_auc_device` is the device form (`svk_roc_eer`).
+device; `dataset_embeddings` for the file-driven entry points).  By default
+ROC / EER / AUC and the top-1 count stay on the host exactly as the reference
+computes them (sklearn + scipy, evaluation.py:47-52, 112-134).  `device=True`
+(`get_and_plot_k_eer_auc`, `evaluate`) keeps the score matrix on the GPU:
+`svk_top1` for the argmax, hits and one-hot labels, ONE `svk_roc_k` call for the
+k splits and their ROC curves; `get_eer_auc_device` is the single-split form.
 """
 import os
 
@@ -29,23 +32,34 @@ def get_eer_auc(label, distance):
     return eer, auc, fpr, tpr
 
 
-def get_eer_auc_device(label, distance):
-    """(eer, auc) like `get_eer_auc`, computed on the GPU (sort + scan + one pass over the ROC
+def get_eer_auc_device(label, distance, curve=False):
+    """(eer, auc) like `get_eer_auc`, computed on the GPU (radix sort + scans + one pass over the ROC
     points): for score sets that should not travel to the host (dev-set scale, 1.8e8 pairs).
-    Accepts NumPy arrays or CUDA tensors of any shape; no fpr / tpr arrays are returned."""
+    Accepts NumPy arrays or CUDA tensors of any shape.  curve=True: (eer, auc, fpr, tpr), the shape
+    `get_eer_auc` returns -- fpr / tpr bit-identical to sklearn's roc_curve (svk_roc_k, k = 1), which
+    also raises, as sklearn does, for NaN or infinite scores."""
+    if curve:
+        return get_engine().roc_k(distance, label, k=1, curve=True)[0]
     return get_engine().roc_eer(distance, label)
 
 
-def get_and_plot_k_eer_auc(label, scores, k=1, plot_path='eer_auc.png'):
+def get_and_plot_k_eer_auc(label, scores, k=1, plot_path='eer_auc.png', device=False):
     """Mean EER / AUC over k consecutive equal slices, printed in percent, ROC
     curves saved to `plot_path` when matplotlib is importable (evaluation.py:11-44).
-    Returns (mean_eer, mean_auc) in addition to the reference's prints."""
-    step = int(label.shape[0] / float(k))
+    Returns (mean_eer, mean_auc) in addition to the reference's prints.
+    device=True: one `svk_roc_k` call on the GPU for all k splits (labels / scores may be CUDA
+    tensors; the curves of the plot come from the device too)."""
     eers, aucs, curves = np.zeros((k, 1)), np.zeros((k, 1)), []
-    for split_num in range(k):
-        lo, hi = split_num * step, (split_num + 1) * step
-        eers[split_num], aucs[split_num], fpr, tpr = get_eer_auc(label[lo:hi], scores[lo:hi])
-        curves.append((fpr, tpr))
+    if device:
+        for split_num, res in enumerate(get_engine().roc_k(scores, label, k=k, curve=bool(plot_path))):
+            eers[split_num], aucs[split_num] = res[0], res[1]
+            curves.append(res[2:])
+    else:
+        step = int(label.shape[0] / float(k))
+        for split_num in range(k):
+            lo, hi = split_num * step, (split_num + 1) * step
+            eers[split_num], aucs[split_num], fpr, tpr = get_eer_auc(label[lo:hi], scores[lo:hi])
+            curves.append((fpr, tpr))
     print("EER=", np.mean(eers) * 100)
     print("AUC=", np.mean(aucs) * 100)
     if plot_path:
@@ -227,7 +241,29 @@ def load_indexed_labels(path):
     raise FileNotFoundError(f"{stem}.json / {stem}.txt not found ({path} is a pickle: not loaded)")
 
 
-def _evaluate_files(k, plot_path):
+def _true_columns(test_ids, speaker_ids):
+    """Column of each test id among the enrolled speaker ids (labels_from_ids' one-hot as an index), -1 for an id that
+    was never enrolled."""
+    col = {}
+    for j, sid in enumerate(speaker_ids):
+        col.setdefault(sid, j)
+    return np.array([col.get(t, -1) for t in test_ids], dtype=np.int32)
+
+
+def _device_top1_roc(scores, test_ids, speaker_ids, k, plot_path, print_lines):
+    """The device half of `evaluate(device=True)`: argmax / hits / one-hot labels (svk_top1), the reference's per-utterance
+    line from the argmax indices (print_lines: the file-driven form prints them, as the host path does), EER / AUC
+    (svk_roc_k).  scores: the device score matrix."""
+    amax, correct, labels = get_engine().top1(scores, _true_columns(test_ids, speaker_ids), want_labels=True)
+    amax = amax.cpu().numpy() if print_lines else ()
+    for i in range(len(amax)):
+        current_id = test_ids[i]
+        print('correct speaker {} , the speaker was closer to {}'.format(current_id, speaker_ids[int(amax[i])]))
+    eer, auc = get_and_plot_k_eer_auc(labels.reshape(-1), scores.reshape(-1), k=k, plot_path=plot_path, device=True)
+    return eer, auc, correct, labels
+
+
+def _evaluate_files(k, plot_path, device=False):
     """evaluation.py:90-146 as written: checkpoint, id list, id table, WAV tree and enrolled models
     under `constants.ROOT` / `constants.DATA_ORIGIN`."""
     from . import constants as c
@@ -243,6 +279,14 @@ def _evaluate_files(k, plot_path):
     ev = Evaluation(model, dir_path)
     speaker_model_ids = list(ev.speaker_models.keys())
     emb = dataset_embeddings(dataset, model)
+    if device:
+        test_ids = [f[0:7] for f in dataset.sound_files]
+        scores = get_engine().cosine_scores(emb, ev._enroll_matrix())
+        eer, auc, correct, labels = _device_top1_roc(scores, test_ids, speaker_model_ids, k, plot_path, True)
+        accuracy = correct * 100 / len(dataset)
+        print(f'Accuracy: {accuracy}%')
+        return {"eer": eer, "auc": auc, "accuracy": accuracy, "scores": scores, "labels": labels,
+                "speaker_ids": speaker_model_ids, "test_ids": test_ids}
     scores = get_engine().cosine_scores(emb, ev._enroll_matrix()).to("cpu").numpy().astype(np.float64)
     labels = np.zeros_like(scores)
     correct = 0
@@ -260,17 +304,27 @@ def _evaluate_files(k, plot_path):
             "speaker_ids": speaker_model_ids, "test_ids": [f[0:7] for f in dataset.sound_files]}
 
 
-def evaluate(model=None, cubes=None, test_ids=None, speaker_models=None, k=1, plot_path='eer_auc.png'):
+def evaluate(model=None, cubes=None, test_ids=None, speaker_models=None, k=1, plot_path='eer_auc.png', device=False):
     """`evaluate()` -- no arguments, like evaluation.py:90-146: read the checkpoint, the id list, the WAVs and
     the enrolled `{id}.pt` models from the paths in `constants`, score every utterance against every
     enrolled speaker (one batched front end + network + ONE cosine launch instead of the reference's
     per-utterance, per-speaker loop), print the reference's lines, save the ROC plot.
     `evaluate(model, cubes, test_ids, speaker_models)` is the same loop on in-memory data.
-    Returns a dict (the reference returns None): eer, auc, accuracy, scores, labels."""
+    Returns a dict (the reference returns None): eer, auc, accuracy, scores, labels -- float64 NumPy arrays.
+    device=True: the score matrix never leaves the GPU.  Accuracy comes from `svk_top1`, EER / AUC from ONE `svk_roc_k`
+    call, the labels from the enrolled column of each test id (-1, an all-zero row, for an id never enrolled); the
+    per-utterance lines are printed from the argmax indices.  `scores` and `labels` are then the DEVICE tensors
+    (float32 [n_test, n_speakers], uint8 one-hot)."""
     if model is None and cubes is None:
-        return _evaluate_files(k, plot_path)
+        return _evaluate_files(k, plot_path, device)
     ev = Evaluation(model, speaker_models)
     speaker_ids = list(ev.speaker_models.keys())
+    if device:
+        scores = ev.score_all(cubes)
+        eer, auc, correct, labels = _device_top1_roc(scores, list(test_ids), speaker_ids, k, plot_path, False)
+        accuracy = correct * 100 / max(1, len(test_ids))
+        print(f'Accuracy: {accuracy}%')
+        return {"eer": eer, "auc": auc, "accuracy": accuracy, "scores": scores, "labels": labels}
     scores = ev.score_all(cubes).to("cpu").numpy().astype(np.float64)
     labels = labels_from_ids(test_ids, speaker_ids)
     correct = int(sum(speaker_ids[int(np.argmax(scores[i]))] == test_ids[i] for i in range(len(test_ids))))
