@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SVK_VERSION 113 /* 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
+#define SVK_VERSION 114 /* 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
 
 typedef enum svk_status {
   SVK_OK = 0,
@@ -383,6 +383,28 @@ int svk_c3d2_conv42(svk_ctx* ctx, const float* d_in, int32_t n_utt, const float*
 size_t svk_c3d2_fc5_workspace_floats(int32_t n_utt);
 int svk_c3d2_fc5(svk_ctx* ctx, const float* d_in, int32_t n_utt, const float* d_wfrag, const float* d_bias, float* d_work,
                  float* d_out);
+
+/* The classification head, model.py:170-174 (forward, development=True: F.softmax(FC6(PReLu5(x)))) and the accuracy pass of
+ * train.py:104-119 (torch.max of that softmax, hits against the true labels), widened to top-k (csrc/head.hip):
+ *   d_emb    [n][128] f32 (svk_c3d2_fc5's output), 16-byte aligned;  prelu_slope: PReLu5's one slope
+ *   d_w6     [n_labels][128] f32, FC6.weight as stored (row-major, 16-byte aligned);  d_b6 [n_labels] f32
+ *   d_probs  NULL, or [n][n_labels] f32 (64-bit offsets): the softmax
+ *   d_topk   NULL, or [n][k] int32: label indices in descending order of p, ties to the lower index (1 <= k <= 8)
+ *   d_true   NULL, or [n] int32 true labels; then h_hits (HOST) [k] int64: hits[r] = rows whose true label is among their
+ *            first r + 1 (a label of -1 or outside [0, n_labels) never counts).  Synchronises the stream when d_true is given.
+ * Arithmetic, per row:
+ *   - z = PReLU5(x); l = FC6(z) in exact f32 on v_mfma_f32_16x16x4_f32: f32 products and accumulation in a fixed order
+ *     (eight 16-product fma chains added pairwise, then the bias), no half pairs;
+ *   - m = max l (NaN if a logit is NaN), e = exp(l - m), s = sum of e in f32 in a fixed order (compensated), p = e / s
+ *     (IEEE division);
+ *   - d_topk is the stable descending sort of the p the kernel writes (a NaN above every number, as torch.sort puts it), bit
+ *     for bit, whether or not d_probs is asked for: a NaN row's top-1 is its first NaN, as torch.argmax and svk_top1 give;
+ *   - a row's results depend on that row and the weights alone, not on n or the launch geometry; runs are bit-identical.
+ * 1 <= n_labels <= 65 536, n >= 0 (0: no launch).  SVK_ERR_BAD_ARG for k < 1 or k > n_labels when d_topk or d_true is given,
+ * NULL weights, d_true without h_hits; SVK_ERR_UNSUPPORTED for k > 8 or n_labels > 65 536.  No workspace: the hit counters
+ * live in the context. */
+int svk_c3d2_head(svk_ctx* ctx, const float* d_emb, int64_t n, int32_t n_labels, float prelu_slope, const float* d_w6,
+                  const float* d_b6, float* d_probs, int32_t k, int32_t* d_topk, const int32_t* d_true, int64_t* h_hits);
 
 
 /* ---- multi-GPU: the one exchange step of the path ------------------------------------------------

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsvk.so")
 
 SVK_OK = 0
-VERSION = 113                      # include/svk.h SVK_VERSION
+VERSION = 114                      # include/svk.h SVK_VERSION (0.1.12: + svk_c3d2_head)
 SVK_ERR_BAD_ARG, SVK_ERR_UNSUPPORTED, SVK_ERR_HIP, SVK_ERR_NO_DEVICE, SVK_ERR_OOM, SVK_ERR_RCCL = -1, -2, -3, -4, -5, -6
 OUT_MFE, OUT_LMFE, OUT_MFCC = 0, 1, 2
 PCM_I16, PCM_F32 = 0, 1
@@ -90,6 +90,7 @@ SIGNATURES = {
     "svk_c3d2_conv42": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
     "svk_c3d2_fc5_workspace_floats": (C.c_size_t, [_i32]),
     "svk_c3d2_fc5": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "svk_c3d2_head": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _i32, _vp, _vp, C.POINTER(_i64)]),
     "svk_comm_unique_id": (C.c_int, [_vp, C.c_char_p]),
     "svk_comm_init": (C.c_int, [_vp, C.c_char_p, _i32, _i32]),
     "svk_allgather_f32": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),

@@ -34,8 +34,9 @@ constexpr size_t SVK_SLOT_CONV32_42 = 96;      // svk_c3d2_conv32t; svk_c3d2_con
 constexpr size_t SVK_SLOT_CONV41 = 100;        // svk_c3d2_conv41 (1 word)
 constexpr size_t SVK_SLOT_STAGE1 = 112;        // svk_c3d2_stage1 / svk_c3d2_stage1_c3 (1 word)
 constexpr size_t SVK_SLOT_TOP1 = 120;          // svk_top1: the hit counter (1 u64)
+constexpr size_t SVK_SLOT_HEAD = 128;          // svk_c3d2_head: the hit counters of ranks 1 .. 8 (8 u64)
 static_assert(SVK_SLOT_STAGE2 + 8 <= SVK_SLOT_CONV31 && SVK_SLOT_STAGE1 + 4 <= SVK_SLOT_TOP1 && SVK_SLOT_TOP1 % 8 == 0 &&
-                  SVK_SLOT_TOP1 + 8 <= SVK_SCRATCH_BYTES,
+                  SVK_SLOT_TOP1 + 8 <= SVK_SLOT_HEAD && SVK_SLOT_HEAD % 8 == 0 && SVK_SLOT_HEAD + 64 <= SVK_SCRATCH_BYTES,
               "the scratch slots overlap or do not fit the handle's scratch");
 
 inline int svk_fail(svk_ctx* ctx, int code, const char* fmt, ...) {

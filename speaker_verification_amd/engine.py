@@ -562,6 +562,36 @@ class Engine:
                                     self._ptr(out)), self.ctx)
         return out
 
+    def c3d2_head(self, emb, tables, probs=True, k=1, true_idx=None):
+        """svk_c3d2_head: embeddings [n, 128] -> PReLU5 -> FC6 -> softmax (model.py:170-174).  tables = (w6 [n_labels, 128],
+        b6 [n_labels], slope) as `C3D2.fused_head()` holds them.  Returns (probs f32 [n, n_labels] | None, top-k int32 [n, k] |
+        None, hits | None), tensors on the device: the top-k when k is not None, hits (a list of k ints: rows whose true label
+        is among their first r + 1) when true_idx ([n] ints, -1 = none) is given."""
+        torch = _torch()
+        w6, b6, slope = tables
+        x = self.to_device(emb, torch.float32)
+        if x.dim() != 2 or x.shape[1] != 128:
+            raise ValueError("c3d2_head wants embeddings (n, 128)")
+        x = x.contiguous()
+        n, n_labels = int(x.shape[0]), int(w6.shape[0])
+        if tuple(w6.shape) != (n_labels, 128) or tuple(b6.shape) != (n_labels,) or w6.device != x.device or b6.device != x.device:
+            raise ValueError("c3d2_head wants FC6 tables w6 (n_labels, 128) and b6 (n_labels,) on the device")
+        if true_idx is not None and k is None:
+            raise ValueError("c3d2_head counts hits over the top-k: give k with true_idx")
+        tr = None
+        if true_idx is not None:
+            tr = self.to_device(true_idx, torch.int32).reshape(-1).contiguous()
+            if tr.numel() != n:
+                raise ValueError("c3d2_head wants one true label per row")
+        p = torch.empty((n, n_labels), dtype=torch.float32, device=self.device) if probs else None
+        top = torch.empty((n, int(k)), dtype=torch.int32, device=self.device) if k is not None and int(k) >= 1 else None
+        hits = (C.c_int64 * max(1, int(k) if k is not None else 1))()
+        self._stream()
+        check(self.lib.svk_c3d2_head(self.ctx, self._ptr(x), n, n_labels, float(slope), self._ptr(w6), self._ptr(b6),
+                                     self._ptr(p), int(k) if k is not None else 0, self._ptr(top), self._ptr(tr),
+                                     hits if tr is not None else None), self.ctx)
+        return p, top, ([int(v) for v in hits[:int(k)]] if tr is not None else None)
+
     def cosine_scores(self, test, enroll):
         torch = _torch()
         t = self.to_device(test, torch.float32)

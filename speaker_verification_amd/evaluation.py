@@ -332,3 +332,37 @@ def evaluate(model=None, cubes=None, test_ids=None, speaker_models=None, k=1, pl
     accuracy = correct * 100 / max(1, len(test_ids))
     print(f'Accuracy: {accuracy}%')
     return {"eer": eer, "auc": auc, "accuracy": accuracy, "scores": scores, "labels": labels}
+
+
+def identification_accuracy(model, data, labels=None, topk=(1, 5), batch=4096):
+    """train.py:104-119's accuracy pass as a function: which of the model's n_labels training speakers each input is.
+    `data`: cubes [n, C, 20, 80, 40] (tensor or array) with `labels` [n] (class indices), or a `load_data.AudioDataset`, whose
+    labels are `indexed[sound_files[i][0:7]]` (load_data.py:73) and whose embeddings come from `dataset_embeddings` (the same
+    crop draws from NumPy's global RNG).  The head runs through `C3D2.identify` (svk_c3d2_head on the device, no probability
+    matrix).  Returns {"top1": %, "top5": % (one key per entry of `topk`), "predicted": int32 [n] top-1 labels, "n": n}."""
+    k = max(topk)
+    device = next(model.parameters()).device
+    model.eval()
+    if hasattr(data, "sound_files"):
+        true = np.array([data.indexed[f[0:7]] for f in data.sound_files], dtype=np.int32)
+        emb = dataset_embeddings(data, model)
+        chunks = [(emb[lo:lo + batch], true[lo:lo + batch]) for lo in range(0, len(true), batch)]
+    else:
+        if labels is None:
+            raise ValueError("identification_accuracy on cubes needs their labels")
+        true = np.asarray(labels, dtype=np.int32).reshape(-1)
+        if len(true) != len(data):
+            raise ValueError("one label per cube")
+        chunks = ((torch.as_tensor(data[lo:lo + batch], dtype=torch.float32).to(device), true[lo:lo + batch])
+                  for lo in range(0, len(true), batch))
+    n = len(true)
+    hits = np.zeros(k, dtype=np.int64)
+    predicted = []
+    for x, t in chunks:
+        top, h = model.identify(x, k=k, true_idx=t)
+        hits += np.asarray(h, dtype=np.int64)
+        predicted.append(top[:, 0].cpu().numpy().astype(np.int32))
+    out = {"top%d" % r: (100.0 * float(hits[r - 1]) / n if n else 0.0) for r in topk}
+    out["predicted"] = np.concatenate(predicted) if predicted else np.zeros(0, dtype=np.int32)
+    out["n"] = n
+    return out

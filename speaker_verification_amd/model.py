@@ -19,6 +19,10 @@ Which code runs a forward:
   * training mode, gradients, other channel counts, tensors on the host: the torch layers
     (autograd needs them; the north-star leaves the training forward on PyTorch-ROCm).
 `model.inference_kernels = False` keeps an instance on the torch layers (A/B comparisons in tools).
+
+The classification head of `forward(x, development=True)` (PReLU5 -> FC6 -> softmax, model.py:170-174) runs on torch operators
+unless `model.head_kernels = True`, which sends it to `svk_c3d2_head` (csrc/head.hip) whenever the network itself runs on the
+kernels; `identify` (top-k labels, the accuracy pass of train.py:104-119) uses that kernel wherever the kernels apply.
 """
 import weakref
 
@@ -41,11 +45,13 @@ EMBED_DIM = 128
 _FLAT = 4 * 3 * 3 * 128
 CUBE_SHAPE = (1, 20, 80, 40)          # channel, crops, frames, coefficients (utils.py:20-21, 368-379)
 _EMBEDDERS = weakref.WeakKeyDictionary()   # model -> (state key, FusedEmbedder): kept off the module (deepcopy / pickling stay plain)
+_HEADS = weakref.WeakKeyDictionary()       # model -> (head key, FusedHead), the same way
 
 
 class C3D2(nn.Module):
     inference_kernels = True          # False on an instance: forward stays on the torch layers whatever the mode
     three_channel_kernels = False     # True on an instance (or the class): forward runs three-channel cubes on the kernels too
+    head_kernels = False              # True: forward(x, development=True) takes its softmax from svk_c3d2_head when x runs on the kernels
 
     def __init__(self, n_labels, num_channels):
         super().__init__()
@@ -84,11 +90,43 @@ class C3D2(nn.Module):
     def forward(self, x, development=True):
         if self.runs_on_kernels(x):
             x = self.fused_inference()(x)
+            if development and self.head_kernels:
+                return self.fused_head()(x, probs=True, k=None)[0]
         else:
             x = self.torch_layers(x)
         if development:
             x = F.softmax(self.FC6(self.PReLu5(x)), dim=1)
         return x
+
+    def _embeddings_on_kernels(self, emb):
+        """True when `identify` may hand the embeddings [n, 128] to svk_c3d2_head: forward's routing rules for a tensor that
+        is already FC5's output."""
+        return bool(self.inference_kernels and not self.training and isinstance(emb, torch.Tensor) and emb.is_cuda
+                    and emb.dim() == 2 and emb.shape[1] == EMBED_DIM and emb.dtype == torch.float32
+                    and not (torch.is_grad_enabled() and emb.requires_grad))
+
+    def identify(self, x, k=1, true_idx=None):
+        """The top-k speakers of each input, most probable first: cubes as forward takes them, or embeddings [n, 128].
+        Returns (top-k int32 [n, k], hits): hits[r] = inputs whose true_idx ([n], -1 = unknown) is among their first r + 1
+        labels, None without true_idx.  On svk_c3d2_head (no probability matrix is written) where the kernels apply; elsewhere
+        torch's softmax and a stable sort, ties to the lower label as the kernel breaks them."""
+        with torch.no_grad():
+            if x.dim() == 2:
+                emb, on_kernels = x, self._embeddings_on_kernels(x)
+            elif self.runs_on_kernels(x):
+                emb, on_kernels = self.fused_inference()(x), True
+            else:
+                emb, on_kernels = self.torch_layers(x), False
+            if on_kernels:
+                _, top, hits = self.fused_head()(emb, probs=False, k=k, true_idx=true_idx)
+                return top, hits
+            p = F.softmax(self.FC6(self.PReLu5(emb)), dim=1)
+            top = torch.sort(p, dim=1, descending=True, stable=True)[1][:, :k].to(torch.int32)
+            if true_idx is None:
+                return top, None
+            t = torch.as_tensor(true_idx, device=top.device).reshape(-1, 1).long()
+            first = (top.long() == t).long().cumsum(1).clamp(max=1)       # 1 from the true label's rank on
+            return top, [int(v) for v in first.sum(0)]
 
     def load_checkpoint(self, checkpoint_dict):
         """New model with `checkpoint_dict["state_dict"]` loaded; `module.`
@@ -124,6 +162,45 @@ class C3D2(nn.Module):
         if hit is None or hit[0] != key:
             hit = _EMBEDDERS[self] = (key, FusedEmbedder(self))
         return hit[1]
+
+    def _head_key(self):
+        """Identity and version of the head's tensors (FC6.*, PReLu5.*), which `_state_key` leaves out."""
+        return tuple((k, v.data_ptr(), v._version) for k, v in self.state_dict(keep_vars=True).items()
+                     if k.startswith(("FC6", "PReLu5")))
+
+    def fused_head(self):
+        """The classification head of the CURRENT weights for svk_c3d2_head: FC6's weight and bias as f32 tables, PReLu5's
+        slope.  Cached under its own key: a change to FC6 or PReLu5 rebuilds it, a change elsewhere does not."""
+        key = self._head_key()
+        hit = _HEADS.get(self)
+        if hit is None or hit[0] != key:
+            hit = _HEADS[self] = (key, FusedHead(self))
+        return hit[1]
+
+
+class FusedHead:
+    """model.py:170-174's PReLU5 -> FC6 -> softmax as svk_c3d2_head; a snapshot of the weights at build time."""
+
+    def __init__(self, model):
+        if model.PReLu5.weight.numel() != 1 or tuple(model.FC6.weight.shape[1:]) != (EMBED_DIM,):
+            raise ValueError("svk_c3d2_head takes FC6 (128 -> n_labels) behind a one-slope PReLU5 (model.py:138-139)")
+        with torch.no_grad():
+            self.w6 = model.FC6.weight.detach().to(torch.float32).contiguous().clone()
+            self.b6 = model.FC6.bias.detach().to(torch.float32).contiguous().clone()
+            self.slope = float(model.PReLu5.weight.detach().reshape(()))
+        self.n_labels = int(self.w6.shape[0])
+        self.device = self.w6.device
+
+    def tables(self):
+        return self.w6, self.b6, self.slope
+
+    @torch.no_grad()
+    def __call__(self, emb, probs=True, k=1, true_idx=None):
+        """embeddings [n, 128] on the device -> (probs [n, n_labels] | None, top-k int32 [n, k] | None, hits | None)."""
+        if self.device.type != "cuda":
+            raise RuntimeError("svk_c3d2_head runs on the GPU; move the model to the device -- there is no CPU fallback")
+        from .engine import get_engine
+        return get_engine(self.device.index).c3d2_head(emb, self.tables(), probs=probs, k=k, true_idx=true_idx)
 
 
 class FusedEmbedder:
