@@ -10,6 +10,9 @@ Every stage is a libsvk.so kernel, the C3D2 forward included (`svk_c3d2_stage1`,
 the module checkpoints load into.
 """
 import os
+import threading
+from concurrent.futures import ThreadPoolExecutor
+from functools import partial
 
 import numpy as np
 import torch
@@ -17,6 +20,77 @@ import torch
 from . import _lib
 from . import constants as c
 from .engine import get_engine, spec_from_seconds
+
+
+def _timed(spans, name, fn):
+    """fn() between two timing HIP events on the current stream, kept in `spans`: spans[name] = (start, end) in a dict,
+    (name, start, end) appended to a list; just fn() when spans is None."""
+    if spans is None:
+        return fn()
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    out = fn()
+    end.record()
+    if isinstance(spans, dict):
+        spans[name] = (start, end)
+    else:
+        spans.append((name, start, end))
+    return out
+
+
+class _Upload:
+    """Host -> device copies, issued in order from a helper thread on `stream`: a pageable copy holds its calling thread,
+    and the caller's thread keeps launching kernels meanwhile.  copies: (device dst, host src) pairs.  With `slots`, the
+    destinations repeat every `slots` copies: copy k is issued once the caller has released copy k - slots and runs once
+    the GPU has done the kernels queued before that release.  A failure in the helper is raised in the caller's `wait`;
+    leaving the `with` block releases everything (the helper never waits for a caller that failed) and joins the helper."""
+
+    def __init__(self, stream, copies, slots=0):
+        self.stream, self.slots = stream, slots
+        self.main = torch.cuda.current_stream(stream.device)
+        self.copied = [torch.cuda.Event() for _ in copies]
+        self.consumed = [torch.cuda.Event() for _ in copies]
+        self.issued = [threading.Event() for _ in copies]
+        self.released = [threading.Event() for _ in copies]
+        self.failure = []
+        stream.wait_stream(self.main)        # destinations may outlive a call: kernels queued before may still read them
+        self.worker = threading.Thread(target=self._run, args=(copies,), daemon=True)
+        self.worker.start()
+
+    def _run(self, copies):
+        try:
+            with torch.cuda.stream(self.stream):
+                for k, (dst, src) in enumerate(copies):
+                    if self.slots and k >= self.slots:
+                        self.released[k - self.slots].wait()
+                        self.stream.wait_event(self.consumed[k - self.slots])
+                    dst.copy_(src, non_blocking=True)
+                    self.copied[k].record(self.stream)
+                    self.issued[k].set()
+        except BaseException as err:
+            self.failure.append(err)
+            for ev in self.issued:
+                ev.set()
+
+    def wait(self, k):
+        """Order the caller's stream behind copy k."""
+        self.issued[k].wait()
+        if self.failure:
+            raise self.failure[0]
+        self.main.wait_event(self.copied[k])
+
+    def release(self, k):
+        """The kernels that read copy k are queued: its destination may take copy k + slots once they have run."""
+        self.consumed[k].record(self.main)
+        self.released[k].set()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for ev in self.released:
+            ev.set()
+        self.worker.join()
 
 
 class VerificationPipeline:
@@ -57,7 +131,7 @@ class VerificationPipeline:
         self.rng = np.random.RandomState(crop_seed)
         self.last_stats = {}
         self.overlap_front = bool(overlap_front)
-        self._side_stream = None
+        self._stream_pair, self._buffers, self._packers = None, {}, None       # made on first use, kept across calls
 
     def refresh_model(self):
         """Re-snapshot the (BN-folded) inference weights after the model's state changed."""
@@ -89,7 +163,6 @@ class VerificationPipeline:
     def voiced(self, pcm):
         """[n, L] int16 -> (packed voiced samples [n, L] int16, voiced_len [n] i32)."""
         if not self.use_vad:
-            n, L = pcm.shape
             return pcm, None
         res = self.eng.vad_energy(pcm, self.vad_threshold, fs=c.SAMPLE_RATE, frame_ms=c.VAD_FRAME_MS,
                                   padding_ms=c.VAD_PADDING_MS, compact=True)
@@ -131,12 +204,7 @@ class VerificationPipeline:
         pcm = self.eng.to_device(pcm)
         crops, cubes = [], []
         for lo, hi in self.chunks(pcm.shape[0]):
-            vlen, gather = self.vad(pcm[lo:hi])
-            feat, n_frames = self.features(pcm[lo:hi], vlen, gather)
-            if self.crop_rng == "device":
-                idx = self.eng.draw_crops(n_frames, c.CUBE_CROPS, c.CUBE_FRAMES, self.crop_seed, first_utt + lo, self.bad_clips)
-            else:
-                idx = self.draw_crops(n_frames.to("cpu").numpy())
+            feat, _, idx = self._front(pcm[lo:hi], first_utt + lo)
             if want_cubes:
                 cubes.append(self.cubes(feat, idx))
             crops.append(idx.cpu().numpy() if hasattr(idx, "cpu") else np.asarray(idx))
@@ -152,18 +220,26 @@ class VerificationPipeline:
         feature rows and crop starts itself; the other six kernels follow (model.FusedEmbedder.embed_features)."""
         if self.kernel_events is None:
             return self.embedder.embed_features(feat, crop_idx)
-        spans = {"cubes": feat.shape[0]}
-
-        def timed(name, fn):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            out = fn()
-            b.record()
-            spans[name] = (a, b)
-            return out
-        out = self.embedder.embed_features(feat, crop_idx, timed)
-        self.kernel_events.append(spans)
+        events = {"cubes": feat.shape[0]}
+        out = self.embedder.embed_features(feat, crop_idx, partial(_timed, events))
+        self.kernel_events.append(events)
         return out
+
+    def _crop_starts(self, n_frames, first, crop_idx=None):
+        """Crop starts of a micro-batch whose row 0 is clip `first`: the caller's `crop_idx` (host) if given, else drawn on
+        the device keyed by the global clip index, else from the host RNG in clip order."""
+        if crop_idx is not None:
+            return np.asarray(crop_idx, dtype=np.int32)
+        if self.crop_rng == "device":
+            return self.eng.draw_crops(n_frames, c.CUBE_CROPS, c.CUBE_FRAMES, self.crop_seed, first, self.bad_clips)
+        return self.draw_crops(n_frames.to("cpu").numpy())      # tiny D2H: T per utterance
+
+    def _front(self, chunk, first, crop_idx=None):
+        """The front step of a [n, L] device chunk of uniform clips whose row 0 is clip `first`: VAD (index form, nothing
+        copied) -> front end -> CMVN -> crop starts.  Returns (feat, n_frames, crop starts)."""
+        vlen, gather = self.vad(chunk)
+        feat, n_frames = self.features(chunk, vlen, gather)
+        return feat, n_frames, self._crop_starts(n_frames, first, crop_idx)
 
     # ---- whole path ---------------------------------------------------------------------
     def embed(self, pcm, crop_idx=None, return_intermediates=False, first_utt=0):
@@ -178,46 +254,31 @@ class VerificationPipeline:
                 and len(spans) > 1):
             return self._embed_overlapped(pcm, spans, emb, first_utt)
         for lo, hi in spans:
-            chunk = pcm[lo:hi]
+            chunk, given = pcm[lo:hi], None if crop_idx is None else crop_idx[lo:hi]
             if return_intermediates:                       # the packed voiced samples are part of what is handed back
                 voiced, vlen = self.voiced(chunk)
                 feat, n_frames = self.features(voiced, vlen)
-            else:
-                vlen, gather = self.vad(chunk)
-                feat, n_frames = self.features(chunk, vlen, gather)
-            if crop_idx is None and self.crop_rng == "device":
-                idx = self.eng.draw_crops(n_frames, c.CUBE_CROPS, c.CUBE_FRAMES, self.crop_seed,
-                                          first_utt + lo, self.bad_clips)
-            elif crop_idx is None:
-                idx = self.draw_crops(n_frames.to("cpu").numpy())      # tiny D2H: T per utterance
-            else:
-                idx = np.asarray(crop_idx[lo:hi], dtype=np.int32)
-            if return_intermediates:
+                idx = self._crop_starts(n_frames, first_utt + lo, given)
                 cube = self.cubes(feat, idx)
                 emb[lo:hi] = self.embed_cubes(cube)
                 inter.append({"lo": lo, "hi": hi, "voiced": voiced, "voiced_len": vlen, "feat": feat,
                               "n_frames": n_frames, "crop_idx": idx, "cube": cube})
             else:
+                feat, _, idx = self._front(chunk, first_utt + lo, given)
                 emb[lo:hi] = self.embed_features(feat, idx)
         return (emb, inter) if return_intermediates else emb
 
     def _embed_overlapped(self, pcm, spans, emb, first_utt):
         """Two HIP streams: the side stream turns micro-batch k+1 into features + crop starts (HBM / VALU work) while the
         main stream runs the MFMA-bound network on micro-batch k."""
-        dev = self.eng.device
-        main = torch.cuda.current_stream(dev)
-        if self._side_stream is None:
-            self._side_stream = torch.cuda.Stream(device=dev)
-        side = self._side_stream
+        main = torch.cuda.current_stream(self.eng.device)
+        side = self._streams()[1]
         side.wait_stream(main)                     # whatever produced `pcm` is ordered before the side stream
 
         def stage(k):
             lo, hi = spans[k]
             with torch.cuda.stream(side):
-                vlen, gather = self.vad(pcm[lo:hi])
-                feat, n_frames = self.features(pcm[lo:hi], vlen, gather)
-                idx = self.eng.draw_crops(n_frames, c.CUBE_CROPS, c.CUBE_FRAMES, self.crop_seed, first_utt + lo,
-                                          self.bad_clips)
+                feat, _, idx = self._front(pcm[lo:hi], first_utt + lo)
                 done = torch.cuda.Event()
                 done.record(side)
             return (feat, idx), done
@@ -234,15 +295,13 @@ class VerificationPipeline:
         side.wait_stream(main)
         return emb
 
-    def _ragged_batches(self, lengths, max_batch_samples, max_feature_bytes=1 << 30, max_padding=None):
+    def _ragged_batches(self, lengths, max_batch_samples, max_feature_bytes=1 << 30, max_padding=2.0):
         """Clip indices sorted by length and cut into batches of at most `micro_batch` clips and `max_batch_samples`
         samples (16-byte-aligned clip slots): a batch costs its own samples, not n x the longest clip -- up to a point: the
         front end enumerates clips x tiles-of-the-LONGEST-clip and the feature buffer is sized the same way, so a batch also
         ends where its padded size (clips x longest) would pass `max_padding` (2 by default) x its real size (the long tail of a VoxCeleb-like
         length distribution otherwise makes one batch of 12 .. 145 s clips that is 88 % padding).  NumPy throughout: the plan
         of 2 048 clips takes ~0.1 ms (a Python loop over clips took 1 ms, with the GPU idle)."""
-        if max_padding is None:
-            max_padding = float(os.environ.get("SVK_RAGGED_PADDING", "2.0"))
         lengths = np.asarray(lengths, dtype=np.int64)
         n = lengths.size
         if not n:
@@ -312,16 +371,7 @@ class VerificationPipeline:
         copies nothing (the front end reads the kept frames where they lie, svk_frontend_run's d_src_chunk) and the
         normalisation (utils.py:382-397) is applied by the cube gather to the 20 x 80 rows the network reads, not to every row
         of a clip.  Nothing here touches the host."""
-        def timed(name, fn):
-            if spans is None:
-                return fn()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            out = fn()
-            b.record()
-            spans.append((name, a, b))
-            return out
-
+        timed = partial(_timed, spans)
         dev_lens, gather = lens, None
         if self.use_vad:
             dev_lens, gather = timed("vad", lambda: self.vad(dev_buf, lengths=lens, offsets=offs, longest=longest))
@@ -351,42 +401,77 @@ class VerificationPipeline:
             self.rows = hit.view(self.cap, c.CUBE_CROPS * c.CUBE_FRAMES, c.NUM_COEF)
             self.at = self.done = 0            # cubes gathered / handed to the network so far (absolute counts)
 
-        def _event(self):
-            if self.spans is None:
-                return None
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            return ev
-
         def push(self, feat, idx, stats=None):
             n = feat.shape[0]
             assert n <= self.step, "a batch must not exceed the network step"
-            a = self._event()
             w = self.at % self.cap
             first = min(n, self.cap - w)
-            self.pipe.eng.cube_gather(feat[:first], idx[:first], c.CUBE_FRAMES, out=self.cubes[w:w + first],
-                                      stats=None if stats is None else stats[:first])
-            if first < n:                        # the batch wraps around the end of the ring
-                self.pipe.eng.cube_gather(feat[first:], idx[first:], c.CUBE_FRAMES, out=self.cubes[:n - first],
-                                          stats=None if stats is None else stats[first:])
-            if a is not None:
-                self.spans.append(("gather", a, self._event()))
+
+            def gather():
+                self.pipe.eng.cube_gather(feat[:first], idx[:first], c.CUBE_FRAMES, out=self.cubes[w:w + first],
+                                          stats=None if stats is None else stats[:first])
+                if first < n:                    # the batch wraps around the end of the ring
+                    self.pipe.eng.cube_gather(feat[first:], idx[first:], c.CUBE_FRAMES, out=self.cubes[:n - first],
+                                              stats=None if stats is None else stats[first:])
+            _timed(self.spans, "gather", gather)
             self.at += n
             while self.at - self.done >= self.step:
                 self._network(self.step)
 
         def _network(self, n):
             lo = self.done % self.cap              # a multiple of `step`: [lo, lo + n) never wraps
-            a = self._event()
-            out = self.pipe.embed_features(self.rows[lo:lo + n], self.pipe.embedder.crop_starts(n, self.cubes.device))
-            self.emb[self.order[self.done:self.done + n]] = out
-            if a is not None:
-                self.spans.append(("network", a, self._event()))
+
+            def network():
+                out = self.pipe.embed_features(self.rows[lo:lo + n], self.pipe.embedder.crop_starts(n, self.cubes.device))
+                self.emb[self.order[self.done:self.done + n]] = out
+            _timed(self.spans, "network", network)
             self.done += n
 
         def finish(self):
             if self.at > self.done:
                 self._network(self.at - self.done)
+
+    def _streams(self):
+        """(upload stream, side stream), made on first use: every host -> device copy of the pipeline runs on the first, the
+        front steps of the overlap form on the second."""
+        if self._stream_pair is None:
+            self._stream_pair = (torch.cuda.Stream(device=self.eng.device), torch.cuda.Stream(device=self.eng.device))
+        return self._stream_pair
+
+    def _staging(self, numel, pinned=False):
+        """Two 1-D int16 buffers of at least `numel` samples, on the device or in pinned host memory: the upload of batch
+        k + 1 fills one while the kernels read batch k from the other.  Kept across calls, grown when a call needs more."""
+        bufs = self._buffers.get(pinned)
+        if bufs is None or bufs[0].numel() < numel:
+            bufs = self._buffers[pinned] = [torch.empty((numel,), dtype=torch.int16, pin_memory=True) if pinned else
+                                            torch.empty((numel,), dtype=torch.int16, device=self.eng.device) for _ in range(2)]
+        return bufs
+
+    def _ragged_loop(self, emb, plan, offsets, lengths, step, first_utt, spans, fetch, release=None):
+        """The body of both ragged forms.  plan: the clip indices of every batch, in the order they run; offsets / lengths:
+        per clip, into the buffer fetch(k) returns for batch k once the current stream is ordered behind its upload;
+        release(k): batch k's buffer has been read.  Embeddings land in emb[clip index]."""
+        dev = self.eng.device
+        # the whole schedule goes up ONCE, before the loop: a host array handed to a launch is a synchronous copy that waits
+        # for everything queued before it
+        order = np.concatenate(plan).astype(np.int64)
+        order_dev = torch.from_numpy(order).to(dev)
+        keys_dev = order_dev + int(first_utt)
+        offs_dev = torch.from_numpy(offsets[order]).to(dev)
+        lens_dev = torch.from_numpy(lengths[order].astype(np.int32)).to(dev)
+        ring = self._CubeRing(self, step, emb, order_dev, spans)
+        pos = 0
+        for k, ids in enumerate(plan):
+            sl = slice(pos, pos + len(ids))
+            feat, idx, stats = self._ragged_front(fetch(k), offs_dev[sl], lens_dev[sl], int(lengths[ids].max()), keys_dev[sl],
+                                                  spans=spans)
+            if release is not None:
+                release(k)
+            # the network runs as soon as a full step of cubes has gathered: its kernels then cover the host side of the
+            # next batch
+            ring.push(feat, idx, stats)
+            pos += len(ids)
+        ring.finish()
 
     def embed_ragged(self, clips, max_batch_samples=64 * 1024 * 1024, first_utt=0, spans=None):
         """Clips of DIFFERENT lengths (VoxCeleb1 utterances run from 4 to 145 s): `clips` is a list of 1-D
@@ -402,76 +487,48 @@ class VerificationPipeline:
         batches = self._ragged_batches(lengths, max_batch_samples)
         if not batches:
             return emb
+        offsets = np.empty_like(lengths)                   # of each clip in its batch's staging buffer
+        for ids, _ in batches:
+            slots = (lengths[ids] + 7) // 8 * 8
+            offsets[ids] = np.cumsum(slots) - slots
         # Two pinned host buffers + two device buffers: batch k + 1 is packed by 8 host threads (np.copyto releases the
-        # GIL) and copied on a side stream while the GPU works on batch k -- the host-side np.zeros + clip-by-clip copy +
+        # GIL) and copied on the upload stream while the GPU works on batch k -- the host-side np.zeros + clip-by-clip copy +
         # pageable upload of the first version was 8 x the GPU time of the whole workload.
         cap = max(total for _, total in batches)
-        if getattr(self, "_rag_cap", 0) < cap:
-            self._rag_cap = cap
-            self._rag_pinned = [torch.empty((cap,), dtype=torch.int16).pin_memory() for _ in range(2)]
-            self._rag_np = [t.numpy() for t in self._rag_pinned]
-            self._rag_dev = [torch.empty((cap,), dtype=torch.int16, device=dev) for _ in range(2)]
-            self._rag_stream = torch.cuda.Stream(device=dev)
-            from concurrent.futures import ThreadPoolExecutor
-            self._rag_threads = int(os.environ.get("SVK_RAGGED_THREADS", "8"))
-            self._rag_pool = ThreadPoolExecutor(max_workers=self._rag_threads)
-        # every batch's clip order, batch-local offsets and lengths go up ONCE, before the loop: a host array handed to a
-        # launch is a synchronous copy that waits for everything queued before it
-        order = np.concatenate([np.asarray(b, dtype=np.int64) for b, _ in batches])
-        lens_sorted = lengths[order]
-        offs_sorted = np.empty_like(order)
-        pos = 0
-        for batch, _ in batches:
-            slots = (lens_sorted[pos:pos + len(batch)] + 7) // 8 * 8
-            offs_sorted[pos:pos + len(batch)] = np.concatenate([[0], np.cumsum(slots)[:-1]])
-            pos += len(batch)
-        order_dev = torch.from_numpy(order).to(dev)
-        keys_dev = order_dev + int(first_utt)
-        offs_dev = torch.from_numpy(offs_sorted).to(dev)
-        lens_dev = torch.from_numpy(lens_sorted.astype(np.int32)).to(dev)
+        pinned, staged = self._staging(cap, pinned=True), self._staging(cap)
+        threads = int(os.environ.get("SVK_RAGGED_THREADS", "8"))
+        if self._packers is None or self._packers[0] != threads:
+            self._packers = (threads, ThreadPoolExecutor(max_workers=threads))
+        pool = self._packers[1]
         main = torch.cuda.current_stream(dev)
-        copy_stream = self._rag_stream
-        copy_stream.synchronize()                          # a previous call's copies may still read the pinned buffers
-        copy_stream.wait_stream(main)
+        upload = self._streams()[0]
+        upload.synchronize()                               # a previous call's copies may still read the pinned buffers
+        upload.wait_stream(main)
         copied = [torch.cuda.Event() for _ in range(2)]
         consumed = [torch.cuda.Event() for _ in range(2)]
-        starts = np.concatenate([[0], np.cumsum([len(b) for b, _ in batches])])
 
-        def stage(k):
-            batch, total = batches[k]
+        def fetch(k):                                      # host packing + H2D of batch k, under the kernels of batch k - 1
+            ids, total = batches[k]
             slot = k & 1
             if k >= 2:
                 consumed[slot].synchronize()               # the GPU is done with what this pinned / device pair held
-            offs = offs_sorted[starts[k]:starts[k + 1]]
-            dst = self._rag_np[slot]
+            dst = pinned[slot].numpy()
 
             def put(lo, hi):
-                for q in range(lo, hi):
-                    src = np.asarray(clips[batch[q]], dtype=np.int16)
-                    np.copyto(dst[offs[q]:offs[q] + src.size], src, casting="no")
-            step = -(-len(batch) // self._rag_threads)
-            jobs = [self._rag_pool.submit(put, lo, min(len(batch), lo + step)) for lo in range(0, len(batch), step)]
-            for jb in jobs:
-                jb.result()
-            with torch.cuda.stream(copy_stream):
-                self._rag_dev[slot][:total].copy_(self._rag_pinned[slot][:total], non_blocking=True)
-                copied[slot].record(copy_stream)
-
-        ring = self._CubeRing(self, self.micro_batch, emb, order_dev, spans)
-        stage(0)
-        for k, (batch, total) in enumerate(batches):
-            slot = k & 1
+                for q in ids[lo:hi]:
+                    src = np.asarray(clips[q], dtype=np.int16)
+                    np.copyto(dst[offsets[q]:offsets[q] + src.size], src, casting="no")
+            step = -(-len(ids) // threads)
+            for job in [pool.submit(put, lo, lo + step) for lo in range(0, len(ids), step)]:
+                job.result()
+            with torch.cuda.stream(upload):
+                staged[slot][:total].copy_(pinned[slot][:total], non_blocking=True)
+                copied[slot].record(upload)
             main.wait_event(copied[slot])
-            sl = slice(int(starts[k]), int(starts[k + 1]))
-            feat, idx, stats = self._ragged_front(self._rag_dev[slot][:total], offs_dev[sl], lens_dev[sl], int(lens_sorted[sl].max()),
-                                                  keys_dev[sl], spans=spans)
-            consumed[slot].record(main)
-            # the network runs as soon as a full micro-batch of cubes has gathered: its kernels then cover the host-side
-            # packing of the next batch
-            ring.push(feat, idx, stats)
-            if k + 1 < len(batches):
-                stage(k + 1)                               # host packing + H2D of the next batch under this batch's kernels
-        ring.finish()
+            return staged[slot][:total]
+
+        self._ragged_loop(emb, [ids for ids, _ in batches], offsets, lengths, self.micro_batch, first_utt, spans, fetch,
+                          release=lambda k: consumed[k & 1].record(main))
         return emb
 
     def embed_ragged_resident(self, buf, offsets, lengths, max_batch_samples=64 * 1024 * 1024, first_utt=0, spans=None):
@@ -482,7 +539,7 @@ class VerificationPipeline:
             the voiced frames (the VAD hands the front end an index of them);
           * a HOST NumPy array (a loader that decodes into one arena): uploaded as it is, no per-clip packing on the host
             (the list form, `embed_ragged`, is bound by that packing: ~20 GB/s of host copy against 54 GB/s of pageable
-            upload on the GPU box).  Arenas larger than two batches go up in pieces of ~`max_batch_samples` on a side
+            upload on the GPU box).  Arenas larger than two batches go up in pieces of ~`max_batch_samples` on the upload
             stream from a helper thread, and the clips of piece p run (length-sorted among themselves) while piece p + 1
             travels."""
         if self.crop_rng != "device":
@@ -513,137 +570,52 @@ class VerificationPipeline:
         groups, pieces = [np.arange(len(lengths))], [(0, n_samples)]
         if host and n_samples > 2 * max_batch_samples:
             groups, pieces = self._upload_groups(offsets, lengths, n_samples, max_batch_samples)
-        # the whole schedule is known from the lengths: plan every group's batches and upload order / offsets / lengths ONCE
-        plan = []                                             # (group, clip indices of the batch, longest clip)
+        plan, group_of = [], []                               # every group's batches, in group order
         for g, idx in enumerate(groups):
             for batch, _ in self._ragged_batches(lengths[idx], max_batch_samples):
-                ids = idx[np.asarray(batch, dtype=np.int64)]
-                plan.append((g, ids, int(lengths[ids].max())))
-        order = np.concatenate([ids for _, ids, _ in plan]).astype(np.int64)
-        order_dev = torch.from_numpy(order).to(dev)
-        keys_dev = order_dev + int(first_utt)
-        offs_dev = torch.from_numpy(offsets[order]).to(dev)
-        lens_dev = torch.from_numpy(lengths[order]).to(dev)
-        flags, events, worker = None, None, None
-        if host:
-            import threading
-            if getattr(self, "_up_stream", None) is None:
-                self._up_stream = torch.cuda.Stream(device=dev)
-            dev_buf = torch.empty((n_samples,), dtype=torch.int16, device=dev)
-            flags = [threading.Event() for _ in pieces]
-            events = [torch.cuda.Event() for _ in pieces]
-            self._up_stream.wait_stream(torch.cuda.current_stream(dev))
-            src = torch.from_numpy(buf)
-
-            failure = []
-
-            def upload():   # (pageable copies hold their calling thread: a helper thread, so that the main one keeps launching)
-                try:
-                    with torch.cuda.stream(self._up_stream):
-                        for g, (a, b) in enumerate(pieces):
-                            dev_buf[a:b].copy_(src[a:b], non_blocking=True)
-                            events[g].record(self._up_stream)
-                            flags[g].set()
-                except BaseException as err:   # surfaces in the caller's thread; nobody is left waiting
-                    failure.append(err)
-                    for f in flags:
-                        f.set()
-            worker = threading.Thread(target=upload, daemon=True)
-            worker.start()
-            buf = dev_buf
+                plan.append(idx[np.asarray(batch, dtype=np.int64)])
+                group_of.append(g)
         # with pieces still travelling the network runs per micro-batch of gathered cubes (it covers the next piece's upload);
         # otherwise over micro-batches as large as the main path's
         step = self.micro_batch if len(groups) > 1 else max(self.micro_batch, 4096)
-        ring = self._CubeRing(self, step, emb, order_dev, spans)
-        main = torch.cuda.current_stream(dev)
-        pos, seen = 0, -1
-        for g, ids, longest in plan:
-            if flags is not None and g != seen:
-                flags[g].wait()
-                if failure:
-                    worker.join()
-                    raise failure[0]
-                main.wait_event(events[g])
-                seen = g
-            sl = slice(pos, pos + len(ids))
-            feat, idx, stats = self._ragged_front(buf, offs_dev[sl], lens_dev[sl], longest, keys_dev[sl], spans=spans)
-            ring.push(feat, idx, stats)
-            pos += len(ids)
-        if worker is not None:
-            worker.join()
-        ring.finish()
+        if not host:
+            self._ragged_loop(emb, plan, offsets, lengths, step, first_utt, spans, lambda k: buf)
+            return emb
+        src = torch.from_numpy(buf)
+        buf = torch.empty((n_samples,), dtype=torch.int16, device=dev)
+        with _Upload(self._streams()[0], [(buf[a:b], src[a:b]) for a, b in pieces]) as up:
+            def fetch(k):                                     # the first batch of a piece waits for that piece
+                if k == 0 or group_of[k] != group_of[k - 1]:
+                    up.wait(group_of[k])
+                return buf
+            self._ragged_loop(emb, plan, offsets, lengths, step, first_utt, spans, fetch)
         return emb
 
     def embed_host(self, pcm_host, first_utt=0):
         """Host-fed variant of `embed`: `pcm_host` is a [n, L] int16 NumPy array (e.g. decoded WAVs) or a CPU torch
-        tensor, pinned or not.  Micro-batches go through a copy stream and two device buffers, so the H2D copy of batch
+        tensor, pinned or not.  Micro-batches go through the upload stream and two device buffers, so the H2D copy of batch
         k + 1 overlaps the kernels of batch k (96 kB per 3 s clip over PCIe).  A HELPER THREAD issues the
         copies: a pageable upload holds its calling thread (the runtime stages it through its own pinned chunks, 54 GB/s on
         the GPU box -- faster than the 20 GB/s at which this process could copy into a pinned buffer of its own, the
         round-2 form), and the main thread keeps launching kernels."""
         if self.crop_rng != "device":
             raise ValueError("embed_host overlaps copies with compute and needs crop_rng='device'")
-        import threading
         src = pcm_host if isinstance(pcm_host, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pcm_host))
         if src.dtype != torch.int16 or src.dim() != 2 or src.is_cuda:
             raise ValueError("pcm_host must be a [n, L] int16 array in host memory")
         n, L = src.shape
-        dev = self.eng.device
         spans = self.chunks(n)
-        emb = torch.empty((n, 128), dtype=torch.float32, device=dev)
+        emb = torch.empty((n, 128), dtype=torch.float32, device=self.eng.device)
         if not spans:
             return emb
-        size = max(hi - lo for lo, hi in spans)
-        key = (size, L)
-        if getattr(self, "_host_key", None) != key:
-            self._host_key = key
-            self._staged = [torch.empty((size, L), dtype=torch.int16, device=dev) for _ in range(2)]
-            self._copy_stream = torch.cuda.Stream(device=dev)
-        staged, copy_stream = self._staged, self._copy_stream
-        main = torch.cuda.current_stream(dev)
-        # The staged buffers outlive the call: kernels of a previous call on `main` may still READ them.
-        copy_stream.wait_stream(main)
-        copied = [torch.cuda.Event() for _ in spans]
-        consumed = [torch.cuda.Event() for _ in spans]
-        issued = [threading.Event() for _ in spans]      # host side: copy k is queued / batch k's kernels are queued
-        launched = [threading.Event() for _ in spans]
-        failure = []
-
-        def uploader():
-            try:
-                with torch.cuda.stream(copy_stream):
-                    for k, (lo, hi) in enumerate(spans):
-                        if k >= 2:                        # the slot's previous batch must have been consumed by the GPU
-                            launched[k - 2].wait()
-                            copy_stream.wait_event(consumed[k - 2])
-                        staged[k & 1][:hi - lo].copy_(src[lo:hi], non_blocking=True)
-                        copied[k].record(copy_stream)
-                        issued[k].set()
-            except BaseException as err:                  # surface it in the caller's thread
-                failure.append(err)
-                for ev in issued:
-                    ev.set()
-
-        worker = threading.Thread(target=uploader, daemon=True)
-        worker.start()
-        try:
+        staged = self._staging(max(hi - lo for lo, hi in spans) * L)
+        copies = [(staged[k & 1][:(hi - lo) * L].view(hi - lo, L), src[lo:hi]) for k, (lo, hi) in enumerate(spans)]
+        with _Upload(self._streams()[0], copies, slots=2) as up:
             for k, (lo, hi) in enumerate(spans):
-                issued[k].wait()
-                if failure:
-                    raise failure[0]
-                main.wait_event(copied[k])
-                chunk = staged[k & 1][:hi - lo]
-                vlen, gather = self.vad(chunk)
-                feat, n_frames = self.features(chunk, vlen, gather)
-                idx = self.eng.draw_crops(n_frames, c.CUBE_CROPS, c.CUBE_FRAMES, self.crop_seed, first_utt + lo,
-                                          self.bad_clips)
+                up.wait(k)
+                feat, _, idx = self._front(copies[k][0], first_utt + lo)
                 emb[lo:hi] = self.embed_features(feat, idx)
-                consumed[k].record(main)
-                launched[k].set()
-        finally:
-            for ev in launched:                           # never leave the helper waiting
-                ev.set()
-            worker.join()
+                up.release(k)
         return emb
 
     def score(self, test_emb, enroll_emb):

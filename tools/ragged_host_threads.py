@@ -29,8 +29,7 @@ for k in range(n):
 pipe = VerificationPipeline(seeded_model(2024, n_labels=1211), use_vad=True, normalize=True, preemph_cof=0.98, crop_rng="device",
                             micro_batch=1024)
 for threads in (4, 8, 12, 16, 24, 32):
-    os.environ["SVK_RAGGED_THREADS"] = str(threads)
-    pipe._rag_cap = 0                      # rebuild the staging buffers and the pool
+    os.environ["SVK_RAGGED_THREADS"] = str(threads)         # embed_ragged makes a new packing pool when it changes
     pipe.embed_ragged(clips)
     torch.cuda.synchronize()
     ts = []
