@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path on MI355X (contract: see the task prompt / DESIGN.md section 6).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 One STEP = one pass of the whole path over BASELINE.json's corpus, 148 642 synthetic 3 s / 16 kHz clips,
 sharded over the N ranks (rank r owns the contiguous range of ceil(148 642 / N) clips; STRONG scaling:
@@ -18,7 +18,11 @@ Launch: with WORLD_SIZE in the environment (torch.distributed.run) this process 
 and --gpus N > 1 this process only starts N fresh rank processes of itself (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_ADDR / MASTER_PORT set), polls them, ends the others when one dies, relays rank 0's JSON line.
 
-The JSON line also carries
+A plain run does what its result line needs and no more: set up, warm up, time the K steps, write --dump-outputs, print
+the line (metric, value, unit, higher_is_better, dtype, ms_per_step, the configuration; ranks_seen / backend / allgather_us /
+per_rank_ms / slowest_rank / fastest_rank: what torch.distributed reports, the HIP-event time of the embedding all-gather,
+every rank's own step time).  With --full the line also carries what the headline does not need:
+  eer           -- the EER / AUC of the 4 874 x 40 score matrix through host sklearn and svk_roc_eer;
   roofline      -- the dominant kernel, c3d2_stage1h_kernel (cube + conv1_1 + conv1_2 + pool1 through two-piece f16 products,
                    ~30 % of the step), bound MFMA: frac = ISSUED matrix work (SQ_INSTS_MFMA per cube from the committed PMC
                    pass x 16 384 FLOP x cubes per launch) / the HIP-event duration of each launch in the timed region / the
@@ -37,19 +41,19 @@ The JSON line also carries
   roofline_e2e  -- the whole step: frac = the time the matrix pipes need at their peaks for the MFMA work issued per
                    utterance / wall time; algorithmic_frac from SURVEY 8(d)'s 676.6 MFLOP against the f32 matrix peak
                    (ceiling 232 k utt/s/GPU on that pipe);
-  ranks_seen / backend / allgather_us / per_rank_ms / slowest_rank / fastest_rank / scaling_efficiency_vs -- what
-                   torch.distributed reports, the HIP-event time of the embedding all-gather, every rank's own step time,
-                   N x the committed 1-GPU value for reference;
+  scaling_efficiency_vs -- N x the committed 1-GPU value for reference;
   cpu_baseline  -- the CPU oracle (NumPy/torch-CPU restatement of the reference, kind "port") timed in a
                    fresh child process on rank 0, N = 1 only: the per-utterance chain on single-threaded workers at
                    pool sizes around the container's CPU quota (`value` = the best; every worker warmed before the clock
                    starts; chain and pair-by-pair scoring timed separately), plus 1-core / all-core and batch-1 / batch-64
                    variants per stage;
   parity        -- the PRODUCTION path (libsvk end to end) vs the oracle on that sample: embeddings, scores, the EER on
-                   both sides (eer_equal) + the EER of the 4 874 x 40 matrix through host sklearn, svk_roc_eer and the oracle.
-Rank 0 also writes one JSON line to STDERR, just before the result line: the side benches (host_fed, micro_batch_breakdown,
-frontend_A, cosine_mfma, stage_kernels, ingest_resample, ragged -- the other hand-written kernels / workloads on their own)
-and `notes`, the prose that explains the result's fields, keyed by their path in it ("roofline.note").
+                   both sides (eer_equal) + the EER of the 4 874 x 40 matrix through the oracle.
+The rooflines come from HIP events the timed steps record either way, plus one untimed VAD pass; cpu_baseline, parity and the
+side benches run after the timed steps, on their own (about 25 s at N = 1).  With --full rank 0 also writes
+one JSON line to STDERR, just before the result line: the side benches (host_fed, micro_batch_breakdown, frontend_A,
+cosine_mfma, stage_kernels, ingest_resample, ragged -- the other hand-written kernels / workloads on their own) and `notes`,
+the prose that explains the result's fields, keyed by their path in it ("roofline.note").
 
 --dump-outputs DIR writes what the timed path computed in its last step (float32 .npy): scores.npy, the 4 874 x 40 score
 matrix, and embeddings.npy, the [clips, 128] embeddings, or a fixed sample of 65 536 of them for a larger corpus.
@@ -112,7 +116,12 @@ def parse(argv=None):
                          "peak).  Measured on one box: 4 096 -> 402 k utt/s, 16 384 -> 412 k, 32 768 -> 419 k; another: 32 768 -> "
                          "415.6 k, 74 321 -> 421.8 k -- every launch of a persistent kernel drains and refills the chip; the "
                          "embeddings do not depend on the batching, bit for bit (tools/check_micro_batch.py)")
-    ap.add_argument("--cpu-sample", type=int, default=2048, help="clips of the CPU-oracle baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the roofline rows and the EER of the timed steps, the committed 1-GPU "
+                         "value for reference, and with N = 1 the side benches, the CPU-oracle baseline and parity (each "
+                         "timed on its own after the timed steps; --no-extras / --parity-only / --cpu-sample narrow it).  "
+                         "Without it a run sets up, warms up, times the steps, dumps and prints the result line")
+    ap.add_argument("--cpu-sample", type=int, default=2048, help="with --full: clips of the CPU-oracle baseline (0 = skip)")
     ap.add_argument("--no-vad", action="store_true")
     ap.add_argument("--no-cmvn", action="store_true")
     ap.add_argument("--no-preemph", action="store_true")
@@ -120,9 +129,11 @@ def parse(argv=None):
                     help="seeded random-init C3D2 with calibrated BatchNorm (rounds 1-3) instead of the committed trained checkpoint")
     ap.add_argument("--checkpoint", default=os.path.join(REPO, "speaker_verification_amd", "checkpoints", "c3d2_synth.pt"),
                     help="{'state_dict': ...} of a C3D2 (reference format, model.py:177-186); loaded weights-only")
-    ap.add_argument("--no-extras", action="store_true", help="skip the per-kernel side benches (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the side benches, the CPU-oracle baseline and parity (a run without --full has none)")
     ap.add_argument("--parity-only", action="store_true",
-                    help="of the extras, only the CPU-oracle leg: cpu_baseline + parity (EER on both sides) on --cpu-sample clips")
+                    help="with --full: of the extras, only the CPU-oracle leg: cpu_baseline + parity (EER on both sides) on "
+                         "--cpu-sample clips")
     ap.add_argument("--frontend-only", action="store_true", help="time BASELINE config 2 only (for rocprof)")
     ap.add_argument("--stages-only", action="store_true", help="time the stage-level kernels only (for rocprof)")
     ap.add_argument("--ragged-only", action="store_true", help="the realistic-length workload only (4 .. 145 s clips)")
@@ -140,6 +151,8 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.parity_only and not args.full:
+        ap.error("--parity-only narrows --full: give both")
     return args
 
 
@@ -1038,7 +1051,6 @@ def main():
         dist.all_gather(every, mine)                       # each rank's own wall time of the K steps ...
         per_rank_ms = [float(t.item()) / args.steps * 1e3 for t in every]
         dt = max(float(t.item()) for t in every)           # ... and the max over ranks is the job's
-    bad = int(pipe.bad_clips.item())
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, full, scores)
 
@@ -1046,6 +1058,35 @@ def main():
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         value = n_total * args.steps / dt
+        result = {
+            "metric": "utterances/sec (MFCC->embed->cosine)", "value": value, "unit": "utterances/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            # f32 in, f32 out, f32 accumulation everywhere; the first two blocks' PRODUCTS are three f16 piece products per f32 product
+            # (22-bit operands: 1e-6 of the activation scale from the f32 kernel it replaces, parity bars unchanged)
+            "dtype": "f32 (conv1_1 .. conv4_1: two-piece f16 products, f32 accumulation)",
+            "data": "synthetic (seeded formant 'voices', 3 s / 16 kHz int16, generated on device); C3D2 weights: %s"
+                    % ("seeded random init" if args.random_init else
+                       "the committed checkpoint trained on synthetic speakers disjoint from the corpus's (tools/train_synth_checkpoint.py)"),
+            "weights": weights_meta,
+            "config": {"workload": "configs[4]: %d-clip corpus over %d rank(s) (%d clips on rank 0): energy-VAD -> pre-emph + "
+                                   "lmfe(25ms/10ms/1024/40) -> CMVN -> 20x80x40 cube -> C3D2(f32) -> all-gather -> "
+                                   "%dx%d cosine" % (n_total, world, n_local, n_test, len(ids)),
+                       "corpus_clips": n_total, "clips_per_rank": n_local, "micro_batch": spans[0][1] - spans[0][0],
+                       "vad": pipe.use_vad, "cmvn": pipe.normalize, "preemph": not args.no_preemph,
+                       "parallelism": "dp%d" % world, "crop_rng": "device"},
+            "ranks_seen": dist.get_world_size() if use_dist else 1,
+            "backend": ("rccl (torch 'nccl')" if args.backend == "nccl" else "gloo") if use_dist else None,
+            "allgather_us": float(np.median([a.elapsed_time(b) for a, b in ag_events])) * 1e3 if use_dist else None,
+            "allgather_bytes_per_rank": svdist.shard_rows(n_total, world) * 128 * 4,
+            "per_rank_ms": per_rank_ms,
+            "slowest_rank": int(np.argmax(per_rank_ms)), "fastest_rank": int(np.argmin(per_rank_ms)),
+            # what shaped RCCL's choice of algorithm / transport, when the caller set any of it (NCCL_DEBUG=INFO prints the
+            # ring / tree and the xGMI links picked to each rank's stderr file in the launcher's RANK_LOG_DIR)
+            "rccl_env": {k: v for k, v in os.environ.items()
+                         if k.startswith(("NCCL_", "RCCL_")) or k in ("HSA_ENABLE_IPC_MODE_LEGACY", "HIP_VISIBLE_DEVICES")},
+        }
+    if rank == 0 and args.full:
         # roofline of the fused front-end kernel: HIP events on the launch stream around each launch of the
         # timed region; algorithmic bytes of the launches as they ran (clips shortened by the VAD): kept
         # samples x 2 B read + produced frames x 40 x 4 B written, counted in one extra untimed VAD pass
@@ -1160,35 +1201,10 @@ def main():
                 "this_run": pmc_provenance("")[1]})
             stage2_roofline = network_rows.get("stage2")
             network_rows["_covered_share_of_step"] = covered_ms / args.steps / ms_per_step
-        result = {
-            "metric": "utterances/sec (MFCC->embed->cosine)", "value": value, "unit": "utterances/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            # f32 in, f32 out, f32 accumulation everywhere; the first two blocks' PRODUCTS are three f16 piece products per f32 product
-            # (22-bit operands: 1e-6 of the activation scale from the f32 kernel it replaces, parity bars unchanged)
-            "dtype": "f32 (conv1_1 .. conv4_1: two-piece f16 products, f32 accumulation)",
-            "data": "synthetic (seeded formant 'voices', 3 s / 16 kHz int16, generated on device); C3D2 weights: %s"
-                    % ("seeded random init" if args.random_init else
-                       "the committed checkpoint trained on synthetic speakers disjoint from the corpus's (tools/train_synth_checkpoint.py)"),
-            "weights": weights_meta,
-            "config": {"workload": "configs[4]: %d-clip corpus over %d rank(s) (%d clips on rank 0): energy-VAD -> pre-emph + "
-                                   "lmfe(25ms/10ms/1024/40) -> CMVN -> 20x80x40 cube -> C3D2(f32) -> all-gather -> "
-                                   "%dx%d cosine" % (n_total, world, n_local, n_test, len(ids)),
-                       "corpus_clips": n_total, "clips_per_rank": n_local, "micro_batch": spans[0][1] - spans[0][0],
-                       "vad": pipe.use_vad, "cmvn": pipe.normalize, "preemph": not args.no_preemph,
-                       "parallelism": "dp%d" % world, "crop_rng": "device"},
-            "ranks_seen": dist.get_world_size() if use_dist else 1,
-            "backend": ("rccl (torch 'nccl')" if args.backend == "nccl" else "gloo") if use_dist else None,
-            "allgather_us": float(np.median([a.elapsed_time(b) for a, b in ag_events])) * 1e3 if use_dist else None,
-            "allgather_bytes_per_rank": svdist.shard_rows(n_total, world) * 128 * 4,
-            "per_rank_ms": per_rank_ms,
-            "slowest_rank": int(np.argmax(per_rank_ms)), "fastest_rank": int(np.argmin(per_rank_ms)),
+        bad = int(pipe.bad_clips.item())
+        result.update({
             # what N GPUs would do at the committed 1-GPU rate (the driver computes the efficiency from its own per-N runs)
             "scaling_efficiency_vs": committed_one_gpu_value(world),
-            # what shaped RCCL's choice of algorithm / transport, when the caller set any of it (NCCL_DEBUG=INFO prints the
-            # ring / tree and the xGMI links picked to each rank's stderr file under gpurun_out/bench_ranks/)
-            "rccl_env": {k: v for k, v in os.environ.items()
-                         if k.startswith(("NCCL_", "RCCL_")) or k in ("HSA_ENABLE_IPC_MODE_LEGACY", "HIP_VISIBLE_DEVICES")},
             "rccl_expectation_us": {"direct_one_shot": 62, "ring": 435,
                                     "note": "SURVEY section 5, 9.5 MB per rank at 8 ranks over 153 GB/s xGMI links"},
             "roofline": main_roofline,
@@ -1217,9 +1233,9 @@ def main():
                              "C3D2 trained on 100 synthetic speakers that are not in the corpus (speaker_verification_amd/checkpoints/"
                              "c3d2_synth.json): the 40 test speakers are unseen, the EER is an operating point on a steep ROC")
                             + ".  Host sklearn path = svk_roc_eer = CPU oracle on the same scores; GPU = CPU EER from PCM on the parity sample"},
-        }
+        })
 
-    if rank == 0 and world == 1 and not args.no_extras and not args.parity_only:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and not args.parity_only:
         # the side entries keep round 4's 4 096-clip launch sequences (their numbers stay comparable, and a host-fed run of
         # 8 x 74 321 clips would copy the whole corpus to the host four times)
         pipe.micro_batch = min(pipe.micro_batch, 4096)
@@ -1260,7 +1276,7 @@ def main():
         mb = result["micro_batch_breakdown"]["stages"]
         result["ragged"]["fixed_3s_front_end_share_for_comparison"] = float(
             sum(v["share"] for k, v in mb.items() if not k.startswith(("cube", "cosine"))))
-    if rank == 0 and world == 1 and (not args.no_extras or args.parity_only):
+    if rank == 0 and world == 1 and args.full and (not args.no_extras or args.parity_only):
         if args.cpu_sample > 0:
             # sample: whole speakers from the start of the corpus (the last utterance of each enrols, Q17)
             ns = min(args.cpu_sample, n_local)
@@ -1311,8 +1327,9 @@ def main():
                 "variants": rec["stages"], "child_wall_s": rec["wall_s"]}
     if rank == 0:
         line, detail = split_record(result)
-        sys.stderr.write(json.dumps(detail) + "\n")
-        sys.stderr.flush()
+        if args.full:
+            sys.stderr.write(json.dumps(detail) + "\n")
+            sys.stderr.flush()
         print(json.dumps(line))
     if use_dist:
         dist.barrier()

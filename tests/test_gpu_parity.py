@@ -1980,7 +1980,7 @@ def test_bench_two_ranks_share_one_gpu(tmp_path):
     code the 8-GPU run executes): contiguous shards, padded gather, every rank scores, rank 0 reports.  The sharded
     run must report two ranks and give the SAME scores-derived numbers as the one-rank run, and --dump-outputs must
     hand back the same arrays from both."""
-    common = ["--corpus", "5001", "--micro-batch", "1024", "--steps", "1", "--warmup", "1", "--no-extras"]
+    common = ["--corpus", "5001", "--micro-batch", "1024", "--steps", "1", "--warmup", "1", "--full", "--no-extras"]
     two = _bench_line(["--gpus", "2", "--backend", "gloo", "--dump-outputs", str(tmp_path / "two")] + common)
     one = _bench_line(["--dump-outputs", str(tmp_path / "one")] + common)
     for name, shape in (("embeddings", (5001, 128)), ("scores", (4874, 40))):
@@ -2030,11 +2030,28 @@ def test_bench_two_ranks_share_one_gpu(tmp_path):
         assert rec["roofline_frontend"]["bound"] == "hbm" and rec["roofline_e2e"]["bound"] == "mfma"
 
 
+def test_bench_plain_run_is_the_headline(tmp_path):
+    """Without --full the bench times the same steps and hands back the same arrays, but its line carries the headline and
+    the configuration only: no EER, no roofline rows, none of the side benches or the CPU-oracle leg."""
+    common = ["--corpus", "5001", "--micro-batch", "1024", "--steps", "1", "--warmup", "1"]
+    plain = _bench_line(["--dump-outputs", str(tmp_path / "plain")] + common)
+    full = _bench_line(["--dump-outputs", str(tmp_path / "full"), "--full", "--no-extras"] + common)
+    for name in ("embeddings", "scores"):
+        assert np.array_equal(np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy"))), name
+    assert plain["metric"] == full["metric"] and plain["unit"] == full["unit"] and plain["dtype"] == full["dtype"]
+    assert plain["higher_is_better"] is True and plain["value"] == pytest.approx(5001 / (plain["ms_per_step"] * 1e-3), rel=1e-6)
+    assert plain["config"] == full["config"] and plain["steps"] == 1 and plain["warmup"] == 1
+    moved = {"eer", "roofline", "roofline_frontend", "roofline_stage2", "roofline_network", "roofline_e2e", "scaling_efficiency_vs",
+             "rccl_expectation_us", "parity", "cpu_baseline"}
+    assert not moved & set(plain) and moved - {"parity", "cpu_baseline"} <= set(full)
+    assert set(plain) == set(full) - moved
+
+
 def test_bench_four_ranks_uneven_shards_on_one_gpu():
     """BASELINE config 5's shape in small: 20 003 clips over FOUR ranks (shards of 5 001, 5 001, 5 001, 5 000: the last one
     short, the gather padded) on this one GPU through gloo -- the same embeddings, hence the same EER / AUC to the last
     digit, as one rank over the whole corpus."""
-    common = ["--corpus", "20003", "--micro-batch", "2048", "--steps", "1", "--warmup", "0", "--no-extras"]
+    common = ["--corpus", "20003", "--micro-batch", "2048", "--steps", "1", "--warmup", "0", "--full", "--no-extras"]
     four = _bench_line(["--gpus", "4", "--backend", "gloo"] + common, timeout=1200)
     one = _bench_line(common)
     assert four["ranks_seen"] == 4 and four["n_gpus"] == 4 and four["config"]["clips_per_rank"] == 5001
@@ -2058,7 +2075,7 @@ def test_bench_under_torch_distributed_run():
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    common = ["--corpus", "5001", "--micro-batch", "1024", "--steps", "1", "--warmup", "0", "--no-extras"]
+    common = ["--corpus", "5001", "--micro-batch", "1024", "--steps", "1", "--warmup", "0", "--full", "--no-extras"]
     proc = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                            "127.0.0.1", "--master-port", str(port), os.path.join(repo, "bench.py"), "--gpus", "2", "--backend", "gloo"]
                           + common, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
@@ -2075,7 +2092,7 @@ def test_bench_parity_leg_at_the_trained_operating_point():
     """bench.py's CPU-oracle leg (cpu_baseline + parity) on the first 492 clips (four speakers) of a 5 001-clip corpus with
     the committed trained checkpoint: the production path's embeddings against the oracle's from the same PCM, and the EER
     on both sides -- equal, at an operating point where the ROC is steep (not the diagonal of a random-init network)."""
-    rec = _bench_line(["--corpus", "5001", "--micro-batch", "1024", "--steps", "1", "--warmup", "0", "--parity-only",
+    rec = _bench_line(["--corpus", "5001", "--micro-batch", "1024", "--steps", "1", "--warmup", "0", "--full", "--parity-only",
                        "--cpu-sample", "492"], timeout=1200)
     par, base = rec["parity"], rec["cpu_baseline"]
     assert par["sample_clips"] == 492 and par["embed_max_abs_diff"] <= 5e-5 * par["embed_scale"]

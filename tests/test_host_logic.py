@@ -491,6 +491,15 @@ def test_bench_result_line_and_detail_record():
     assert rebuilt == rec
 
 
+def test_bench_full_is_opt_in():
+    """A plain run is the headline alone; --full adds the rest, and the options that narrow --full ask for it."""
+    import bench
+    assert not bench.parse([]).full and bench.parse(["--full"]).full
+    assert bench.parse(["--full", "--parity-only"]).parity_only and bench.parse(["--no-extras"]).no_extras
+    with pytest.raises(SystemExit):
+        bench.parse(["--parity-only"])
+
+
 def test_bench_dump_outputs(tmp_path):
     """--dump-outputs: float32 .npy files of what the timed step returned, at most 64 MB; a corpus larger than
     DUMP_MAX_ROWS is sampled with a fixed seed, the same rows every run."""

@@ -15,7 +15,7 @@ cd /tmp && export TMPDIR=/tmp
 # roofline row `stale` when the committed counters come from other sources than the ones it runs)
 python3 -c "import sys, json; sys.path.insert(0, '$root'); from speaker_verification_amd import _lib; print(json.dumps(_lib.provenance()))" > $out/prof_provenance.json
 echo "[1/6] kernel trace + stats of the end-to-end bench"
-rp --kernel-trace --stats --output-format csv -d $out/prof_bench -- python3 $root/bench.py --steps 3 --warmup 1 --no-extras > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err
+rp --kernel-trace --stats --output-format csv -d $out/prof_bench -- python3 $root/bench.py --steps 3 --warmup 1 --full --no-extras > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err
 echo "[2/6] HBM read / write counters"
 rp --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python3 $root/bench.py --frontend-only > $out/pmc_fetch.log 2>&1
 rp --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- python3 $root/bench.py --frontend-only > $out/pmc_write.log 2>&1
@@ -32,7 +32,7 @@ cd /tmp
 echo "[5b] the reference's file-driven entry points (create_speaker_models() + evaluate()) under the kernel trace"
 rp --kernel-trace --stats --output-format csv -d $out/prof_evaluate -- python3 $root/tools/profile_evaluate.py > $out/prof_evaluate.log 2>&1
 echo "[6/6] the bench itself + the stage-level kernels"
-python3 $root/bench.py --steps 3 --warmup 1 > $out/bench_final.json 2> $out/bench_final.err
+python3 $root/bench.py --steps 3 --warmup 1 --full > $out/bench_final.json 2> $out/bench_final.err
 python3 $root/bench.py --stages-only > $out/stages_final.json 2> $out/stages_final.err
 python3 $root/tools/prune_prof.py $out      # per-dispatch traces and other libraries' counter rows do not travel back
 echo done
