@@ -234,6 +234,34 @@ __device__ __forceinline__ float max_with_lane_xor1(float x) {
   return d;
 }
 
+// conv1_1's K order.  A B fragment is four patch words, each the (h, l) pair of one tap's value as the conversion leaves it
+// (low half h, high half l): K = 8 kk + 2 e + {0: h, 1: l}, so the A operand is [H_t | H_t] x 4 and [L_t | 0] x 4 -- the three
+// piece products of the 15 taps in two MFMAs, as before, but a lane reads four words where the [h | h | l | l] order read eight
+// and sorted their halves with four v_perm_b32.  The taps (kd, kw), t = 5 kd + kw, are cut into dominoes that ONE read
+// instruction can fetch for every lane: words 0, 1 of a lane = a vertical pair (kd, kw), (kd + 1, kw), one depth = 640 words
+// apart (ds_read2st64_b32); words 2, 3 = a horizontal pair (kd, kw), (kd, kw + 1) with kw in {0, 3}, adjacent words in a row
+// [c0 c1 c2 - | c3 c4 c5 -] for both column parities:
+//   kk = 0: (0-1, 1), (2; 0-1)    kk = 1: (0-1, 2), (0; 3-4)    kk = 2: (0-1, 0), (1; 3-4)    kk = 3: (1-2, 2), (2; 3-4)
+// Tap (1, 2) lies in two dominoes; kk = 3's copy takes tap 15's zero weight.
+constexpr unsigned long long CONV11_TAPS = 0xedcf98504372ba61ull;   // t of word e of lane group kk: 4 bits at 4 (4 kk + e)
+__device__ __forceinline__ int conv11_tap(int kk, int e) { return (int)(CONV11_TAPS >> (4 * (4 * kk + e))) & 15; }
+// the word offset of word e of lane group kk (e = 0: its vertical pair, e = 2: its horizontal pair) from pixel (dd, r, c)'s row
+__device__ __forceinline__ int conv11_word(int kk, int e, int c) {
+  const int t = conv11_tap(kk, e), kd = t == 15 ? 1 : t / 5, col = c + (t == 15 ? 2 : t % 5);
+  return kd * (NFRAME * WPW) + col + (col >= 3 ? 1 : 0);
+}
+// A = [H_t | H_t], [L_t | 0] for the four taps of lane (i, kk), gathered from a d_w1blk block in svk.h's order: element (lane
+// co + 16 (t >> 3), e = t & 7) is tap t of output channel co, H in the block's first 64 lanes, L in its second (t = 15 is 0)
+__device__ __forceinline__ void conv11_weights(const unsigned short* blk, int i, int kk, u32x4& WH, u32x4& WL) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int t = conv11_tap(kk, e), x = (i + 16 * (t >> 3)) * 8 + (t & 7);
+    const unsigned h = blk[x], l = blk[64 * 8 + x];
+    WH[e] = h | (h << 16);
+    WL[e] = l;
+  }
+}
+
 // The three-channel first block (svk_c3d2_stage1_c3; utils.FeatureCube3C, model.py:110 with num_channels = 3) is the same kernel
 // with NCH = 3: feature rows [n][3][max_frames][40], conv1_1's K = 45 taps as three K = 32 blocks [h | l] of one channel's 15 taps
 // + a zero tap each (six MFMAs per tile instead of two), the accumulators of a wave's 13 tiles kept in registers across the three
@@ -257,7 +285,10 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
     W2[pr][0] = p.w2blk[(2 * pr) * 64 + lane];
     W2[pr][1] = p.w2blk[(2 * pr + 1) * 64 + lane];
   }
-  const u32x4 W1a = p.w1blk[lane], W1b = p.w1blk[64 + lane];
+  u32x4 W1a, W1b;   // NCH = 1: conv1_1's A operand, held across the item loop (NCH = 3 gathers its three per item)
+  if constexpr (NCH == 1) conv11_weights(reinterpret_cast<const unsigned short*>(p.w1blk), i, kk, W1a, W1b);
+  // the lane's vertical and horizontal pair, as patch-word offsets from its pixel's row (pixel 16 tt + i of tile tt: row 8 tt + (i >> 1))
+  const int pov = (8 * wave + (i >> 1)) * WPW + conv11_word(kk, 0, i & 1), poh = (8 * wave + (i >> 1)) * WPW + conv11_word(kk, 2, i & 1);
   f32x4 b1v, sl1v, b2v, sl2v;   // a lane holds channels 4 kk .. 4 kk + 3 of ONE position (A = the weights)
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -339,37 +370,27 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
 
     // ---- (1) conv1_1 + PReLU -> act1 as (h, l): 100 tiles of 16 pixels, tile tt = wave + 8 m ----
     if constexpr (NCH == 1) {
-      // B = [h taps 0-7 | h taps 8-15 | l taps 0-7 | l taps 8-15] by kk; tap t = (kd, kw) = (t / 5, t % 5), t = 15: the zero column
-      const unsigned* pw[8];
-      const unsigned* const pbase = reinterpret_cast<const unsigned*>(patch) + 8 * WPW * wave + (i >> 1) * WPW;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int t0 = e, t1 = 8 + e;                                  // kk & 1 = 0 / 1
-        const int o0 = (t0 / 5) * (NFRAME * WPW), c0 = t0 % 5;
-        const int o1 = t1 < 15 ? (t1 / 5) * (NFRAME * WPW) : 0, c1 = t1 < 15 ? t1 % 5 : 0;
-        const int colA = (i & 1) + c0, colB = (i & 1) + c1;
-        const int offA = o0 + colA + (colA >= 3 ? 1 : 0), offB = o1 + colB + (colB >= 3 ? 1 : 0);
-        pw[e] = pbase + ((kk & 1) ? offB : offA);
-      }
-      const unsigned sel = kk < 2 ? 0x05040100u : 0x07060302u;         // the h halves / the l halves of two words
+      // B = four patch words per lane, each a tap's (h, l) pair as it lies in the patch (K order: conv11_tap)
+      const unsigned* const pv = reinterpret_cast<const unsigned*>(patch) + pov;
+      const unsigned* const ph = reinterpret_cast<const unsigned*>(patch) + poh;
       // pixel 16 tt + i = (dd = tt / 10, r = 8 (tt % 10) + (i >> 1), col = i & 1): slot 8 tt + 2 (i >> 2) + (i & 1) of the plane
       // (quarter kk >> 1 [+ 2 for l], parity (i >> 1) & 1); the lane's four channels are bytes 8 (kk & 1) .. + 7 of the slot
       unsigned* const aw = act + 4 * ((((kk >> 1) * 2 + ((i >> 1) & 1)) * HPLANE) + 8 * wave + 2 * (i >> 2) + (i & 1)) + 2 * (kk & 1);
       auto tile_group = [&](auto nt_tag, int m0) {
         constexpr int NT = decltype(nt_tag)::value;
-        unsigned w[NT][8];
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) w[t][e] = pw[e][64 * WPW * (m0 + t)];
-        f32x4 acc[NT];
         u32x4 B[NT];
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-#pragma unroll
-          for (int jx = 0; jx < 4; ++jx) B[t][jx] = __builtin_amdgcn_perm(w[t][2 * jx + 1], w[t][2 * jx], sel);
-          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W1a), __builtin_bit_cast(f16x8, B[t]), b1v, 0, 0, 0);
+          const int o = 64 * WPW * (m0 + t);
+          B[t] = (u32x4){pv[o], pv[o + NFRAME * WPW], ph[o], ph[o + 1]};
+          // (a fence per tile: without it the compiler pairs words of DIFFERENT tiles into one read2 and reassembles B with
+          // three v_mov_b32 per tile)
+          __builtin_amdgcn_sched_barrier(0);
         }
+        f32x4 acc[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W1a), __builtin_bit_cast(f16x8, B[t]), b1v, 0, 0, 0);
 #pragma unroll
         for (int t = 0; t < NT; ++t)
           acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W1b), __builtin_bit_cast(f16x8, B[t]), acc[t], 0, 0, 0);
@@ -395,38 +416,23 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
         for (int ch = 1; ch < NCH; ++ch)
           dma_patch_plane(p, cur, (int64_t)NCH * cur.u + ch, starts_cur, pair, lane, chan12 + (ch - 1) * WP_FLOATS);
       }
-      // the addresses of the one-channel kernel, as word offsets into a channel's patch
-      int po[8];
-      const int pbase = 8 * WPW * wave + (i >> 1) * WPW;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int t0 = e, t1 = 8 + e;
-        const int o0 = (t0 / 5) * (NFRAME * WPW), c0 = t0 % 5;
-        const int o1 = t1 < 15 ? (t1 / 5) * (NFRAME * WPW) : 0, c1 = t1 < 15 ? t1 % 5 : 0;
-        const int colA = (i & 1) + c0, colB = (i & 1) + c1;
-        const int offA = o0 + colA + (colA >= 3 ? 1 : 0), offB = o1 + colB + (colB >= 3 ? 1 : 0);
-        po[e] = pbase + ((kk & 1) ? offB : offA);
-      }
-      const unsigned sel = kk < 2 ? 0x05040100u : 0x07060302u;
       unsigned* const aw = act + 4 * ((((kk >> 1) * 2 + ((i >> 1) & 1)) * HPLANE) + 8 * wave + 2 * (i >> 2) + (i & 1)) + 2 * (kk & 1);
       f32x4 acc[13];   // tile wave + 8 m; m = 12 for waves 0 - 3 only
-      // one channel's K = 32 block [h | l] x [H | H], [L | 0] into the accumulators (the bias rides in with channel 0)
+      // one channel's K = 32 block (conv11_tap's order) into the accumulators (the bias rides in with channel 0)
       auto chan_pass = [&](auto first_tag, const unsigned* src, u32x4 WH, u32x4 WL) {
         auto group = [&](auto nt_tag, auto m0_tag) {
           constexpr int NT = decltype(nt_tag)::value, M0 = decltype(m0_tag)::value;
-          unsigned w[NT][8];
-#pragma unroll
-          for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) w[t][e] = src[po[e] + 64 * WPW * (M0 + t)];
           u32x4 B[NT];
 #pragma unroll
           for (int t = 0; t < NT; ++t) {
+            const int o = 64 * WPW * (M0 + t);   // the addresses of the one-channel kernel
+            B[t] = (u32x4){src[pov + o], src[pov + o + NFRAME * WPW], src[poh + o], src[poh + o + 1]};
+            __builtin_amdgcn_sched_barrier(0);
+          }
 #pragma unroll
-            for (int jx = 0; jx < 4; ++jx) B[t][jx] = __builtin_amdgcn_perm(w[t][2 * jx + 1], w[t][2 * jx], sel);
+          for (int t = 0; t < NT; ++t)
             acc[M0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, WH), __builtin_bit_cast(f16x8, B[t]),
                                                                  decltype(first_tag)::value ? b1v : acc[M0 + t], 0, 0, 0);
-          }
 #pragma unroll
           for (int t = 0; t < NT; ++t)
             acc[M0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, WL), __builtin_bit_cast(f16x8, B[t]), acc[M0 + t], 0, 0, 0);
@@ -439,12 +445,16 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
         group(std::integral_constant<int, 2>{}, std::integral_constant<int, 10>{});
         if (wave < 4) group(std::integral_constant<int, 1>{}, std::integral_constant<int, 12>{});
       };
-      // conv1_1's weight blocks are read per item (L1-resident, 48 B per lane per channel): held across the item loop as W1a / W1b
-      // are in the one-channel kernel, the six blocks and the 13 accumulators spill (256 VGPRs).  The opaque copy of the pointer
+      // conv1_1's weight blocks are gathered per item (L1-resident, 16 halves per lane per channel): held across the item loop as
+      // W1a / W1b are in the one-channel kernel, the six blocks and the 13 accumulators spill (256 VGPRs).  The opaque copy of the pointer
       // keeps the compiler from hoisting the loads out of the loop.
-      const u32x4* w1blk = p.w1blk;
+      const unsigned short* w1blk = reinterpret_cast<const unsigned short*>(p.w1blk);
       asm volatile("" : "+s"(w1blk));
-      chan_pass(std::true_type{}, reinterpret_cast<const unsigned*>(patch), w1blk[lane], w1blk[64 + lane]);
+      {
+        u32x4 WH, WL;
+        conv11_weights(w1blk, i, kk, WH, WL);
+        chan_pass(std::true_type{}, reinterpret_cast<const unsigned*>(patch), WH, WL);
+      }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of channels 1 and 2 have landed
       if (part == 0) {
 #pragma unroll
@@ -452,9 +462,11 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
       }
       __syncthreads();   // channels 1 and 2 are in place and converted
 #pragma unroll
-      for (int ch = 1; ch < NCH; ++ch)
-        chan_pass(std::false_type{}, reinterpret_cast<const unsigned*>(chan12 + (ch - 1) * WP_FLOATS), w1blk[2 * ch * 64 + lane],
-                  w1blk[(2 * ch + 1) * 64 + lane]);
+      for (int ch = 1; ch < NCH; ++ch) {
+        u32x4 WH, WL;
+        conv11_weights(w1blk + 2 * ch * 64 * 8, i, kk, WH, WL);
+        chan_pass(std::false_type{}, reinterpret_cast<const unsigned*>(chan12 + (ch - 1) * WP_FLOATS), WH, WL);
+      }
       __syncthreads();   // every wave has read channels 1 and 2: act1 may be written
 #pragma unroll
       for (int m = 0; m < 13; ++m) {
