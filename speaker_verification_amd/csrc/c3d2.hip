@@ -22,7 +22,8 @@
 //      converted in place to (h, l) half pairs by the waves that fetched it;
 //   2. conv1_1 as a GEMM [16 channels] x [K = 32: 15 taps + pad, h | l] x [16 pixels], + PReLU, split into (h, l), written to
 //      the act1 tile in LDS: 10 depths x 80 rows x 2 columns x 16 channels;
-//   3. conv1_2 as an implicit GEMM in the direct form, two taps per K = 32 block, the weights of all 27 taps in 112 VGPRs;
+//   3. conv1_2 as an implicit GEMM in the direct form, two taps per K = 32 block, the weights of all 27 taps in 112 VGPRs; a wave
+//      walks one set of 16 (row, column) positions along the depth and reads every fragment once for its three kd (depth chains);
 //   4. bias (in the accumulator), PReLU, max over the column pair (adjacent lanes: one DPP instruction), 16-byte stores.
 #include <climits>
 #include <vector>
@@ -269,7 +270,15 @@ __device__ __forceinline__ void conv11_weights(const unsigned short* blk, int i,
 // and 2 are fetched at the top of the item into the act1 tile, which is free until conv1_1's epilogue writes it, while channel 0
 // is multiplied.  conv1_2, the pool and the output layout are the one-channel kernel's.  (NCH = 1 is the code as it was: every
 // NCH = 3 step is under `if constexpr`.)
-template <bool SLOPE01, int NCH = 1>
+// conv1_2's depth chains (phase (2) of the kernel): CONV12_CHAIN output depths per chain; its units in issue order are the four
+// pair units of input depth s = 0 .. CONV12_CHAIN + 1 and, behind those of every s >= 2, pairs 12 and 13 of output s - 2
+constexpr int CONV12_CHAIN = 4, CONV12_UNITS = 4 * (CONV12_CHAIN + 2) + 2 * CONV12_CHAIN;
+constexpr int conv12_unit_step(int n) { return n < 8 ? n / 4 : 2 + (n - 8) / 6; }
+constexpr int conv12_unit_sub(int n) { return n < 8 ? n % 4 : (n - 8) % 6; }   // 0 .. 3: pair m of the step; 4, 5: pairs 12, 13
+static_assert(2 * CONV12_CHAIN == TD, "two chains cover an item's output depths");
+
+// (NCH = 3 keeps the tile loop: with 13 conv1_1 accumulators behind it the chain takes its spill from 6 to 16 VGPRs)
+template <bool SLOPE01, int NCH = 1, bool CONV12_CHAINS = (NCH == 1)>
 __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p) {
   extern __shared__ __attribute__((aligned(16))) float smem_c3d2[];
   unsigned* const act = reinterpret_cast<unsigned*>(smem_c3d2);   // [HACT_WORDS]
@@ -483,7 +492,7 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
     __syncthreads();   // act1 is complete; the patch buffer is free
     const int item3 = q_item3;
 
-    // ---- (2) conv1_2 + PReLU + pool: 36 tiles of 16 positions, position P = 16 t + i -> (depth P / 72, row, column) ----
+    // ---- (2) conv1_2 + PReLU + pool: 576 positions (depth, row, column) in tiles of 16 ----
     {
       if (part == 0 && next < n_items) {
         if constexpr (NCH == 1) {
@@ -496,12 +505,8 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
       }
       const int u = cur.u, q = cur.q(), j = cur.j();
       float* const obase = p.out + (int64_t)u * S_N + (TD * q) * S_D + j * S_W + 4 * kk;
-      // tiles t = wave + 8 m (m < 4); the last four go to the YOUNGER waves (the older ones fetch and convert the next patch)
-#pragma unroll 1
-      for (int m = 0; m < 4 + part; ++m) {
-        const int t = m < 4 ? wave + 8 * m : 28 + wave;
-        const int P = 16 * t + i;
-        const int dq = (P * 911) >> 16, rem = P - 72 * dq, row = rem >> 1;          // P / 72 for P < 576
+      // One stand-alone tile: 16 positions (dq, row, column i & 1), every fragment read by the tile itself (27 reads, 41 MFMAs)
+      auto tile = [&](int dq, int row) {
         // pixel (dd = dq + kd, r = 2 row + kh, col), channels 8 (kk & 1) .. + 7: slot (((kk & 1) * 2 + (kh & 1)) * 10 + dd) * 80 +
         // (row + kh / 2) * 2 + col of the h planes; the l planes 4 HPLANE slots on.  The taps of a pair (kd, 2 m), (kd, 2 m + 1)
         // differ by the parity plane; the pair (0, 8) | (1, 8) by one depth
@@ -542,6 +547,81 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[r] = max_with_lane_xor1(y[r]);
         if ((i & 1) == 0) *reinterpret_cast<f32x4*>(obase + dq * S_D + row * S_PAR) = o;
+      };
+      if constexpr (CONV12_CHAINS) {
+        // A DEPTH CHAIN: the fragment of pair (kd, m) of output (dq, row, col) is the act1 slot of (dq + kd, row + m, col) -- it
+        // depends on the input depth dq + kd alone, so a wave that keeps ONE set of 16 (row, col) positions over consecutive
+        // output depths reads the eight fragments (pairs m = 0 .. 3, h and l) of an input depth ONCE and multiplies them into
+        // three live accumulators: kd = 0 of output dd, kd = 1 of dd - 1, kd = 2 of dd - 2.  An output whose kd = 2 step is done
+        // takes pairs 12 and 13 (three reads of its own) and leaves through the epilogue.  Every output receives its 41 MFMAs
+        // in the stand-alone tile's order (kd-major, pairs 0 - 3 inside a kd, then 12, 13) with the same operands: bit-identical.
+        // Eight chains of four output depths, one per wave: rows 8 pt .. 8 pt + 7 (pt = wave & 3) x depth half (wave >> 2), six
+        // input depths, 6 x 8 + 4 x 3 = 60 reads for 164 MFMAs.  Rows 32 - 35 (64 positions) are four stand-alone tiles of two
+        // depths each on the YOUNGER waves (the older ones fetch and convert the next patch): 588 reads per item, not 972.
+        {
+          const int row = 8 * pair + (i >> 1), d0 = 4 * part;
+          const int base = 16 * (((kk & 1) * 2) * HPLANE + d0 * 80 + 2 * row + (i & 1));
+          const char* const a2 = reinterpret_cast<const char*>(act) + base + (kk >= 2 ? 16 * HPLANE : 0);
+          const char* const a3 = reinterpret_cast<const char*>(act) + base + (kk >= 2 ? 16 * 80 : 0);
+          const char* const a13 = a3 + (kk >= 2 ? 16 * 4 * HPLANE - 16 * 80 : 0);
+          // unit n of the chain's 32 (conv12_unit_step / _sub): the four pairs of input depth s, behind them (s >= 2) pairs 12
+          // and 13 of output s - 2.  Fragments TWO units ahead, three rotating sets, as in the stand-alone tile
+          auto rd = [&](int n, int piece) -> u32x4 {
+            const int s = conv12_unit_step(n), e = conv12_unit_sub(n);
+            const char* ad = e < 4 ? a2 + 1280 * s + 32 * e : e == 4 ? a3 + 1280 * (s - 2) + 32 * 4 : a13 + 1280 * s + 32 * 4;
+            return *reinterpret_cast<const u32x4*>(ad + 16 * 4 * HPLANE * piece);
+          };
+          auto mfma3 = [&](f32x4 c, int pr, u32x4 h, u32x4 l) -> f32x4 {
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W2[pr][0]), __builtin_bit_cast(f16x8, h), c, 0, 0, 0);
+            if (pr < HPAIRS - 1)
+              c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W2[pr][0]), __builtin_bit_cast(f16x8, l), c, 0, 0, 0);
+            return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W2[pr][1]), __builtin_bit_cast(f16x8, h), c, 0, 0, 0);
+          };
+          f32x4 acc[CONV12_CHAIN];
+          u32x4 bh[3], bl[3];
+          bh[0] = rd(0, 0);
+          bl[0] = rd(0, 1);
+          bh[1] = rd(1, 0);
+          bl[1] = rd(1, 1);
+#pragma unroll
+          for (int n = 0; n < CONV12_UNITS; ++n) {
+            if (n + 2 < CONV12_UNITS) {
+              bh[(n + 2) % 3] = rd(n + 2, 0);
+              if (conv12_unit_sub(n + 2) != 5) bl[(n + 2) % 3] = rd(n + 2, 1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const int s = conv12_unit_step(n), e = conv12_unit_sub(n);
+            if (e < 4) {
+#pragma unroll
+              for (int kd = 0; kd < 3; ++kd) {
+                const int o = s - kd;
+                if (o >= 0 && o < CONV12_CHAIN) acc[o] = mfma3(kd == 0 && e == 0 ? b2v : acc[o], 4 * kd + e, bh[n % 3], bl[n % 3]);
+              }
+            } else {
+              const int o = s - 2;
+              acc[o] = mfma3(acc[o], 8 + e, bh[n % 3], bl[n % 3]);
+              if (e == 5) {
+                const f32x4 y = prelu4<SLOPE01>(acc[o], sl2v);
+                f32x4 v;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = max_with_lane_xor1(y[r]);
+                if ((i & 1) == 0) *reinterpret_cast<f32x4*>(obase + (d0 + o) * S_D + row * S_PAR) = v;
+              }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+        if (part) tile(2 * pair + (i >> 3), 32 + ((i >> 1) & 3));
+      } else {
+        // tiles t = wave + 8 m (m < 4) of positions P = 16 t + i -> (depth P / 72, row, column); the last four go to the YOUNGER
+        // waves (the older ones fetch and convert the next patch)
+#pragma unroll 1
+        for (int m = 0; m < 4 + part; ++m) {
+          const int t = m < 4 ? wave + 8 * m : 28 + wave;
+          const int P = 16 * t + i;
+          const int dq = (P * 911) >> 16, rem = P - 72 * dq;          // P / 72 for P < 576
+          tile(dq, rem >> 1);
+        }
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces have landed
@@ -768,10 +848,11 @@ __global__ __launch_bounds__(256, 2) void c3d2_conv21h_kernel(const Conv21hParam
 // tap (H x h, H x l, L x h), 24 taps.  Item = (cube, pooled column j, third q of the output depths) as before; its input
 // [6 d][36 h][2 w][32 c] is split while it is staged: eight planes (four channel quarters x {h, l}) of 16-byte slots, a plane
 // split by the parity of the row (rows are 2 apart along a tile): slot ((r & 1) * 6 + d) * 46 + (r >> 1) * 2 + col.  The item's
-// 4 d x 15 rows x 2 columns = 120 positions are 7.5 tiles of 16; wave = (N tile nt, every other tile): the 48 weight blocks of an
-// N tile are 192 VGPRs.  Pool = max over adjacent lanes (the column pair), the even lane stores four channels. ----
-// Depth pitch 46, not 36: a tile's positions run on from one depth's 30 to the next, and with 46 = 30 (mod 16) so do their slots mod 16
-// -- the sixteen lanes of an LDS lane group stay on sixteen different 16-byte bank groups in the three of 7.5 tiles that straddle depths
+// 4 d x 15 rows x 2 columns = 120 positions; wave = (N tile nt, plane tile: 16 of a depth's 30 positions) walks the four output depths
+// as a depth chain (below): the 48 weight blocks of an N tile are 192 VGPRs.  Pool = max over adjacent lanes (the column pair),
+// the even lane stores four channels. ----
+// Depth pitch 46, not 36, comes from the tiles of 16 consecutive positions that ran on from one depth's 30 to the next (46 = 30
+// (mod 16): their slots mod 16 ran on too); a plane tile's sixteen slots are consecutive at any pitch, and the layout is kept as it was
 constexpr int C22H_DP = 46;
 constexpr int C22H_PLANE = 560;                      // 2 * 6 * 46 = 552 slots per plane, padded to a multiple of 16
 constexpr int C22H_LDS_WORDS = 4 * 8 * C22H_PLANE;   // 71 680 bytes
@@ -853,41 +934,55 @@ __global__ __launch_bounds__(256, 2) void c3d2_conv22h_kernel(const Conv22hParam
     if (threadIdx.x == 0) q_next = p.queue ? (int)q_ticket + (int)gridDim.x : item + (int)gridDim.x;
     __syncthreads();
     const int item_next = q_next;
-    // tiles t = half, half + 2, ...: positions P = 16 t + i -> (depth P / 30, row (P % 30) / 2, column P & 1)
-#pragma unroll 1
-    for (int t = half; t < (C22H_POS + 15) / 16; t += 2) {
-      const int P = min(16 * t + i, C22H_POS - 1);
-      const int dq = (P * 2185) >> 16, r30 = P - 30 * dq, row = r30 >> 1;      // P / 30 for P < 120
-      // input pixel (dq + kd, 2 row + kh, col), channels 8 kk .. + 7: slot ((kh & 1) * 6 + dq + kd) * 46 + (row + kh / 2) * 2 + col of plane kk [l: + 4]
-      const char* const a2 = reinterpret_cast<const char*>(reg) + 16 * (kk * C22H_PLANE + dq * C22H_DP + 2 * row + (i & 1));
-      auto rd = [&](int tap, int piece) -> u32x4 {
-        const int kd = tap >> 3, kh = tap & 7;
-        return *reinterpret_cast<const u32x4*>(a2 + 16 * (((kh & 1) * 6 + kd) * C22H_DP + (kh >> 1) * 2) + 16 * 4 * C22H_PLANE * piece);
+    // A DEPTH CHAIN per wave (see c3d2_stage1h_kernel's conv1_2): the kernel is (3, 8, 1), so the fragment of tap (kd, kh) of output
+    // (dq, row, col) depends on the input depth dq + kd alone.  Wave = (N tile, plane tile `half`: positions 16 half + i of a
+    // depth's 30 = 15 rows x 2 columns; the last two lanes of tile 1 are clamped and store nothing) runs the item's four output
+    // depths over its six input depths: the sixteen fragments (kh = 0 .. 7, h and l) of an input depth are read ONCE and
+    // multiplied into three live accumulators -- taps 0 - 7 of output dd, 8 - 15 of dd - 1, 16 - 23 of dd - 2.  96 reads per wave
+    // where four tiles read 192; every output still receives taps 0 .. 23 in order with the same operands: bit-identical.
+    {
+      static_assert(C22H_POS == 4 * 2 * O2_H, "four output depths of 15 rows x 2 columns");
+      const int r30 = min(16 * half + i, 2 * O2_H - 1), row = r30 >> 1;
+      // input pixel (dd, 2 row + kh, col), channels 8 kk .. + 7: slot ((kh & 1) * 6 + dd) * 46 + (row + kh / 2) * 2 + col of plane kk [l: + 4]
+      const char* const a2 = reinterpret_cast<const char*>(reg) + 16 * (kk * C22H_PLANE + r30);
+      // unit n = 8 s + kh: fragments TWO units ahead (three rotating sets)
+      auto rd = [&](int n, int piece) -> u32x4 {
+        const int s = n >> 3, kh = n & 7;
+        return *reinterpret_cast<const u32x4*>(a2 + 16 * (((kh & 1) * 6 + s) * C22H_DP + (kh >> 1) * 2) + 16 * 4 * C22H_PLANE * piece);
       };
-      f32x4 acc = b4;
+      float* const obase = p.out + ((((int64_t)u * O2_D + 4 * q) * O2_H + row) * O2_W + j) * 32 + 16 * nt + 4 * kk;
+      f32x4 acc[4];
       u32x4 bh[3], bl[3];
       bh[0] = rd(0, 0);
       bl[0] = rd(0, 1);
       bh[1] = rd(1, 0);
       bl[1] = rd(1, 1);
 #pragma unroll
-      for (int tap = 0; tap < 24; ++tap) {
-        if (tap + 2 < 24) {
-          bh[(tap + 2) % 3] = rd(tap + 2, 0);
-          bl[(tap + 2) % 3] = rd(tap + 2, 1);
+      for (int n = 0; n < 48; ++n) {
+        if (n + 2 < 48) {
+          bh[(n + 2) % 3] = rd(n + 2, 0);
+          bl[(n + 2) % 3] = rd(n + 2, 1);
         }
         __builtin_amdgcn_sched_barrier(0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[tap][0]), __builtin_bit_cast(f16x8, bh[tap % 3]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[tap][0]), __builtin_bit_cast(f16x8, bl[tap % 3]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[tap][1]), __builtin_bit_cast(f16x8, bh[tap % 3]), acc, 0, 0, 0);
+        const int s = n >> 3, kh = n & 7;
+#pragma unroll
+        for (int kd = 0; kd < 3; ++kd) {
+          const int o = s - kd, tap = 8 * kd + kh;
+          if (o >= 0 && o < 4) {
+            acc[o] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[tap][0]), __builtin_bit_cast(f16x8, bh[n % 3]), tap == 0 ? b4 : acc[o], 0, 0, 0);
+            acc[o] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[tap][0]), __builtin_bit_cast(f16x8, bl[n % 3]), acc[o], 0, 0, 0);
+            acc[o] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[tap][1]), __builtin_bit_cast(f16x8, bh[n % 3]), acc[o], 0, 0, 0);
+          }
+        }
+        if (kh == 7 && s >= 2) {
+          const f32x4 y = prelu4<SLOPE01>(acc[s - 2], sl4);
+          f32x4 v;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = max_with_lane_xor1(y[r]);
+          if ((i & 1) == 0 && 16 * half + i < 2 * O2_H) *reinterpret_cast<f32x4*>(obase + (s - 2) * (O2_H * O2_W * 32)) = v;
+        }
         __builtin_amdgcn_sched_barrier(0);
       }
-      const f32x4 y = prelu4<SLOPE01>(acc, sl4);
-      f32x4 o;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o[r] = max_with_lane_xor1(y[r]);
-      if ((i & 1) == 0 && 16 * t + i < C22H_POS)
-        *reinterpret_cast<f32x4*>(p.out + ((((int64_t)u * O2_D + 4 * q + dq) * O2_H + row) * O2_W + j) * 32 + 16 * nt + 4 * kk) = o;
     }
     __syncthreads();
     item = item_next;
