@@ -2,9 +2,12 @@
 //   c3d2_stage1h_kernel   cube + conv1_1 + conv1_2 + pool1 on v_mfma_f32_16x16x32_f16 through two-piece f16 products (round 4)
 //   c3d2_conv21h_kernel   conv2_1, two-piece f16 products
 //   c3d2_conv22h_kernel   conv2_2 + pool2, two-piece f16 products
-//   c3d2_conv31h_kernel   conv3_1, two-piece f16 products; writes the chunked, column-major layout c3d2_tail_kernel<Conv32T> stages
-// (conv3_2, conv4_1, conv4_2 and FC5 live in c3d2_tail.hip.)  BatchNorm (eval mode) is folded into weights and biases by
-// the host (model.FusedEmbedder).  Work items come from device-wide counters.  What earlier rounds built and superseded is
+//   c3d2_conv31h_kernel   conv3_1, two-piece f16 products; writes the chunked, column-major layout c3d2_conv32h_kernel stages
+//   c3d2_conv32h_kernel   conv3_2, two-piece f16 products, K split over two waves per N tile
+//   c3d2_conv41h_kernel   conv4_1, two-piece f16 products; writes the chunked layout c3d2_conv42_kernel stages
+// (conv4_2 and FC5, on the f32 matrix pipe, are in c3d2_tail.hip; the leaf helpers of all of them in c3d2_common.h.)  BatchNorm
+// (eval mode) is folded into weights and biases by the host (model.FusedEmbedder).  Work items come from device-wide counters.
+// What earlier rounds built and superseded is
 // under tools/experiments/ with its measured numbers: the direct-form f32 kernels, the t-plane first block, the K-split conv3_2
 // (c3d2_superseded_r3.patch) and the f32 first and second blocks through the depth transform, round 4's 7.12 + 5.09 ms kernels
 // (stage1_f32_winograd.patch, stage2_f32_winograd.patch).
@@ -28,10 +31,8 @@
 #include <climits>
 #include <vector>
 
+#include "c3d2_common.h"
 #include "svk_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -56,8 +57,6 @@ struct ItemPos {
   }
 };
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 struct Stage1Params {
   const float* feat;
   const int32_t* crop;
@@ -72,14 +71,6 @@ struct Stage1Params {
   float* out;
   unsigned* queue;
 };
-
-__device__ __forceinline__ float prelu(float v, float slope) { return v > 0.f ? v : slope * v; }
-// 0 <= slope <= 1 (nn.PReLU starts at 0.25 and trained slopes stay there): prelu(v) = max(v, slope v), two
-// instructions instead of compare / multiply / select (+ a wait state); bit-identical for finite v.
-template <bool SLOPE01>
-__device__ __forceinline__ float prelu_t(float v, float slope) {
-  return SLOPE01 ? fmaxf(v, slope * v) : prelu(v, slope);
-}
 
 // a per-thread constant plus an immediate.
 // (a VECTOR load by lanes 0 .. 11, not twelve scalar loads: scalar loads return out of order, so while any is in
@@ -154,37 +145,6 @@ __device__ __forceinline__ void dma_patch_plane(const Stage1Params& p, ItemPos i
   dma_patch_w(q, it, starts_v, pair, lane, patch);
 }
 
-// prelu for 0 <= slope <= 1 straight off MFMA accumulators: fmaxf() on a value the compiler cannot prove canonical costs a
-// third instruction (v_max x, x in front of the real one) and the product is one v_mul per value; written as vectors it is one
-// v_pk_mul_f32 per PAIR + one v_max_f32 per value (12 -> 6 instructions per four values; the same product, the same
-// maximum: bit-identical for every finite and infinite input, NaN stays NaN).
-// (the product is left to the compiler -- it selects v_pk_mul_f32 for a two-float vector product and, unlike for an asm
-// statement, counts the wait states between an MFMA and the first instruction that reads its result; the v_max behind it
-// depends on that product, so it is issued later still)
-__device__ __forceinline__ f32x2 pk_mul(f32x2 a, f32x2 b) { return a * b; }
-__device__ __forceinline__ float max_raw(float a, float b) {
-  float d;
-  asm("v_max_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-  return d;
-}
-template <bool SLOPE01>
-__device__ __forceinline__ f32x4 prelu4(f32x4 v, f32x4 slope) {
-  f32x4 o;
-  if (SLOPE01) {
-    const f32x2 m0 = pk_mul(__builtin_shufflevector(v, v, 0, 1), __builtin_shufflevector(slope, slope, 0, 1));
-    const f32x2 m1 = pk_mul(__builtin_shufflevector(v, v, 2, 3), __builtin_shufflevector(slope, slope, 2, 3));
-    o[0] = max_raw(v[0], m0[0]);
-    o[1] = max_raw(v[1], m0[1]);
-    o[2] = max_raw(v[2], m1[0]);
-    o[3] = max_raw(v[3], m1[1]);
-  } else {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) o[r] = prelu(v[r], slope[r]);
-  }
-  return o;
-}
-
-
 // =====================================================================================================
 // The first block on the F16 matrix pipe through TWO-PIECE products (round 4, second half).  An f32 value x is carried as
 // the pair (h, l) of halves with h = f16(x), l = f16(x - h): 22 significant bits in the same four bytes, and
@@ -207,33 +167,9 @@ __device__ __forceinline__ f32x4 prelu4(f32x4 v, f32x4 slope) {
 //     remainder tiles, no exchange buffer.
 // Same boundary as svk_c3d2_stage1 (f32 feature rows + crop starts in, f32 pooled activation out).
 // =====================================================================================================
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int HACT_WORDS = 16 * DIN * NFRAME * 2;            // 25 600 32-bit words = 6 400 slots of 16 bytes
 constexpr int HPLANE = DIN * NFRAME;                         // slots per (quarter, row parity) plane: [10 dd][40 r / 2][2 col]
 constexpr int HPAIRS = 14;                                   // tap pairs of conv1_2 (27 taps + one empty)
-
-// (h, l) of two f32 values as two packed-half words: {h0, h1}, {l0, l1}
-__device__ __forceinline__ void split2(f32x2 v, unsigned& h, unsigned& l) {
-  const f16x2 hh = __builtin_convertvector(v, f16x2);
-  h = __builtin_bit_cast(unsigned, hh);
-  // l = f16(x - f32(h)) as ONE instruction per value: v_fma_mix reads h as a half and x as a float, multiplies by -1 and rounds the
-  // f32 result (exact: x - h has at most 13 significant bits) into one half of the destination -- where the compiler's own code is
-  // two v_cvt_f32_f16, a packed subtract and v_cvt_pk_f16_f32.  Bit-identical on 2^22 random pairs incl. denormals, NaN, infinities.
-  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(h), "v"(v[0]));
-  asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l) : "v"(h), "v"(v[1]));
-}
-
-// max(x, x of lane ^ 1) as ONE instruction (DPP quad_perm [1, 0, 3, 2] on the first source).  Written out: four calls of
-// __builtin_amdgcn_mov_dpp on the four registers of an accumulator came back as one v_mov_b32_dpp of the first (ROCm 7.2).
-// (the s_nop: a DPP read of a register the previous vector instruction wrote needs two wait states, and the compiler does not
-// count them for asm statements)
-__device__ __forceinline__ float max_with_lane_xor1(float x) {
-  float d;
-  asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=v"(d) : "v"(x));
-  return d;
-}
 
 // conv1_1's K order.  A B fragment is four patch words, each the (h, l) pair of one tap's value as the conversion leaves it
 // (low half h, high half l): K = 8 kk + 2 e + {0: h, 1: l}, so the A operand is [H_t | H_t] x 4 and [L_t | 0] x 4 -- the three
@@ -745,20 +681,10 @@ __global__ __launch_bounds__(256, 2) void c3d2_conv21h_kernel(const Conv21hParam
   const int i = lane & 15, kk = lane >> 4;
   u32x4 W[2][6][2];
 #pragma unroll
-  for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-    for (int pr = 0; pr < 6; ++pr) {
-      W[nt][pr][0] = p.wblk[((nt * 6 + pr) * 2) * 64 + lane];
-      W[nt][pr][1] = p.wblk[((nt * 6 + pr) * 2 + 1) * 64 + lane];
-    }
+  for (int nt = 0; nt < 2; ++nt) load_wblk(p.wblk, nt * 6, lane, W[nt]);
   f32x4 b4[2], sl4[2];   // a lane holds channels 16 nt + 4 kk .. + 3 of ONE position
 #pragma unroll
-  for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      b4[nt][r] = p.bias[16 * nt + 4 * kk + r];
-      sl4[nt][r] = p.slope[16 * nt + 4 * kk + r];
-    }
+  for (int nt = 0; nt < 2; ++nt) load_bias_slope(p.bias, p.slope, nt, kk, b4[nt], sl4[nt]);
   constexpr int BLOCKS = S2_H / 4;   // 9 row blocks per cube
   const int n_items = p.n_utt * BLOCKS;
   __shared__ int q_next;   // dynamic work items (two workgroups share a CU)
@@ -790,13 +716,7 @@ __global__ __launch_bounds__(256, 2) void c3d2_conv21h_kernel(const Conv21hParam
           sv[k - r0] = *reinterpret_cast<const f32x4*>(g);
         }
 #pragma unroll
-        for (int k = r0; k < r0 + NV; ++k) {
-          unsigned h0, l0, h1, l1;
-          split2(__builtin_shufflevector(sv[k - r0], sv[k - r0], 0, 1), h0, l0);
-          split2(__builtin_shufflevector(sv[k - r0], sv[k - r0], 2, 3), h1, l1);
-          *reinterpret_cast<u32x2*>(a0s + 4 * 64 * k) = (u32x2){h0, h1};
-          *reinterpret_cast<u32x2*>(a0s + 4 * 64 * k + 4 * 2 * C21H_PIX) = (u32x2){l0, l1};
-        }
+        for (int k = r0; k < r0 + NV; ++k) park_pieces(a0s + 4 * 64 * k, 4 * 2 * C21H_PIX, sv[k - r0], true);
       }
     }
     if (threadIdx.x == 0) q_next = p.queue ? (int)q_ticket + (int)gridDim.x : item + (int)gridDim.x;
@@ -876,17 +796,9 @@ __global__ __launch_bounds__(256, 2) void c3d2_conv22h_kernel(const Conv22hParam
   const int i = lane & 15, kk = lane >> 4;
   const int nt = wave & 1, half = wave >> 1;
   u32x4 W[24][2];
-#pragma unroll
-  for (int t = 0; t < 24; ++t) {
-    W[t][0] = p.wblk[((nt * 24 + t) * 2) * 64 + lane];
-    W[t][1] = p.wblk[((nt * 24 + t) * 2 + 1) * 64 + lane];
-  }
+  load_wblk(p.wblk, nt * 24, lane, W);
   f32x4 b4, sl4;   // channels 16 nt + 4 kk .. + 3 of ONE position
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    b4[r] = p.bias[16 * nt + 4 * kk + r];
-    sl4[r] = p.slope[16 * nt + 4 * kk + r];
-  }
+  load_bias_slope(p.bias, p.slope, nt, kk, b4, sl4);
   constexpr int PER_CUBE = O2_W * (O2_D / 4);   // 7 x 3 items
   const int n_items = p.n_utt * PER_CUBE;
   __shared__ int q_next;
@@ -921,13 +833,7 @@ __global__ __launch_bounds__(256, 2) void c3d2_conv22h_kernel(const Conv22hParam
           }
           const int slot = ((hh & 1) * 6 + d) * C22H_DP + (hh >> 1) * 2 + wq;
           unsigned* const dst = reg + 4 * ((piece >> 1) * C22H_PLANE + slot) + 2 * (piece & 1);
-          unsigned h0, l0, h1, l1;
-          split2(__builtin_shufflevector(sv[k - r0], sv[k - r0], 0, 1), h0, l0);
-          split2(__builtin_shufflevector(sv[k - r0], sv[k - r0], 2, 3), h1, l1);
-          if (k < 13 || tl < 128) {
-            *reinterpret_cast<u32x2*>(dst) = (u32x2){h0, h1};
-            *reinterpret_cast<u32x2*>(dst + 4 * 4 * C22H_PLANE) = (u32x2){l0, l1};
-          }
+          park_pieces(dst, 4 * 4 * C22H_PLANE, sv[k - r0], k < 13 || tl < 128);
         }
       }
     }
@@ -1023,11 +929,7 @@ __global__ __launch_bounds__(256, 3) void c3d2_conv31h_kernel(const Conv31Params
     W[t][1] = p.wblk[((nt * 9 + t) * 2 + 1) * 64 + lane];
   }
   f32x4 b4, sl4;   // channels 16 nt + 4 kk .. + 3 of ONE position
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    b4[r] = p.bias[16 * nt + 4 * kk + r];
-    sl4[r] = p.slope[16 * nt + 4 * kk + r];
-  }
+  load_bias_slope(p.bias, p.slope, nt, kk, b4, sl4);
   const int n_items = p.n_utt * 5;
   __shared__ int q_next;   // dynamic work items: see c3d2_conv21h_kernel (three workgroups share a CU here)
   int item = blockIdx.x;
@@ -1057,15 +959,7 @@ __global__ __launch_bounds__(256, 3) void c3d2_conv31h_kernel(const Conv31Params
         if (256 * k + 255 < 2016 || tl < 2016 - 256 * k) sv[k] = *reinterpret_cast<const f32x4*>(g);
       }
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        unsigned h0, l0, h1, l1;
-        split2(__builtin_shufflevector(sv[k], sv[k], 0, 1), h0, l0);
-        split2(__builtin_shufflevector(sv[k], sv[k], 2, 3), h1, l1);
-        if (256 * k + 255 < 2016 || tl < 2016 - 256 * k) {
-          *reinterpret_cast<u32x2*>(a0s + 4 * 32 * k) = (u32x2){h0, h1};
-          *reinterpret_cast<u32x2*>(a0s + 4 * 32 * k + 4 * 4 * C31H_PLANE) = (u32x2){l0, l1};
-        }
-      }
+      for (int k = 0; k < 8; ++k) park_pieces(a0s + 4 * 32 * k, 4 * 4 * C31H_PLANE, sv[k], 256 * k + 255 < 2016 || tl < 2016 - 256 * k);
     }
     if (threadIdx.x == 0) q_next = p.queue ? (int)q_ticket + (int)gridDim.x : item + (int)gridDim.x;
     __syncthreads();
@@ -1093,9 +987,7 @@ __global__ __launch_bounds__(256, 3) void c3d2_conv31h_kernel(const Conv31Params
           bl[(tap + 2) % 3] = rd(tap + 2, 1);
         }
         __builtin_amdgcn_sched_barrier(0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[tap][0]), __builtin_bit_cast(f16x8, bh[tap % 3]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[tap][0]), __builtin_bit_cast(f16x8, bl[tap % 3]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[tap][1]), __builtin_bit_cast(f16x8, bh[tap % 3]), acc, 0, 0, 0);
+        acc = mfma_pieces(W[tap][0], W[tap][1], bh[tap % 3], bl[tap % 3], acc);
         __builtin_amdgcn_sched_barrier(0);
       }
       // chunked, column-major output [d][chunk = 2 nt + (kk >> 1)][w][h][8]: the lane's four channels are 16 contiguous bytes
@@ -1116,7 +1008,7 @@ __global__ __launch_bounds__(256, 3) void c3d2_conv31h_kernel(const Conv31Params
 // weight blocks of an N tile and ONE K block are 168 VGPRs: wave = (N tile nt, K block kb), eight waves; the two waves of an N tile
 // swap partial sums through LDS (kb 0 finishes tiles 0 - 2, kb 1 tiles 3 - 4).  The next item's runs are loaded into registers in
 // front of the tiles and parked behind them: one workgroup per CU, its memory latency under its own matrix work.
-// (As an instance of the f32 batch-GEMM template of c3d2_tail.hip, Winograd F(2,3) along depth: 1.34 - 1.62 ms per 4 018 cubes.) ----
+// (As an instance of c3d2_tail.hip's f32 batch-GEMM kernel when that was a template, Winograd F(2,3) along depth: 1.34 - 1.62 ms per 4 018 cubes.) ----
 // depth pitch 25, not 15: a tile's positions run on from one depth's 9 rows to the next, and with 25 = 9 (mod 16) so do their slots
 // mod 16 (see C22H_DP)
 constexpr int C32H_DP = 25;
@@ -1176,13 +1068,7 @@ __global__ __launch_bounds__(512) void c3d2_conv32h_kernel(const Conv32hParams p
       const int run = (e * 2185) >> 16, r = e - 30 * run;
       const int d = run >> 3, chunk = run & 7;
       unsigned* const dst = reg + 4 * (chunk * C32H_PLANE + d * C32H_DP + (r >> 1)) + 2 * (r & 1);
-      unsigned h0, l0, h1, l1;
-      split2(__builtin_shufflevector(sv[k], sv[k], 0, 1), h0, l0);
-      split2(__builtin_shufflevector(sv[k], sv[k], 2, 3), h1, l1);
-      if (k < 4 || threadIdx.x < 2400 - 4 * 512) {
-        *reinterpret_cast<u32x2*>(dst) = (u32x2){h0, h1};
-        *reinterpret_cast<u32x2*>(dst + 4 * 8 * C32H_PLANE) = (u32x2){l0, l1};
-      }
+      park_pieces(dst, 4 * 8 * C32H_PLANE, sv[k], k < 4 || threadIdx.x < 2400 - 4 * 512);
     }
   };
   // items: the first two of a workgroup at a fixed stride, every later one drawn from the device-wide counter ONE item ahead (the
@@ -1218,9 +1104,7 @@ __global__ __launch_bounds__(512) void c3d2_conv32h_kernel(const Conv32hParams p
           bl[(tap + 1) & 1] = rd(tap + 1, 1);
         }
         __builtin_amdgcn_sched_barrier(0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[tap][0]), __builtin_bit_cast(f16x8, bh[tap & 1]), a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[tap][0]), __builtin_bit_cast(f16x8, bl[tap & 1]), a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[tap][1]), __builtin_bit_cast(f16x8, bh[tap & 1]), a, 0, 0, 0);
+        a = mfma_pieces(W[tap][0], W[tap][1], bh[tap & 1], bl[tap & 1], a);
         __builtin_amdgcn_sched_barrier(0);
       }
       // partial sums over this wave's K block -> LDS (kept in registers for the tiles a wave finishes they cost 12 VGPRs this kernel
@@ -1256,7 +1140,7 @@ __global__ __launch_bounds__(512) void c3d2_conv32h_kernel(const Conv32hParams p
 // while staged into sixteen planes (eight channel chunks x {h, l}) of 16-byte slots, slot = d * 59 + 9 w + h; outputs 6 d x 9 h x 3 w =
 // 162 positions = 10.1 tiles; wave = N tile (eight waves: 128 output channels; 36 weight blocks = 144 VGPRs), every wave walks all
 // eleven tiles.  The next cube is loaded into registers in front of the tiles and parked behind them.
-// (As an instance of the f32 batch-GEMM template of c3d2_tail.hip, Winograd F(2,3) along depth: 0.54 - 0.69 ms per 4 018 cubes.) ----
+// (As an instance of c3d2_tail.hip's f32 batch-GEMM kernel when that was a template, Winograd F(2,3) along depth: 0.54 - 0.69 ms per 4 018 cubes.) ----
 // A plane holds [8 d][5 w][9 h] at depth pitch 59: positions are walked (depth, column, row) with the row fastest, 27 per depth, and
 // 59 = 27 (mod 16), so sixteen consecutive positions are sixteen consecutive slots mod 16 at every tap (see C22H_DP)
 constexpr int C41H_DP = 59;
@@ -1314,13 +1198,7 @@ __global__ __launch_bounds__(512) void c3d2_conv41h_kernel(const Conv41hParams p
       const int d = run >> 3, chunk = run & 7;
       const int pix = r >> 1, ph = (pix * 13) >> 6, pw = pix - 5 * ph;       // pixel = 5 h + w; pix / 5 for pix < 45
       unsigned* const dst = reg + 4 * (chunk * C41H_PLANE + d * C41H_DP + 9 * pw + ph) + 2 * (r & 1);
-      unsigned h0, l0, h1, l1;
-      split2(__builtin_shufflevector(sv[k], sv[k], 0, 1), h0, l0);
-      split2(__builtin_shufflevector(sv[k], sv[k], 2, 3), h1, l1);
-      if (k < NPC - 1 || threadIdx.x < C41H_PIECES - (NPC - 1) * 512) {
-        *reinterpret_cast<u32x2*>(dst) = (u32x2){h0, h1};
-        *reinterpret_cast<u32x2*>(dst + 4 * 8 * C41H_PLANE) = (u32x2){l0, l1};
-      }
+      park_pieces(dst, 4 * 8 * C41H_PLANE, sv[k], k < NPC - 1 || threadIdx.x < C41H_PIECES - (NPC - 1) * 512);
     }
   };
   int item = blockIdx.x, item_next = item + (int)gridDim.x;   // the counter is drawn one item ahead, as in c3d2_conv32h_kernel
@@ -1355,9 +1233,7 @@ __global__ __launch_bounds__(512) void c3d2_conv41h_kernel(const Conv41hParams p
           bl[(st + 1) & 1] = rd(st + 1, 1);
         }
         __builtin_amdgcn_sched_barrier(0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[st >> 1][st & 1][0]), __builtin_bit_cast(f16x8, bh[st & 1]), a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[st >> 1][st & 1][0]), __builtin_bit_cast(f16x8, bl[st & 1]), a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[st >> 1][st & 1][1]), __builtin_bit_cast(f16x8, bh[st & 1]), a, 0, 0, 0);
+        a = mfma_pieces(W[st >> 1][st & 1][0], W[st >> 1][st & 1][1], bh[st & 1], bl[st & 1], a);
         __builtin_amdgcn_sched_barrier(0);
       }
       if (16 * t + i < C41H_POS) {
@@ -1372,6 +1248,21 @@ __global__ __launch_bounds__(512) void c3d2_conv41h_kernel(const Conv41hParams p
     item = item_next;
     item_next = q_next;
   }
+}
+
+// The launch of one persistent two-piece kernel (conv2_1 .. conv4_1): `p` with its work-item counter (from svk_work_queue, which the
+// entry point has already called: a NULL queue = items at a fixed stride), the kernel of the pair that flags bit 1 selects, at most
+// max_per_cu workgroups of `threads` per CU.  `name` is what the entry point's errors call the launch.
+template <class P>
+int launch_conv(svk_ctx* ctx, const char* name, void (*kern_slope01)(const P), void (*kern_any)(const P), int32_t flags, P p,
+                size_t lds, int threads, int max_per_cu, int64_t items, unsigned* queue) {
+  void (*kern)(const P) = (flags & 2) ? kern_slope01 : kern_any;
+  p.queue = queue;
+  unsigned grid;
+  if (int rc = svk_persistent_grid(ctx, name, kern, lds, threads, max_per_cu, items, &grid)) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, ctx->stream, p);
+  SVK_LAUNCH_CHECK(ctx);
+  return SVK_OK;
 }
 
 }  // namespace
@@ -1392,26 +1283,13 @@ extern "C" int svk_c3d2_stage2(svk_ctx* ctx, const float* d_in, int32_t n_utt, c
   // conv2_1 and conv2_2 share a CU between workgroups: as many as the occupancy calculator allows
   unsigned* queues;
   if (int rc = svk_work_queue(ctx, SVK_SLOT_STAGE2, 2, &queues)) return rc;
-  {
-    Conv21hParams p{d_in, reinterpret_cast<const u32x4*>(d_w21blk), d_bias21, d_slope21, d_act2, n_utt, queues};
-    void (*kern)(const Conv21hParams) = (flags & 2) ? c3d2_conv21h_kernel<true> : c3d2_conv21h_kernel<false>;
-    const size_t lds = sizeof(unsigned) * (size_t)C21H_LDS_WORDS;
-    unsigned grid;
-    if (int rc = svk_persistent_grid(ctx, "svk_c3d2_stage2 (conv2_1)", kern, lds, 256, INT_MAX, (int64_t)n_utt * (S2_H / 4), &grid))
-      return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx->stream, p);
-    SVK_LAUNCH_CHECK(ctx);
-  }
-  {
-    Conv22hParams p{d_act2, reinterpret_cast<const u32x4*>(d_w22blk), d_bias22, d_slope22, d_out, n_utt, queues ? queues + 1 : nullptr};
-    void (*kern)(const Conv22hParams) = (flags & 2) ? c3d2_conv22h_kernel<true> : c3d2_conv22h_kernel<false>;
-    const size_t lds = sizeof(unsigned) * (size_t)C22H_LDS_WORDS;
-    unsigned grid;
-    if (int rc = svk_persistent_grid(ctx, "svk_c3d2_stage2 (conv2_2)", kern, lds, 256, INT_MAX, (int64_t)n_utt * 21, &grid)) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx->stream, p);
-    SVK_LAUNCH_CHECK(ctx);
-  }
-  return SVK_OK;
+  const Conv21hParams p21{d_in, reinterpret_cast<const u32x4*>(d_w21blk), d_bias21, d_slope21, d_act2, n_utt, nullptr};
+  if (int rc = launch_conv(ctx, "svk_c3d2_stage2 (conv2_1)", c3d2_conv21h_kernel<true>, c3d2_conv21h_kernel<false>, flags, p21,
+                           sizeof(unsigned) * (size_t)C21H_LDS_WORDS, 256, INT_MAX, (int64_t)n_utt * (S2_H / 4), queues))
+    return rc;
+  const Conv22hParams p22{d_act2, reinterpret_cast<const u32x4*>(d_w22blk), d_bias22, d_slope22, d_out, n_utt, nullptr};
+  return launch_conv(ctx, "svk_c3d2_stage2 (conv2_2)", c3d2_conv22h_kernel<true>, c3d2_conv22h_kernel<false>, flags, p22,
+                     sizeof(unsigned) * (size_t)C22H_LDS_WORDS, 256, INT_MAX, (int64_t)n_utt * 21, queues ? queues + 1 : nullptr);
 }
 
 extern "C" int svk_c3d2_conv31(svk_ctx* ctx, const float* d_in, int32_t n_utt, const void* d_wblk, const float* d_bias,
@@ -1424,15 +1302,11 @@ extern "C" int svk_c3d2_conv31(svk_ctx* ctx, const float* d_in, int32_t n_utt, c
   SVK_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_wblk) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
               "buffers must be 16-byte aligned");
   SVK_REQUIRE(ctx, (int64_t)n_utt * 5 < ((int64_t)1 << 31), "too many cubes for one launch");
-  Conv31Params p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, nullptr};
-  void (*kern)(const Conv31Params) = (flags & 2) ? c3d2_conv31h_kernel<true> : c3d2_conv31h_kernel<false>;
-  const size_t lds = sizeof(unsigned) * (size_t)C31H_LDS_WORDS;
-  unsigned grid;
-  if (int rc = svk_work_queue(ctx, SVK_SLOT_CONV31, 1, &p.queue)) return rc;
-  if (int rc = svk_persistent_grid(ctx, "svk_c3d2_conv31", kern, lds, 256, INT_MAX, (int64_t)n_utt * 5, &grid)) return rc;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx->stream, p);
-  SVK_LAUNCH_CHECK(ctx);
-  return SVK_OK;
+  const Conv31Params p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, nullptr};
+  unsigned* queue;
+  if (int rc = svk_work_queue(ctx, SVK_SLOT_CONV31, 1, &queue)) return rc;
+  return launch_conv(ctx, "svk_c3d2_conv31", c3d2_conv31h_kernel<true>, c3d2_conv31h_kernel<false>, flags, p,
+                     sizeof(unsigned) * (size_t)C31H_LDS_WORDS, 256, INT_MAX, (int64_t)n_utt * 5, queue);
 }
 
 extern "C" int svk_c3d2_conv32t(svk_ctx* ctx, const float* d_in, int32_t n_utt, const void* d_wblk, const float* d_bias,
@@ -1445,15 +1319,11 @@ extern "C" int svk_c3d2_conv32t(svk_ctx* ctx, const float* d_in, int32_t n_utt, 
   SVK_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_wblk) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
               "buffers must be 16-byte aligned");
   SVK_REQUIRE(ctx, (int64_t)n_utt * 5 + 2 * (int64_t)ctx->num_cu < ((int64_t)1 << 31), "too many cubes for one launch");
-  Conv32hParams p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, nullptr};
-  void (*kern)(const Conv32hParams) = (flags & 2) ? c3d2_conv32h_kernel<true> : c3d2_conv32h_kernel<false>;
-  const size_t lds = sizeof(float) * (size_t)(C32H_LDS_WORDS + C32H_XCH_FLOATS);
-  unsigned grid;
-  if (int rc = svk_work_queue(ctx, SVK_SLOT_CONV32_42, 1, &p.queue)) return rc;
-  if (int rc = svk_persistent_grid(ctx, "svk_c3d2_conv32t", kern, lds, 512, 1, (int64_t)n_utt * 5, &grid)) return rc;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, ctx->stream, p);
-  SVK_LAUNCH_CHECK(ctx);
-  return SVK_OK;
+  const Conv32hParams p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, nullptr};
+  unsigned* queue;
+  if (int rc = svk_work_queue(ctx, SVK_SLOT_CONV32, 1, &queue)) return rc;
+  return launch_conv(ctx, "svk_c3d2_conv32t", c3d2_conv32h_kernel<true>, c3d2_conv32h_kernel<false>, flags, p,
+                     sizeof(float) * (size_t)(C32H_LDS_WORDS + C32H_XCH_FLOATS), 512, 1, (int64_t)n_utt * 5, queue);
 }
 
 extern "C" int svk_c3d2_conv41(svk_ctx* ctx, const float* d_in, int32_t n_utt, const void* d_wblk, const float* d_bias,
@@ -1466,13 +1336,9 @@ extern "C" int svk_c3d2_conv41(svk_ctx* ctx, const float* d_in, int32_t n_utt, c
   SVK_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_wblk) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
               "buffers must be 16-byte aligned");
   SVK_REQUIRE(ctx, (int64_t)n_utt + 2 * (int64_t)ctx->num_cu < ((int64_t)1 << 31), "too many cubes for one launch");
-  Conv41hParams p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, nullptr};
-  void (*kern)(const Conv41hParams) = (flags & 2) ? c3d2_conv41h_kernel<true> : c3d2_conv41h_kernel<false>;
-  const size_t lds = sizeof(unsigned) * (size_t)C41H_LDS_WORDS;
-  unsigned grid;
-  if (int rc = svk_work_queue(ctx, SVK_SLOT_CONV41, 1, &p.queue)) return rc;
-  if (int rc = svk_persistent_grid(ctx, "svk_c3d2_conv41", kern, lds, 512, 1, n_utt, &grid)) return rc;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, ctx->stream, p);
-  SVK_LAUNCH_CHECK(ctx);
-  return SVK_OK;
+  const Conv41hParams p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, nullptr};
+  unsigned* queue;
+  if (int rc = svk_work_queue(ctx, SVK_SLOT_CONV41, 1, &queue)) return rc;
+  return launch_conv(ctx, "svk_c3d2_conv41", c3d2_conv41h_kernel<true>, c3d2_conv41h_kernel<false>, flags, p,
+                     sizeof(unsigned) * (size_t)C41H_LDS_WORDS, 512, 1, n_utt, queue);
 }
