@@ -831,8 +831,8 @@ __global__ __launch_bounds__(256) void log_power_kernel(float* __restrict__ p, i
   float m = -INFINITY;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float v = p[i];
-    v = v <= 1e-20f ? 1e-20f : v;            // processing.py:192
-    v = 10.0f * log10f(v);
+    // processing.py:192: the floor is 10 log10(1e-20) = -200 exactly (the device's log10f(1e-20f) is one ulp below -20)
+    v = v <= 1e-20f ? -200.0f : 10.0f * log10f(v);
     p[i] = v;
     m = fmaxf(m, v);
   }
@@ -1151,7 +1151,8 @@ int svk_cmvnw(svk_ctx* ctx, const float* d_in, int32_t n_utt, int32_t max_frames
     return SVK_OK;
   }
   // rows per thread: long enough to amortise the direct window sum of a segment's first row, short enough
-  // to keep a few hundred threads per clip
+  // to keep a few hundred threads per clip.  Only clips of more than CW_CAP frames get here, so this is always 128 (the
+  // 32-row choice dates from before the tile kernel took the short clips)
   const int seg = max_frames <= 1024 ? 32 : 128;
   const int64_t per = (int64_t)((max_frames + seg - 1) / seg) * n_cols;
   const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((per + 255) / 256, ctx->num_cu * 4)), (unsigned)n_utt);

@@ -1413,8 +1413,9 @@ def test_mel_stage_wide_banks(eng):
 
 
 def test_cmvnw_long_clips_and_windows(eng):
-    """Sliding-window sums (one row in, one row out per step) against the oracle's direct window means: clips
-    longer and shorter than the window, the 128-row segment path (> 1 024 frames), ragged batch."""
+    """cmvnw_tile_kernel (prefix sums in LDS; every clip here is at most 3 900 frames, so svk_cmvnw takes nothing else)
+    against the oracle's direct window means: clips longer and shorter than the window, ragged batch.  The sliding-sum
+    kernel (cmvnw_kernel, longer clips) is covered by tests/test_postprocessing_float64.py."""
     rng = np.random.default_rng(17)
     for T, C, win in ((2500, 40, 301), (90, 13, 301), (1024, 8, 31), (1025, 8, 5)):
         x = rng.standard_normal((T, C)) * 3.0 + 1.0
