@@ -20,14 +20,21 @@
 //
 // Work item = (cube u, pooled output column j, half q of the output depths): conv1_2 outputs
 //   d in [8q, 8q + 8), h in [0, 36), w in {2j, 2j + 1}  ->  pooled column j, 16 channels.
-// A persistent workgroup of 8 waves (two per SIMD; it owns the CU's LDS) loops over items:
-//   1. the 12 x 80 x 6 cube patch the item needs is moved into LDS by LDS-DMA inside the previous item's matrix work and
-//      converted in place to (h, l) half pairs by the waves that fetched it;
-//   2. conv1_1 as a GEMM [16 channels] x [K = 32: 15 taps + pad, h | l] x [16 pixels], + PReLU, split into (h, l), written to
-//      the act1 tile in LDS: 10 depths x 80 rows x 2 columns x 16 channels;
-//   3. conv1_2 as an implicit GEMM in the direct form, two taps per K = 32 block, the weights of all 27 taps in 112 VGPRs; a wave
-//      walks one set of 16 (row, column) positions along the depth and reads every fragment once for its three kd (depth chains);
-//   4. bias (in the accumulator), PReLU, max over the column pair (adjacent lanes: one DPP instruction), 16-byte stores.
+// A persistent workgroup of 8 waves (two per SIMD; it owns the CU's LDS) loops over items; the kernel is the item loop over four
+// phases, each a function of its own below:
+//   1. convert_patch: the 12 x 80 x 6 cube patch the item needs is moved into LDS by LDS-DMA (dma_patch_w) inside the previous
+//      item's matrix work and converted in place to (h, l) half pairs by the waves that fetched it;
+//   2. conv11_one_channel / conv11_three_channels: conv1_1 as a GEMM [16 channels] x [K = 32: 15 taps + pad, h | l] x [16 pixels]
+//      (conv11_mfma), + PReLU, split into (h, l), written to the act1 tile in LDS (park_pieces): 10 depths x 80 rows x 2 columns x
+//      16 channels;
+//   3. conv12_chain / conv12_tile: conv1_2 as an implicit GEMM in the direct form, two taps per K = 32 block, the weights of all 27
+//      taps in 112 VGPRs; a wave walks one set of 16 (row, column) positions along the depth and reads every fragment (Conv12Frags)
+//      once for its three kd (depth chains);
+//   4. prelu_pool_store: bias (in the accumulator), PReLU, max over the column pair (adjacent lanes: one DPP instruction), 16-byte
+//      stores.
+// Barriers, waits and the item pipeline are in the kernel itself (conv11_three_channels owns the two barriers around its staged
+// channels).  The other kernels of this file are one function each; all share the leaf helpers of c3d2_common.h, and the host side
+// one parameter struct (ConvParams), one set of argument checks (conv_checks) and one entry body (conv_entry).
 #include <climits>
 #include <vector>
 
@@ -204,364 +211,329 @@ __device__ __forceinline__ void conv11_weights(const unsigned short* blk, int i,
 // + a zero tap each (six MFMAs per tile instead of two), the accumulators of a wave's 13 tiles kept in registers across the three
 // channel passes.  Channel 0 comes through the patch buffer as before (fetched inside the previous item's conv1_2); channels 1
 // and 2 are fetched at the top of the item into the act1 tile, which is free until conv1_1's epilogue writes it, while channel 0
-// is multiplied.  conv1_2, the pool and the output layout are the one-channel kernel's.  (NCH = 1 is the code as it was: every
-// NCH = 3 step is under `if constexpr`.)
-// conv1_2's depth chains (phase (2) of the kernel): CONV12_CHAIN output depths per chain; its units in issue order are the four
+// is multiplied.  conv1_2, the pool and the output layout are the one-channel kernel's.  (The two differ in their conv1_1 phase,
+// conv11_one_channel / conv11_three_channels, and in conv1_2's walk: see the kernel.)
+// conv1_2's depth chains (conv12_chain): CONV12_CHAIN output depths per chain; its units in issue order are the four
 // pair units of input depth s = 0 .. CONV12_CHAIN + 1 and, behind those of every s >= 2, pairs 12 and 13 of output s - 2
 constexpr int CONV12_CHAIN = 4, CONV12_UNITS = 4 * (CONV12_CHAIN + 2) + 2 * CONV12_CHAIN;
 constexpr int conv12_unit_step(int n) { return n < 8 ? n / 4 : 2 + (n - 8) / 6; }
 constexpr int conv12_unit_sub(int n) { return n < 8 ? n % 4 : (n - 8) % 6; }   // 0 .. 3: pair m of the step; 4, 5: pairs 12, 13
 static_assert(2 * CONV12_CHAIN == TD, "two chains cover an item's output depths");
 
-// (NCH = 3 keeps the tile loop: with 13 conv1_1 accumulators behind it the chain takes its spill from 6 to 16 VGPRs)
-template <bool SLOPE01, int NCH = 1, bool CONV12_CHAINS = (NCH == 1)>
+// A lane's place in the workgroup of eight waves: lane = 16 kk + i, wave = 4 part + pair (wave-uniform).  Part 0 are the four
+// OLDER waves, which fetch and convert the patches (see dma_patch_w)
+struct Lane1 { int lane, wave, i, kk, pair, part; };
+
+// the item's channel-0 patch (the one-channel kernel's only one): plane NCH u of [n][NCH][max_frames][40]
+template <int NCH>
+__device__ __forceinline__ void dma_patch_ch0(const Stage1Params& p, ItemPos it, int starts_v, const Lane1& L, float* patch) {
+  if constexpr (NCH == 1) dma_patch_w(p, it, starts_v, L.pair, L.lane, patch);
+  else dma_patch_plane(p, it, (int64_t)NCH * it.u, starts_v, L.pair, L.lane, patch);
+}
+
+// ---- phase 1: the patch at `buf` in place, f32 -> (l << 16 | h) words: by the wave that FETCHED the words (its own vmcnt(0) is
+// all it needs: no barrier of its own), depths pair, pair + 4, pair + 8 = 3 x 640 words = nine 16-byte trips per lane, all nine
+// reads in flight before the first conversion.  (As a pass of all eight waves in front of conv1_1, behind a barrier: 0.45 of 4.11 ms.)
+__device__ __forceinline__ void convert_patch(float* buf, int pair, int lane) {
+  f32x4 v[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const int w = (pair + 4 * (k / 3)) * (NFRAME * WPW) + 256 * (k % 3) + 4 * lane;
+    if (k % 3 < 2 || lane < 32) v[k] = *reinterpret_cast<const f32x4*>(buf + w);
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const int w = (pair + 4 * (k / 3)) * (NFRAME * WPW) + 256 * (k % 3) + 4 * lane;
+    unsigned h0, l0, h1, l1;
+    split2(__builtin_shufflevector(v[k], v[k], 0, 1), h0, l0);
+    split2(__builtin_shufflevector(v[k], v[k], 2, 3), h1, l1);
+    u32x4 o;   // word = the value's own pair: low half h, high half l
+    o[0] = __builtin_amdgcn_perm(l0, h0, 0x05040100u);
+    o[1] = __builtin_amdgcn_perm(l0, h0, 0x07060302u);
+    o[2] = __builtin_amdgcn_perm(l1, h1, 0x05040100u);
+    o[3] = __builtin_amdgcn_perm(l1, h1, 0x07060302u);
+    if (k % 3 < 2 || lane < 32) *reinterpret_cast<u32x4*>(buf + w) = o;
+  }
+}
+
+// ---- phase 2: conv1_1 + PReLU -> act1 as (h, l): 100 tiles of 16 pixels, tile tt = wave + 8 m (m = 12: waves 0 - 3 only) ----
+// A lane's addresses.  Its B fragment is four patch words, each a tap's (h, l) pair as it lies in the patch (K order: conv11_tap):
+// the vertical pair at pov and the horizontal pair at poh, patch-word offsets of tile m = 0 (pixel 16 tt + i of tile tt: row
+// 8 tt + (i >> 1)); tile m is 64 rows on
+__device__ __forceinline__ int conv11_patch_word(const Lane1& L, int e) { return (8 * L.wave + (L.i >> 1)) * WPW + conv11_word(L.kk, e, L.i & 1); }
+// pixel 16 tt + i = (dd = tt / 10, r = 8 (tt % 10) + (i >> 1), col = i & 1): slot 8 tt + 2 (i >> 2) + (i & 1) of the plane
+// (quarter kk >> 1 [+ 2 for l], parity (i >> 1) & 1); the lane's four channels are bytes 8 (kk & 1) .. + 7 of the slot.  -> the
+// h words of tile m = 0; tile m is 4 * 64 m words on, the l words 4 * 4 * HPLANE
+__device__ __forceinline__ unsigned* conv11_act_word(unsigned* act, const Lane1& L) {
+  return act + 4 * ((((L.kk >> 1) * 2 + ((L.i >> 1) & 1)) * HPLANE) + 8 * L.wave + 2 * (L.i >> 2) + (L.i & 1)) + 2 * (L.kk & 1);
+}
+__device__ __forceinline__ u32x4 conv11_frag(const unsigned* pv, const unsigned* ph, int m) {
+  const int o = 64 * WPW * m;
+  return (u32x4){pv[o], pv[o + NFRAME * WPW], ph[o], ph[o + 1]};
+}
+// one channel's K = 32 block, A = (WH, WL), into the accumulators of tiles m0 .. m0 + NT - 1: acc[t] = (FIRST ? bias : acc[t]) + ..
+template <bool FIRST, int NT>
+__device__ __forceinline__ void conv11_mfma(const unsigned* pv, const unsigned* ph, int m0, u32x4 WH, u32x4 WL, f32x4 bias, f32x4* acc) {
+  u32x4 B[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    B[t] = conv11_frag(pv, ph, m0 + t);
+    // (a fence per tile: without it the compiler pairs words of DIFFERENT tiles into one read2 and reassembles B with
+    // three v_mov_b32 per tile)
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, WH), __builtin_bit_cast(f16x8, B[t]), FIRST ? bias : acc[t], 0, 0, 0);
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, WL), __builtin_bit_cast(f16x8, B[t]), acc[t], 0, 0, 0);
+}
+// NT tiles from the patch to act1
+template <bool SLOPE01, int NT>
+__device__ __forceinline__ void conv11_tiles(const unsigned* pv, const unsigned* ph, unsigned* aw, int m0, u32x4 WH, u32x4 WL, f32x4 bias, f32x4 slope) {
+  f32x4 acc[NT];
+  conv11_mfma<true, NT>(pv, ph, m0, WH, WL, bias, acc);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) park_pieces(aw + 4 * 64 * (m0 + t), 4 * 4 * HPLANE, prelu4<SLOPE01>(acc[t], slope), true);
+}
+template <bool SLOPE01>
+__device__ __forceinline__ void conv11_one_channel(const unsigned* patch, int pov, int poh, unsigned* aw, const Lane1& L, u32x4 WH, u32x4 WL,
+                                                   f32x4 bias, f32x4 slope) {
+#pragma unroll
+  for (int m0 = 0; m0 < 12; m0 += 4) conv11_tiles<SLOPE01, 4>(patch + pov, patch + poh, aw, m0, WH, WL, bias, slope);
+  if (L.wave < 4) conv11_tiles<SLOPE01, 1>(patch + pov, patch + poh, aw, 12, WH, WL, bias, slope);
+}
+// one channel's K = 32 block (its patch at `src`) into the accumulators of the wave's 13 tiles (the bias rides in with channel 0)
+template <bool FIRST>
+__device__ __forceinline__ void conv11_chan_pass(const unsigned* src, int pov, int poh, const Lane1& L, u32x4 WH, u32x4 WL, f32x4 bias,
+                                                 f32x4 (&acc)[13]) {
+#pragma unroll
+  for (int m0 = 0; m0 < 12; m0 += 2) conv11_mfma<FIRST, 2>(src + pov, src + poh, m0, WH, WL, bias, acc + m0);
+  if (L.wave < 4) conv11_mfma<FIRST, 1>(src + pov, src + poh, 12, WH, WL, bias, acc + 12);
+}
+// The three-channel form, with its two barriers: channel 0 from the patch buffer; channels 1 and 2 of this item -> the act1 tile's
+// first 2 x 30 KB (nobody reads act1 between the last item's final barrier and this item's epilogue), by the waves that fetch
+// channel 0; they land while channel 0 is multiplied
+template <bool SLOPE01, int NCH>
+__device__ __forceinline__ void conv11_three_channels(const Stage1Params& p, ItemPos cur, int starts_cur, unsigned* act, const float* patch,
+                                                      int pov, int poh, unsigned* aw, const Lane1& L, f32x4 bias, f32x4 slope) {
+  float* const chan12 = reinterpret_cast<float*>(act);
+  if (L.part == 0) {
+#pragma unroll
+    for (int ch = 1; ch < NCH; ++ch)
+      dma_patch_plane(p, cur, (int64_t)NCH * cur.u + ch, starts_cur, L.pair, L.lane, chan12 + (ch - 1) * WP_FLOATS);
+  }
+  f32x4 acc[13];   // tile wave + 8 m; m = 12 for waves 0 - 3 only
+  // conv1_1's weight blocks are gathered per item (L1-resident, 16 halves per lane per channel): held across the item loop as
+  // W1a / W1b are in the one-channel kernel, the six blocks and the 13 accumulators spill (256 VGPRs).  The opaque copy of the pointer
+  // keeps the compiler from hoisting the loads out of the loop.
+  const unsigned short* w1blk = reinterpret_cast<const unsigned short*>(p.w1blk);
+  asm volatile("" : "+s"(w1blk));
+  {
+    u32x4 WH, WL;
+    conv11_weights(w1blk, L.i, L.kk, WH, WL);
+    conv11_chan_pass<true>(reinterpret_cast<const unsigned*>(patch), pov, poh, L, WH, WL, bias, acc);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of channels 1 and 2 have landed
+  if (L.part == 0) {
+#pragma unroll
+    for (int ch = 1; ch < NCH; ++ch) convert_patch(chan12 + (ch - 1) * WP_FLOATS, L.pair, L.lane);
+  }
+  __syncthreads();   // channels 1 and 2 are in place and converted
+#pragma unroll
+  for (int ch = 1; ch < NCH; ++ch) {
+    u32x4 WH, WL;
+    conv11_weights(w1blk + 2 * ch * 64 * 8, L.i, L.kk, WH, WL);
+    conv11_chan_pass<false>(reinterpret_cast<const unsigned*>(chan12 + (ch - 1) * WP_FLOATS), pov, poh, L, WH, WL, bias, acc);
+  }
+  __syncthreads();   // every wave has read channels 1 and 2: act1 may be written
+#pragma unroll
+  for (int m = 0; m < 13; ++m) {
+    if (m == 12 && L.wave >= 4) break;
+    park_pieces(aw + 4 * 64 * m, 4 * 4 * HPLANE, prelu4<SLOPE01>(acc[m], slope), true);
+  }
+}
+
+// ---- phases 3 and 4: conv1_2 + PReLU + pool: 576 positions (depth, row, column) in tiles of 16 ----
+// The B fragments of the 16 positions (depth d + .., row, column i & 1) a lane group reads.  Pixel (dd, r = 2 row + kh, col),
+// channels 8 (kk & 1) .. + 7: slot (((kk & 1) * 2 + (kh & 1)) * 10 + dd) * 80 + (row + kh / 2) * 2 + col of the h planes; the l
+// planes 4 HPLANE slots on.  The taps of a pair (kd, 2 m), (kd, 2 m + 1) differ by the parity plane (a2); the pair 12 = (0, 8) |
+// (1, 8) by one depth (a3); pair 13 = the LAST tap (2, 8) alone, as [h | l] in ONE fragment (a13: lanes kk >= 2 read the l planes):
+// [H | H] x [h | l] + [L | 0] x [h | l] are its three piece products in two MFMAs and one read, where [h | -] and [l | -] against
+// [H | 0], [L | 0] were three and two
+struct Conv12Frags {
+  const char *a2, *a3, *a13;
+  __device__ __forceinline__ Conv12Frags(const unsigned* act, int d, int row, int i, int kk) {
+    const int base = 16 * (((kk & 1) * 2) * HPLANE + d * 80 + 2 * row + (i & 1));
+    a2 = reinterpret_cast<const char*>(act) + base + (kk >= 2 ? 16 * HPLANE : 0);
+    a3 = reinterpret_cast<const char*>(act) + base + (kk >= 2 ? 16 * 80 : 0);
+    a13 = a3 + (kk >= 2 ? 16 * 4 * HPLANE - 16 * 80 : 0);
+  }
+  // piece (0: h, 1: l) of pair m < 4 at INPUT depth d + dd (any kd: the fragment depends on the input depth alone), or of pair 12
+  // (m = 4) / pair 13 (m = 5) of OUTPUT depth d + dd
+  __device__ __forceinline__ u32x4 rd(int dd, int m, int piece) const {
+    const char* ad = m < 4 ? a2 + 1280 * dd + 32 * m : m == 4 ? a3 + 1280 * dd + 32 * 4 : a13 + 1280 * (dd + 2) + 32 * 4;
+    return *reinterpret_cast<const u32x4*>(ad + 16 * 4 * HPLANE * piece);
+  }
+};
+// pair pr's piece products: three, two for the last pair (its fragment is [h | l]: no l fragment)
+__device__ __forceinline__ f32x4 conv12_pieces(const u32x4 (&W2)[HPAIRS][2], int pr, u32x4 h, u32x4 l, f32x4 c) {
+  return mfma_pieces(W2[pr][0], W2[pr][1], h, l, c, pr < HPAIRS - 1);
+}
+
+// One stand-alone tile: 16 positions (dq, row, column i & 1), every fragment read by the tile itself (27 reads, 41 MFMAs):
+// pair pr: 0 .. 11 = (kd = pr / 4, kh = 2 (pr % 4) | + 1), then 12 and 13
+template <bool SLOPE01>
+__device__ __forceinline__ void conv12_tile(const unsigned* act, const u32x4 (&W2)[HPAIRS][2], f32x4 bias, f32x4 slope, float* obase,
+                                            int dq, int row, const Lane1& L) {
+  const Conv12Frags f(act, dq, row, L.i, L.kk);
+  auto rd = [&](int pr, int piece) -> u32x4 { return pr < 12 ? f.rd(pr / 4, pr % 4, piece) : f.rd(0, pr - 8, piece); };
+  f32x4 acc = bias;
+  // fragments TWO pairs ahead (three rotating sets): a pair is 48 cycles of MFMA, less than an LDS round trip
+  u32x4 bh[3], bl[3];
+  bh[0] = rd(0, 0);
+  bl[0] = rd(0, 1);
+  bh[1] = rd(1, 0);
+  bl[1] = rd(1, 1);
+#pragma unroll
+  for (int pr = 0; pr < HPAIRS; ++pr) {
+    if (pr + 2 < HPAIRS) {
+      bh[(pr + 2) % 3] = rd(pr + 2, 0);
+      if (pr + 2 < HPAIRS - 1) bl[(pr + 2) % 3] = rd(pr + 2, 1);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    acc = conv12_pieces(W2, pr, bh[pr % 3], bl[pr % 3], acc);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  prelu_pool_store<SLOPE01>(acc, slope, obase + dq * S_D + row * S_PAR, (L.i & 1) == 0);
+}
+
+// A DEPTH CHAIN: the fragment of pair (kd, m) of output (dq, row, col) is the act1 slot of (dq + kd, row + m, col) -- it
+// depends on the input depth dq + kd alone, so a wave that keeps ONE set of 16 (row, col) positions over consecutive
+// output depths reads the eight fragments (pairs m = 0 .. 3, h and l) of an input depth ONCE and multiplies them into
+// three live accumulators: kd = 0 of output dd, kd = 1 of dd - 1, kd = 2 of dd - 2.  An output whose kd = 2 step is done
+// takes pairs 12 and 13 (three reads of its own) and leaves through the epilogue.  Every output receives its 41 MFMAs
+// in the stand-alone tile's order (kd-major, pairs 0 - 3 inside a kd, then 12, 13) with the same operands: bit-identical.
+// Eight chains of four output depths, one per wave: rows 8 pt .. 8 pt + 7 (pt = wave & 3) x depth half (wave >> 2), six
+// input depths, 6 x 8 + 4 x 3 = 60 reads for 164 MFMAs.  Rows 32 - 35 (64 positions) are four stand-alone tiles of two
+// depths each on the YOUNGER waves (the older ones fetch and convert the next patch): 588 reads per item, not 972.
+template <bool SLOPE01>
+__device__ __forceinline__ void conv12_chain(const unsigned* act, const u32x4 (&W2)[HPAIRS][2], f32x4 bias, f32x4 slope, float* obase,
+                                             const Lane1& L) {
+  const int row = 8 * L.pair + (L.i >> 1), d0 = 4 * L.part;
+  const Conv12Frags f(act, d0, row, L.i, L.kk);
+  // unit n of the chain's 32 (conv12_unit_step / _sub): the four pairs of input depth s, behind them (s >= 2) pairs 12
+  // and 13 of output s - 2.  Fragments TWO units ahead, three rotating sets, as in the stand-alone tile
+  auto rd = [&](int n, int piece) -> u32x4 {
+    const int s = conv12_unit_step(n), e = conv12_unit_sub(n);
+    return f.rd(e < 4 ? s : s - 2, e, piece);
+  };
+  f32x4 acc[CONV12_CHAIN];
+  u32x4 bh[3], bl[3];
+  bh[0] = rd(0, 0);
+  bl[0] = rd(0, 1);
+  bh[1] = rd(1, 0);
+  bl[1] = rd(1, 1);
+#pragma unroll
+  for (int n = 0; n < CONV12_UNITS; ++n) {
+    if (n + 2 < CONV12_UNITS) {
+      bh[(n + 2) % 3] = rd(n + 2, 0);
+      if (conv12_unit_sub(n + 2) != 5) bl[(n + 2) % 3] = rd(n + 2, 1);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const int s = conv12_unit_step(n), e = conv12_unit_sub(n);
+    if (e < 4) {
+#pragma unroll
+      for (int kd = 0; kd < 3; ++kd) {
+        const int o = s - kd;
+        if (o >= 0 && o < CONV12_CHAIN) acc[o] = conv12_pieces(W2, 4 * kd + e, bh[n % 3], bl[n % 3], kd == 0 && e == 0 ? bias : acc[o]);
+      }
+    } else {
+      const int o = s - 2;
+      acc[o] = conv12_pieces(W2, 8 + e, bh[n % 3], bl[n % 3], acc[o]);
+      if (e == 5) prelu_pool_store<SLOPE01>(acc[o], slope, obase + (d0 + o) * S_D + row * S_PAR, (L.i & 1) == 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// The driver: the prologue (operands that stay in registers: conv1_2's weights, 112 VGPRs; NCH = 1: conv1_1's too), the first
+// item's patch, then the item loop over phases 2 - 4 with phase 1 of the NEXT item inside.  Items: `item` is multiplied, item1's
+// patch is fetched (crop starts: `starts`), item2's crop starts are fetched, item3 is drawn from the device-wide counter.
+// (NCH = 3 keeps conv1_2's tile loop: with 13 conv1_1 accumulators behind it the chain takes its spill from 6 to 16 VGPRs)
+template <bool SLOPE01, int NCH = 1>
 __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p) {
+  constexpr bool CONV12_CHAINS = NCH == 1;
   extern __shared__ __attribute__((aligned(16))) float smem_c3d2[];
   unsigned* const act = reinterpret_cast<unsigned*>(smem_c3d2);   // [HACT_WORDS]
   float* const patch = smem_c3d2 + HACT_WORDS;                    // [WP_FLOATS]: [12 dd][80 h][8], f32 from the DMA, then (l << 16 | h) words
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int i = lane & 15, kk = lane >> 4;
-  const int pair = wave & 3, part = wave >> 2;
+  const Lane1 L{lane, wave, lane & 15, lane >> 4, wave & 3, wave >> 2};
   const int n_items = p.n_utt * 36;
 
   u32x4 W2[HPAIRS][2];
-#pragma unroll
-  for (int pr = 0; pr < HPAIRS; ++pr) {
-    W2[pr][0] = p.w2blk[(2 * pr) * 64 + lane];
-    W2[pr][1] = p.w2blk[(2 * pr + 1) * 64 + lane];
-  }
+  load_wblk(p.w2blk, 0, lane, W2);
   u32x4 W1a, W1b;   // NCH = 1: conv1_1's A operand, held across the item loop (NCH = 3 gathers its three per item)
-  if constexpr (NCH == 1) conv11_weights(reinterpret_cast<const unsigned short*>(p.w1blk), i, kk, W1a, W1b);
-  // the lane's vertical and horizontal pair, as patch-word offsets from its pixel's row (pixel 16 tt + i of tile tt: row 8 tt + (i >> 1))
-  const int pov = (8 * wave + (i >> 1)) * WPW + conv11_word(kk, 0, i & 1), poh = (8 * wave + (i >> 1)) * WPW + conv11_word(kk, 2, i & 1);
+  if constexpr (NCH == 1) conv11_weights(reinterpret_cast<const unsigned short*>(p.w1blk), L.i, L.kk, W1a, W1b);
+  const int pov = conv11_patch_word(L, 0), poh = conv11_patch_word(L, 2);
   f32x4 b1v, sl1v, b2v, sl2v;   // a lane holds channels 4 kk .. 4 kk + 3 of ONE position (A = the weights)
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    b1v[r] = p.bias1[4 * kk + r];
-    sl1v[r] = p.slope1[4 * kk + r];
-    b2v[r] = p.bias2[4 * kk + r];
-    sl2v[r] = p.slope2[4 * kk + r];
-  }
+  load_bias_slope(p.bias1, p.slope1, 0, L.kk, b1v, sl1v);
+  load_bias_slope(p.bias2, p.slope2, 0, L.kk, b2v, sl2v);
 
   int starts = 0;
   int starts_cur = 0;   // NCH = 3: the current item's crop starts (`starts` is already the next item's by the top of the loop)
   __shared__ int q_item3;
   int item = blockIdx.x, item1 = item + (int)gridDim.x, item2 = item1 + (int)gridDim.x;
   ItemPos cur = ItemPos::of(item), nx = ItemPos::of(item1), nx2 = ItemPos::of(item2);
-  // The patch in place, f32 -> (l << 16 | h) words: by the wave that FETCHED the words (its own vmcnt(0) is all it needs: no
-  // barrier of its own), depths pair, pair + 4, pair + 8 = 3 x 640 words = nine 16-byte trips per lane, all nine reads in flight
-  // before the first conversion.  (As a pass of all eight waves in front of conv1_1, behind a barrier: 0.45 of 4.11 ms.)
-  auto convert_own = [&]() {
-    f32x4 v[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const int w = (pair + 4 * (k / 3)) * (NFRAME * WPW) + 256 * (k % 3) + 4 * lane;
-      if (k % 3 < 2 || lane < 32) v[k] = *reinterpret_cast<const f32x4*>(patch + w);
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const int w = (pair + 4 * (k / 3)) * (NFRAME * WPW) + 256 * (k % 3) + 4 * lane;
-      unsigned h0, l0, h1, l1;
-      split2(__builtin_shufflevector(v[k], v[k], 0, 1), h0, l0);
-      split2(__builtin_shufflevector(v[k], v[k], 2, 3), h1, l1);
-      u32x4 o;   // word = the value's own pair: low half h, high half l
-      o[0] = __builtin_amdgcn_perm(l0, h0, 0x05040100u);
-      o[1] = __builtin_amdgcn_perm(l0, h0, 0x07060302u);
-      o[2] = __builtin_amdgcn_perm(l1, h1, 0x05040100u);
-      o[3] = __builtin_amdgcn_perm(l1, h1, 0x07060302u);
-      if (k % 3 < 2 || lane < 32) *reinterpret_cast<u32x4*>(patch + w) = o;
-    }
-  };
-  // (the same for a patch at `buf`: NCH = 3's channels 1 and 2, staged in the act1 tile; a separate lambda, so that the one-channel
-  // kernel's code stays what it was)
-  auto convert_own_at = [&](float* buf) {
-    f32x4 v[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const int w = (pair + 4 * (k / 3)) * (NFRAME * WPW) + 256 * (k % 3) + 4 * lane;
-      if (k % 3 < 2 || lane < 32) v[k] = *reinterpret_cast<const f32x4*>(buf + w);
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const int w = (pair + 4 * (k / 3)) * (NFRAME * WPW) + 256 * (k % 3) + 4 * lane;
-      unsigned h0, l0, h1, l1;
-      split2(__builtin_shufflevector(v[k], v[k], 0, 1), h0, l0);
-      split2(__builtin_shufflevector(v[k], v[k], 2, 3), h1, l1);
-      u32x4 o;   // word = the value's own pair: low half h, high half l
-      o[0] = __builtin_amdgcn_perm(l0, h0, 0x05040100u);
-      o[1] = __builtin_amdgcn_perm(l0, h0, 0x07060302u);
-      o[2] = __builtin_amdgcn_perm(l1, h1, 0x05040100u);
-      o[3] = __builtin_amdgcn_perm(l1, h1, 0x07060302u);
-      if (k % 3 < 2 || lane < 32) *reinterpret_cast<u32x4*>(buf + w) = o;
-    }
-  };
   if (item < n_items) {
     starts = fetch_starts(p, cur, lane);
-    if constexpr (NCH == 1) {
-      if (part == 0) dma_patch_w(p, cur, starts, pair, lane, patch);
-    } else {
-      if (part == 0) dma_patch_plane(p, cur, (int64_t)NCH * cur.u, starts, pair, lane, patch);
-      starts_cur = starts;
-    }
+    if (L.part == 0) dma_patch_ch0<NCH>(p, cur, starts, L, patch);
+    starts_cur = starts;
     if (item1 < n_items) starts = fetch_starts(p, nx, lane);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (part == 0 && item < n_items) convert_own();
+  if (L.part == 0 && item < n_items) convert_patch(patch, L.pair, lane);
   __syncthreads();
   while (item < n_items) {
     const int next = item1;
     unsigned q_ticket = 0;
     if (threadIdx.x == 0 && p.queue) q_ticket = atomicAdd(p.queue, 1u);
 
-    // ---- (1) conv1_1 + PReLU -> act1 as (h, l): 100 tiles of 16 pixels, tile tt = wave + 8 m ----
-    if constexpr (NCH == 1) {
-      // B = four patch words per lane, each a tap's (h, l) pair as it lies in the patch (K order: conv11_tap)
-      const unsigned* const pv = reinterpret_cast<const unsigned*>(patch) + pov;
-      const unsigned* const ph = reinterpret_cast<const unsigned*>(patch) + poh;
-      // pixel 16 tt + i = (dd = tt / 10, r = 8 (tt % 10) + (i >> 1), col = i & 1): slot 8 tt + 2 (i >> 2) + (i & 1) of the plane
-      // (quarter kk >> 1 [+ 2 for l], parity (i >> 1) & 1); the lane's four channels are bytes 8 (kk & 1) .. + 7 of the slot
-      unsigned* const aw = act + 4 * ((((kk >> 1) * 2 + ((i >> 1) & 1)) * HPLANE) + 8 * wave + 2 * (i >> 2) + (i & 1)) + 2 * (kk & 1);
-      auto tile_group = [&](auto nt_tag, int m0) {
-        constexpr int NT = decltype(nt_tag)::value;
-        u32x4 B[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          const int o = 64 * WPW * (m0 + t);
-          B[t] = (u32x4){pv[o], pv[o + NFRAME * WPW], ph[o], ph[o + 1]};
-          // (a fence per tile: without it the compiler pairs words of DIFFERENT tiles into one read2 and reassembles B with
-          // three v_mov_b32 per tile)
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        f32x4 acc[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W1a), __builtin_bit_cast(f16x8, B[t]), b1v, 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W1b), __builtin_bit_cast(f16x8, B[t]), acc[t], 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          const f32x4 y = prelu4<SLOPE01>(acc[t], sl1v);
-          unsigned h0, l0, h1, l1;
-          split2(__builtin_shufflevector(y, y, 0, 1), h0, l0);
-          split2(__builtin_shufflevector(y, y, 2, 3), h1, l1);
-          *reinterpret_cast<u32x2*>(aw + 4 * 64 * (m0 + t)) = (u32x2){h0, h1};
-          *reinterpret_cast<u32x2*>(aw + 4 * 64 * (m0 + t) + 4 * 4 * HPLANE) = (u32x2){l0, l1};
-        }
-      };
-#pragma unroll
-      for (int m0 = 0; m0 < 12; m0 += 4) tile_group(std::integral_constant<int, 4>{}, m0);
-      if (wave < 4) tile_group(std::integral_constant<int, 1>{}, 12);
-    } else {
-      // channels 1 and 2 of this item -> the act1 tile's first 2 x 30 KB (nobody reads act1 between the last item's final barrier
-      // and this item's epilogue), by the waves that fetch channel 0; they land while channel 0 is multiplied
-      float* const chan12 = reinterpret_cast<float*>(act);
-      if (part == 0) {
-#pragma unroll
-        for (int ch = 1; ch < NCH; ++ch)
-          dma_patch_plane(p, cur, (int64_t)NCH * cur.u + ch, starts_cur, pair, lane, chan12 + (ch - 1) * WP_FLOATS);
-      }
-      unsigned* const aw = act + 4 * ((((kk >> 1) * 2 + ((i >> 1) & 1)) * HPLANE) + 8 * wave + 2 * (i >> 2) + (i & 1)) + 2 * (kk & 1);
-      f32x4 acc[13];   // tile wave + 8 m; m = 12 for waves 0 - 3 only
-      // one channel's K = 32 block (conv11_tap's order) into the accumulators (the bias rides in with channel 0)
-      auto chan_pass = [&](auto first_tag, const unsigned* src, u32x4 WH, u32x4 WL) {
-        auto group = [&](auto nt_tag, auto m0_tag) {
-          constexpr int NT = decltype(nt_tag)::value, M0 = decltype(m0_tag)::value;
-          u32x4 B[NT];
-#pragma unroll
-          for (int t = 0; t < NT; ++t) {
-            const int o = 64 * WPW * (M0 + t);   // the addresses of the one-channel kernel
-            B[t] = (u32x4){src[pov + o], src[pov + o + NFRAME * WPW], src[poh + o], src[poh + o + 1]};
-            __builtin_amdgcn_sched_barrier(0);
-          }
-#pragma unroll
-          for (int t = 0; t < NT; ++t)
-            acc[M0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, WH), __builtin_bit_cast(f16x8, B[t]),
-                                                                 decltype(first_tag)::value ? b1v : acc[M0 + t], 0, 0, 0);
-#pragma unroll
-          for (int t = 0; t < NT; ++t)
-            acc[M0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, WL), __builtin_bit_cast(f16x8, B[t]), acc[M0 + t], 0, 0, 0);
-        };
-        group(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{});
-        group(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{});
-        group(std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});
-        group(std::integral_constant<int, 2>{}, std::integral_constant<int, 6>{});
-        group(std::integral_constant<int, 2>{}, std::integral_constant<int, 8>{});
-        group(std::integral_constant<int, 2>{}, std::integral_constant<int, 10>{});
-        if (wave < 4) group(std::integral_constant<int, 1>{}, std::integral_constant<int, 12>{});
-      };
-      // conv1_1's weight blocks are gathered per item (L1-resident, 16 halves per lane per channel): held across the item loop as
-      // W1a / W1b are in the one-channel kernel, the six blocks and the 13 accumulators spill (256 VGPRs).  The opaque copy of the pointer
-      // keeps the compiler from hoisting the loads out of the loop.
-      const unsigned short* w1blk = reinterpret_cast<const unsigned short*>(p.w1blk);
-      asm volatile("" : "+s"(w1blk));
-      {
-        u32x4 WH, WL;
-        conv11_weights(w1blk, i, kk, WH, WL);
-        chan_pass(std::true_type{}, reinterpret_cast<const unsigned*>(patch), WH, WL);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of channels 1 and 2 have landed
-      if (part == 0) {
-#pragma unroll
-        for (int ch = 1; ch < NCH; ++ch) convert_own_at(chan12 + (ch - 1) * WP_FLOATS);
-      }
-      __syncthreads();   // channels 1 and 2 are in place and converted
-#pragma unroll
-      for (int ch = 1; ch < NCH; ++ch) {
-        u32x4 WH, WL;
-        conv11_weights(w1blk + 2 * ch * 64 * 8, i, kk, WH, WL);
-        chan_pass(std::false_type{}, reinterpret_cast<const unsigned*>(chan12 + (ch - 1) * WP_FLOATS), WH, WL);
-      }
-      __syncthreads();   // every wave has read channels 1 and 2: act1 may be written
-#pragma unroll
-      for (int m = 0; m < 13; ++m) {
-        if (m == 12 && wave >= 4) break;
-        const f32x4 y = prelu4<SLOPE01>(acc[m], sl1v);
-        unsigned h0, l0, h1, l1;
-        split2(__builtin_shufflevector(y, y, 0, 1), h0, l0);
-        split2(__builtin_shufflevector(y, y, 2, 3), h1, l1);
-        *reinterpret_cast<u32x2*>(aw + 4 * 64 * m) = (u32x2){h0, h1};
-        *reinterpret_cast<u32x2*>(aw + 4 * 64 * m + 4 * 4 * HPLANE) = (u32x2){l0, l1};
-      }
-    }
+    // ---- conv1_1 + PReLU -> act1 ----
+    unsigned* const aw = conv11_act_word(act, L);
+    if constexpr (NCH == 1)
+      conv11_one_channel<SLOPE01>(reinterpret_cast<const unsigned*>(patch), pov, poh, aw, L, W1a, W1b, b1v, sl1v);
+    else
+      conv11_three_channels<SLOPE01, NCH>(p, cur, starts_cur, act, patch, pov, poh, aw, L, b1v, sl1v);
     if (threadIdx.x == 0) q_item3 = p.queue ? (int)q_ticket + 3 * (int)gridDim.x : item2 + (int)gridDim.x;
     __syncthreads();   // act1 is complete; the patch buffer is free
     const int item3 = q_item3;
 
-    // ---- (2) conv1_2 + PReLU + pool: 576 positions (depth, row, column) in tiles of 16 ----
-    {
-      if (part == 0 && next < n_items) {
-        if constexpr (NCH == 1) {
-          dma_patch_w(p, nx, starts, pair, lane, patch);
-        } else {
-          dma_patch_plane(p, nx, (int64_t)NCH * nx.u, starts, pair, lane, patch);
-          starts_cur = starts;
-        }
-        if (item2 < n_items) starts = fetch_starts(p, nx2, lane);
-      }
-      const int u = cur.u, q = cur.q(), j = cur.j();
-      float* const obase = p.out + (int64_t)u * S_N + (TD * q) * S_D + j * S_W + 4 * kk;
-      // One stand-alone tile: 16 positions (dq, row, column i & 1), every fragment read by the tile itself (27 reads, 41 MFMAs)
-      auto tile = [&](int dq, int row) {
-        // pixel (dd = dq + kd, r = 2 row + kh, col), channels 8 (kk & 1) .. + 7: slot (((kk & 1) * 2 + (kh & 1)) * 10 + dd) * 80 +
-        // (row + kh / 2) * 2 + col of the h planes; the l planes 4 HPLANE slots on.  The taps of a pair (kd, 2 m), (kd, 2 m + 1)
-        // differ by the parity plane; the pair (0, 8) | (1, 8) by one depth
-        const int base = 16 * (((kk & 1) * 2) * HPLANE + dq * 80 + 2 * row + (i & 1));
-        const char* const a2 = reinterpret_cast<const char*>(act) + base + (kk >= 2 ? 16 * HPLANE : 0);
-        const char* const a3 = reinterpret_cast<const char*>(act) + base + (kk >= 2 ? 16 * 80 : 0);
-        f32x4 acc = b2v;
-        // pair pr: 0 .. 11 = (kd = pr / 4, kh = 2 (pr % 4) | + 1) off a2; 12 = taps (0, 8) | (1, 8) off a3; 13 = the LAST tap (2, 8)
-        // alone, as [h | l] in ONE fragment (lanes kk >= 2 read the l planes): [H | H] x [h | l] + [L | 0] x [h | l] are its three
-        // piece products in two MFMAs and one read, where [h | -] and [l | -] against [H | 0], [L | 0] were three and two
-        auto rd = [&](int pr, int piece) -> u32x4 {
-          const char* ad = pr < 12 ? a2 + 1280 * (pr / 4) + 32 * (pr % 4) : pr == 12 ? a3 + 32 * 4
-                                   : a3 + 2 * 1280 + 32 * 4 + (kk >= 2 ? 16 * 4 * HPLANE - 16 * 80 : 0);
-          return *reinterpret_cast<const u32x4*>(ad + 16 * 4 * HPLANE * piece);
-        };
-        // fragments TWO pairs ahead (three rotating sets): a pair is 48 cycles of MFMA, less than an LDS round trip
-        u32x4 bh[3], bl[3];
-        bh[0] = rd(0, 0);
-        bl[0] = rd(0, 1);
-        bh[1] = rd(1, 0);
-        bl[1] = rd(1, 1);
-#pragma unroll
-        for (int pr = 0; pr < HPAIRS; ++pr) {
-          if (pr + 2 < HPAIRS) {
-            bh[(pr + 2) % 3] = rd(pr + 2, 0);
-            if (pr + 2 < HPAIRS - 1) bl[(pr + 2) % 3] = rd(pr + 2, 1);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W2[pr][0]), __builtin_bit_cast(f16x8, bh[pr % 3]), acc, 0, 0, 0);
-          if (pr < HPAIRS - 1)
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W2[pr][0]), __builtin_bit_cast(f16x8, bl[pr % 3]), acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W2[pr][1]), __builtin_bit_cast(f16x8, bh[pr % 3]), acc, 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        // PReLU, max over the column pair (lanes i, i ^ 1: the same depth and row), the even lane stores its four channels
-        const f32x4 y = prelu4<SLOPE01>(acc, sl2v);
-        f32x4 o;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = max_with_lane_xor1(y[r]);
-        if ((i & 1) == 0) *reinterpret_cast<f32x4*>(obase + dq * S_D + row * S_PAR) = o;
-      };
-      if constexpr (CONV12_CHAINS) {
-        // A DEPTH CHAIN: the fragment of pair (kd, m) of output (dq, row, col) is the act1 slot of (dq + kd, row + m, col) -- it
-        // depends on the input depth dq + kd alone, so a wave that keeps ONE set of 16 (row, col) positions over consecutive
-        // output depths reads the eight fragments (pairs m = 0 .. 3, h and l) of an input depth ONCE and multiplies them into
-        // three live accumulators: kd = 0 of output dd, kd = 1 of dd - 1, kd = 2 of dd - 2.  An output whose kd = 2 step is done
-        // takes pairs 12 and 13 (three reads of its own) and leaves through the epilogue.  Every output receives its 41 MFMAs
-        // in the stand-alone tile's order (kd-major, pairs 0 - 3 inside a kd, then 12, 13) with the same operands: bit-identical.
-        // Eight chains of four output depths, one per wave: rows 8 pt .. 8 pt + 7 (pt = wave & 3) x depth half (wave >> 2), six
-        // input depths, 6 x 8 + 4 x 3 = 60 reads for 164 MFMAs.  Rows 32 - 35 (64 positions) are four stand-alone tiles of two
-        // depths each on the YOUNGER waves (the older ones fetch and convert the next patch): 588 reads per item, not 972.
-        {
-          const int row = 8 * pair + (i >> 1), d0 = 4 * part;
-          const int base = 16 * (((kk & 1) * 2) * HPLANE + d0 * 80 + 2 * row + (i & 1));
-          const char* const a2 = reinterpret_cast<const char*>(act) + base + (kk >= 2 ? 16 * HPLANE : 0);
-          const char* const a3 = reinterpret_cast<const char*>(act) + base + (kk >= 2 ? 16 * 80 : 0);
-          const char* const a13 = a3 + (kk >= 2 ? 16 * 4 * HPLANE - 16 * 80 : 0);
-          // unit n of the chain's 32 (conv12_unit_step / _sub): the four pairs of input depth s, behind them (s >= 2) pairs 12
-          // and 13 of output s - 2.  Fragments TWO units ahead, three rotating sets, as in the stand-alone tile
-          auto rd = [&](int n, int piece) -> u32x4 {
-            const int s = conv12_unit_step(n), e = conv12_unit_sub(n);
-            const char* ad = e < 4 ? a2 + 1280 * s + 32 * e : e == 4 ? a3 + 1280 * (s - 2) + 32 * 4 : a13 + 1280 * s + 32 * 4;
-            return *reinterpret_cast<const u32x4*>(ad + 16 * 4 * HPLANE * piece);
-          };
-          auto mfma3 = [&](f32x4 c, int pr, u32x4 h, u32x4 l) -> f32x4 {
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W2[pr][0]), __builtin_bit_cast(f16x8, h), c, 0, 0, 0);
-            if (pr < HPAIRS - 1)
-              c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W2[pr][0]), __builtin_bit_cast(f16x8, l), c, 0, 0, 0);
-            return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W2[pr][1]), __builtin_bit_cast(f16x8, h), c, 0, 0, 0);
-          };
-          f32x4 acc[CONV12_CHAIN];
-          u32x4 bh[3], bl[3];
-          bh[0] = rd(0, 0);
-          bl[0] = rd(0, 1);
-          bh[1] = rd(1, 0);
-          bl[1] = rd(1, 1);
-#pragma unroll
-          for (int n = 0; n < CONV12_UNITS; ++n) {
-            if (n + 2 < CONV12_UNITS) {
-              bh[(n + 2) % 3] = rd(n + 2, 0);
-              if (conv12_unit_sub(n + 2) != 5) bl[(n + 2) % 3] = rd(n + 2, 1);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            const int s = conv12_unit_step(n), e = conv12_unit_sub(n);
-            if (e < 4) {
-#pragma unroll
-              for (int kd = 0; kd < 3; ++kd) {
-                const int o = s - kd;
-                if (o >= 0 && o < CONV12_CHAIN) acc[o] = mfma3(kd == 0 && e == 0 ? b2v : acc[o], 4 * kd + e, bh[n % 3], bl[n % 3]);
-              }
-            } else {
-              const int o = s - 2;
-              acc[o] = mfma3(acc[o], 8 + e, bh[n % 3], bl[n % 3]);
-              if (e == 5) {
-                const f32x4 y = prelu4<SLOPE01>(acc[o], sl2v);
-                f32x4 v;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = max_with_lane_xor1(y[r]);
-                if ((i & 1) == 0) *reinterpret_cast<f32x4*>(obase + (d0 + o) * S_D + row * S_PAR) = v;
-              }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-        if (part) tile(2 * pair + (i >> 3), 32 + ((i >> 1) & 3));
-      } else {
-        // tiles t = wave + 8 m (m < 4) of positions P = 16 t + i -> (depth P / 72, row, column); the last four go to the YOUNGER
-        // waves (the older ones fetch and convert the next patch)
+    // ---- the next item's patch (it lands inside this item's conv1_2), the crop starts of the one after ----
+    if (L.part == 0 && next < n_items) {
+      dma_patch_ch0<NCH>(p, nx, starts, L, patch);
+      starts_cur = starts;
+      if (item2 < n_items) starts = fetch_starts(p, nx2, lane);
+    }
+    // ---- conv1_2 + PReLU + pool -> out ----
+    float* const obase = p.out + (int64_t)cur.u * S_N + (TD * cur.q()) * S_D + cur.j() * S_W + 4 * L.kk;
+    if constexpr (CONV12_CHAINS) {
+      conv12_chain<SLOPE01>(act, W2, b2v, sl2v, obase, L);
+      if (L.part) conv12_tile<SLOPE01>(act, W2, b2v, sl2v, obase, 2 * L.pair + (L.i >> 3), 32 + ((L.i >> 1) & 3), L);
+    } else {
+      // tiles t = wave + 8 m (m < 4) of positions P = 16 t + i -> (depth P / 72, row, column); the last four go to the YOUNGER
+      // waves (the older ones fetch and convert the next patch)
 #pragma unroll 1
-        for (int m = 0; m < 4 + part; ++m) {
-          const int t = m < 4 ? wave + 8 * m : 28 + wave;
-          const int P = 16 * t + i;
-          const int dq = (P * 911) >> 16, rem = P - 72 * dq;          // P / 72 for P < 576
-          tile(dq, rem >> 1);
-        }
+      for (int m = 0; m < 4 + L.part; ++m) {
+        const int t = m < 4 ? wave + 8 * m : 28 + wave;
+        const int P = 16 * t + L.i;
+        const int dq = (P * 911) >> 16, rem = P - 72 * dq;          // P / 72 for P < 576
+        conv12_tile<SLOPE01>(act, W2, b2v, sl2v, obase, dq, rem >> 1, L);
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces have landed
-    if (part == 0 && next < n_items) convert_own();
+    if (L.part == 0 && next < n_items) convert_patch(patch, L.pair, lane);
     __syncthreads();  // the next patch is in place and converted; act1 may be overwritten
     item = item1;
     item1 = item2;
@@ -648,6 +620,17 @@ int svk_c3d2_stage1_c3(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t
 // =====================================================================================================
 namespace {
 
+// What every kernel below takes; each kernel's header comment gives its `in`, `wblk` and `out` layouts
+struct ConvParams {
+  const float* in;
+  const u32x4* wblk;    // weight blocks [..][2: H | L][64 lanes] of eight halves
+  const float* bias;    // [output channels]
+  const float* slope;   // [output channels]
+  float* out;
+  int32_t n_utt;
+  unsigned* queue;      // work-item counter (zeroed before the launch), or NULL: items at a fixed stride
+};
+
 constexpr int S2_D = 16, S2_H = 36, S2_W = 18;       // input of conv2_1 (after pool1), 16 channels
 constexpr int A2_D = 14, A2_W = 14;                  // conv2_1 output (32 channels), rows = S2_H.  The layer has 15 columns; pool2 drops
                                                      // conv2_2's 15th, which is all that reads conv2_1's 15th (kernel width 1): never computed
@@ -658,23 +641,15 @@ constexpr int O2_D = 12, O2_H = 15, O2_W = 7;        // after conv2_2 + pool2 (3
 // rows) as before; its input [16 d][4 rows][18 w][16 c] is split into (h, l) while it is staged and lies in LDS as four planes
 // of 16-byte slots (h c0-7, h c8-15, l c0-7, l c8-15), slot = pixel (d * 4 + row) * 18 + col: the 16 positions of a tile --
 // ANY 16 consecutive outputs of the item's 14 d x 4 rows x 14 columns = 784 = 49 full tiles -- read consecutive slots (+ 4 across a
-// row end).  36 MFMAs of 16 cycles per tile where the depth-transformed f32 kernel issued 128 of 32 per 16 positions of a pair. ----
+// row end).  36 MFMAs of 16 cycles per tile where the depth-transformed f32 kernel issued 128 of 32 per 16 positions of a pair.
+//   in   [n][16][36][18][16]          out  [n][14][36][14][32]
+//   wblk [2 nt][6 pairs][2][64]: lane (co = 16 nt + (l & 15), kk): e: W[co][8 (kk & 1) + e][kd][kw + (kk >= 2)], pair = 2 kd + kw / 2 ----
 constexpr int C21H_PIX = S2_D * 4 * S2_W;            // 1 152 pixels = slots per plane
 constexpr int C21H_LDS_WORDS = 4 * 4 * C21H_PIX;     // four planes of 16-byte slots: 73 728 bytes
 constexpr int C21H_POS = A2_D * 4 * A2_W;            // 784 output positions per item
 
-struct Conv21hParams {
-  const float* in;      // [n][16][36][18][16]
-  const u32x4* wblk;    // [2 nt][6 pairs][2][64]: lane (co = 16 nt + (l & 15), kk): e: W[co][8 (kk & 1) + e][kd][kw + (kk >= 2)], pair = 2 kd + kw / 2; H | L
-  const float* bias;    // [32]
-  const float* slope;   // [32]
-  float* out;           // [n][14][36][14][32]
-  int32_t n_utt;
-  unsigned* queue;
-};
-
 template <bool SLOPE01>
-__global__ __launch_bounds__(256, 2) void c3d2_conv21h_kernel(const Conv21hParams p) {
+__global__ __launch_bounds__(256, 2) void c3d2_conv21h_kernel(const ConvParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem_c21w[];
   unsigned* const reg = reinterpret_cast<unsigned*>(smem_c21w);
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -747,6 +722,8 @@ __global__ __launch_bounds__(256, 2) void c3d2_conv21h_kernel(const Conv21hParam
           bl[(pr + 2) % 3] = rd(pr + 2, 1);
         }
         __builtin_amdgcn_sched_barrier(0);
+        // (written out, not mfma_pieces: through the helper the prologue's bias and slope loads come out in another order and the
+        // kernel measured 1.6 % slower, the two builds alternated three times: 0.2936 - 0.2957 -> 0.2993 - 0.2999 ms per 1 024 cubes)
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
           acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[nt][pr][0]), __builtin_bit_cast(f16x8, bh[pr % 3]), acc[nt], 0, 0, 0);
@@ -770,7 +747,9 @@ __global__ __launch_bounds__(256, 2) void c3d2_conv21h_kernel(const Conv21hParam
 // split by the parity of the row (rows are 2 apart along a tile): slot ((r & 1) * 6 + d) * 46 + (r >> 1) * 2 + col.  The item's
 // 4 d x 15 rows x 2 columns = 120 positions; wave = (N tile nt, plane tile: 16 of a depth's 30 positions) walks the four output depths
 // as a depth chain (below): the 48 weight blocks of an N tile are 192 VGPRs.  Pool = max over adjacent lanes (the column pair),
-// the even lane stores four channels. ----
+// the even lane stores four channels.
+//   in   [n][14][36][14][32]          out  [n][12][15][7][32]
+//   wblk [2 nt][24 taps][2][64]: lane (co = 16 nt + (l & 15), kk): e: W[co][8 kk + e][kd][kh], tap = 8 kd + kh ----
 // Depth pitch 46, not 36, comes from the tiles of 16 consecutive positions that ran on from one depth's 30 to the next (46 = 30
 // (mod 16): their slots mod 16 ran on too); a plane tile's sixteen slots are consecutive at any pitch, and the layout is kept as it was
 constexpr int C22H_DP = 46;
@@ -778,18 +757,8 @@ constexpr int C22H_PLANE = 560;                      // 2 * 6 * 46 = 552 slots p
 constexpr int C22H_LDS_WORDS = 4 * 8 * C22H_PLANE;   // 71 680 bytes
 constexpr int C22H_POS = 4 * O2_H * 2;               // 120 positions per item
 
-struct Conv22hParams {
-  const float* in;      // [n][14][36][14][32]
-  const u32x4* wblk;    // [2 nt][24 taps][2][64]: lane (co = 16 nt + (l & 15), kk): e: W[co][8 kk + e][kd][kh], tap = 8 kd + kh; H | L
-  const float* bias;    // [32]
-  const float* slope;   // [32]
-  float* out;           // [n][12][15][7][32]
-  int32_t n_utt;
-  unsigned* queue;
-};
-
 template <bool SLOPE01>
-__global__ __launch_bounds__(256, 2) void c3d2_conv22h_kernel(const Conv22hParams p) {
+__global__ __launch_bounds__(256, 2) void c3d2_conv22h_kernel(const ConvParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem_c22w[];
   unsigned* const reg = reinterpret_cast<unsigned*>(smem_c22w);
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -874,19 +843,10 @@ __global__ __launch_bounds__(256, 2) void c3d2_conv22h_kernel(const Conv22hParam
 #pragma unroll
         for (int kd = 0; kd < 3; ++kd) {
           const int o = s - kd, tap = 8 * kd + kh;
-          if (o >= 0 && o < 4) {
-            acc[o] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[tap][0]), __builtin_bit_cast(f16x8, bh[n % 3]), tap == 0 ? b4 : acc[o], 0, 0, 0);
-            acc[o] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[tap][0]), __builtin_bit_cast(f16x8, bl[n % 3]), acc[o], 0, 0, 0);
-            acc[o] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, W[tap][1]), __builtin_bit_cast(f16x8, bh[n % 3]), acc[o], 0, 0, 0);
-          }
+          if (o >= 0 && o < 4) acc[o] = mfma_pieces(W[tap][0], W[tap][1], bh[n % 3], bl[n % 3], tap == 0 ? b4 : acc[o]);
         }
-        if (kh == 7 && s >= 2) {
-          const f32x4 y = prelu4<SLOPE01>(acc[s - 2], sl4);
-          f32x4 v;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = max_with_lane_xor1(y[r]);
-          if ((i & 1) == 0 && 16 * half + i < 2 * O2_H) *reinterpret_cast<f32x4*>(obase + (s - 2) * (O2_H * O2_W * 32)) = v;
-        }
+        if (kh == 7 && s >= 2)
+          prelu_pool_store<SLOPE01>(acc[s - 2], sl4, obase + (s - 2) * (O2_H * O2_W * 32), (i & 1) == 0 && 16 * half + i < 2 * O2_H);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -900,34 +860,22 @@ __global__ __launch_bounds__(256, 2) void c3d2_conv22h_kernel(const Conv22hParam
 // rows): region 12 depths x 3 rows x 7 columns of 32 channels, split into (h, l) while staged: eight planes (four channel quarters
 // x {h, l}) of 16-byte slots, slot = pixel (d * 3 + row) * 7 + col (32 KB; three workgroups per CU).  The item's 10 d x 3 rows x
 // 5 columns = 150 positions are 9.4 tiles of 16 consecutive positions; wave = N tile (16 of the 64 output channels: 18 weight
-// blocks = 72 VGPRs), every wave walks all ten tiles.  Output chunked and column-major, 16-byte stores. ----
+// blocks = 72 VGPRs), every wave walks all ten tiles.  Output chunked and column-major, 16-byte stores.
+//   in   [n][12][15][7][32]           out  [n][10][8 chunks][5 w][15 h][8] (what svk_c3d2_conv32t stages)
+//   wblk [4 nt][9 taps][2][64]: lane (co = 16 nt + (l & 15), kk): e: W[co][8 kk + e][kd][kw], tap = 3 kd + kw ----
 constexpr int C31H_PLANE = 256;                               // 12 * 3 * 7 = 252 slots per plane, padded to a multiple of 16: the lanes of an LDS
                                                               // lane group sit in different planes (kk) and must not land on each other's slots
 constexpr int C31H_LDS_WORDS = 4 * 8 * C31H_PLANE;            // 32 768 bytes
 constexpr int C31H_POS = 10 * 3 * 5;                          // 150 positions per item
 
-struct Conv31Params {
-  const float* in;      // [n][12][15][7][32]
-  const u32x4* wblk;    // [4 nt][9 taps][2][64]: lane (co = 16 nt + (l & 15), kk): e: W[co][8 kk + e][kd][kw], tap = 3 kd + kw; H | L
-  const float* bias;    // [64]
-  const float* slope;   // [64]
-  float* out;           // chunked and column-major: [n][10][8 chunks][5 w][15 h][8] (what svk_c3d2_conv32t stages)
-  int32_t n_utt;
-  unsigned* queue;      // work-item counter (zeroed before the launch), or NULL
-};
-
 template <bool SLOPE01>
-__global__ __launch_bounds__(256, 3) void c3d2_conv31h_kernel(const Conv31Params p) {
+__global__ __launch_bounds__(256, 3) void c3d2_conv31h_kernel(const ConvParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem_c31[];
   unsigned* const reg = reinterpret_cast<unsigned*>(smem_c31);
   const int lane = threadIdx.x & 63, nt = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int i = lane & 15, kk = lane >> 4;
   u32x4 W[9][2];
-#pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    W[t][0] = p.wblk[((nt * 9 + t) * 2) * 64 + lane];
-    W[t][1] = p.wblk[((nt * 9 + t) * 2 + 1) * 64 + lane];
-  }
+  load_wblk(p.wblk, nt * 9, lane, W);
   f32x4 b4, sl4;   // channels 16 nt + 4 kk .. + 3 of ONE position
   load_bias_slope(p.bias, p.slope, nt, kk, b4, sl4);
   const int n_items = p.n_utt * 5;
@@ -1008,7 +956,9 @@ __global__ __launch_bounds__(256, 3) void c3d2_conv31h_kernel(const Conv31Params
 // weight blocks of an N tile and ONE K block are 168 VGPRs: wave = (N tile nt, K block kb), eight waves; the two waves of an N tile
 // swap partial sums through LDS (kb 0 finishes tiles 0 - 2, kb 1 tiles 3 - 4).  The next item's runs are loaded into registers in
 // front of the tiles and parked behind them: one workgroup per CU, its memory latency under its own matrix work.
-// (As an instance of c3d2_tail.hip's f32 batch-GEMM kernel when that was a template, Winograd F(2,3) along depth: 1.34 - 1.62 ms per 4 018 cubes.) ----
+// (As an instance of c3d2_tail.hip's f32 batch-GEMM kernel when that was a template, Winograd F(2,3) along depth: 1.34 - 1.62 ms per 4 018 cubes.)
+//   in   [n][10][8 chunks][5 w][15 h][8]          out  [n][8 d][8 chunks][45 = 9 h x 5 w][8]
+//   wblk [4 nt][2 kb][21 taps][2][64]: lane (co = 16 nt + (l & 15), kk): e: W[co][32 kb + 8 kk + e][kd][kh], tap = 7 kd + kh ----
 // depth pitch 25, not 15: a tile's positions run on from one depth's 9 rows to the next, and with 25 = 9 (mod 16) so do their slots
 // mod 16 (see C22H_DP)
 constexpr int C32H_DP = 25;
@@ -1017,18 +967,8 @@ constexpr int C32H_LDS_WORDS = 4 * 16 * C32H_PLANE;           // 65 536 bytes
 constexpr int C32H_XCH_FLOATS = 8 * 5 * 64 * 4;               // [wave = nt + 4 kb][tile][lane] f32x4: every wave's partial sums
 constexpr int C32H_POS = 8 * 9;                               // 72 positions per item
 
-struct Conv32hParams {
-  const float* in;      // [n][10][8 chunks][5 w][15 h][8]
-  const u32x4* wblk;    // [4 nt][2 kb][21 taps][2][64]: lane (co = 16 nt + (l & 15), kk): e: W[co][32 kb + 8 kk + e][kd][kh], tap = 7 kd + kh; H | L
-  const float* bias;    // [64]
-  const float* slope;   // [64]
-  float* out;           // [n][8 d][8 chunks][45 = 9 h x 5 w][8]
-  int32_t n_utt;
-  unsigned* queue;
-};
-
 template <bool SLOPE01>
-__global__ __launch_bounds__(512) void c3d2_conv32h_kernel(const Conv32hParams p) {
+__global__ __launch_bounds__(512) void c3d2_conv32h_kernel(const ConvParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem_c32[];
   unsigned* const reg = reinterpret_cast<unsigned*>(smem_c32);
   float* const xch = smem_c32 + C32H_LDS_WORDS;
@@ -1036,11 +976,7 @@ __global__ __launch_bounds__(512) void c3d2_conv32h_kernel(const Conv32hParams p
   const int i = lane & 15, kk = lane >> 4;
   const int nt = wave & 3, kb = wave >> 2;
   u32x4 W[21][2];
-#pragma unroll
-  for (int t = 0; t < 21; ++t) {
-    W[t][0] = p.wblk[(((nt * 2 + kb) * 21 + t) * 2) * 64 + lane];
-    W[t][1] = p.wblk[(((nt * 2 + kb) * 21 + t) * 2 + 1) * 64 + lane];
-  }
+  load_wblk(p.wblk, (nt * 2 + kb) * 21, lane, W);
   f32x4 b4, sl4;   // channels 16 nt + 4 kk .. + 3 of ONE position (the bias rides in K block 0's accumulators)
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -1140,7 +1076,9 @@ __global__ __launch_bounds__(512) void c3d2_conv32h_kernel(const Conv32hParams p
 // while staged into sixteen planes (eight channel chunks x {h, l}) of 16-byte slots, slot = d * 59 + 9 w + h; outputs 6 d x 9 h x 3 w =
 // 162 positions = 10.1 tiles; wave = N tile (eight waves: 128 output channels; 36 weight blocks = 144 VGPRs), every wave walks all
 // eleven tiles.  The next cube is loaded into registers in front of the tiles and parked behind them.
-// (As an instance of c3d2_tail.hip's f32 batch-GEMM kernel when that was a template, Winograd F(2,3) along depth: 0.54 - 0.69 ms per 4 018 cubes.) ----
+// (As an instance of c3d2_tail.hip's f32 batch-GEMM kernel when that was a template, Winograd F(2,3) along depth: 0.54 - 0.69 ms per 4 018 cubes.)
+//   in   [n][8][8 chunks][45][8]                  out  [n][6 d][16 chunks][27 = 9 h x 3 w][8]
+//   wblk [8 nt][9 taps][2 kb][2][64]: lane (co = 16 nt + (l & 15), kk): e: W[co][32 kb + 8 kk + e][kd][kw], tap = 3 kd + kw ----
 // A plane holds [8 d][5 w][9 h] at depth pitch 59: positions are walked (depth, column, row) with the row fastest, 27 per depth, and
 // 59 = 27 (mod 16), so sixteen consecutive positions are sixteen consecutive slots mod 16 at every tap (see C22H_DP)
 constexpr int C41H_DP = 59;
@@ -1149,36 +1087,17 @@ constexpr int C41H_LDS_WORDS = 4 * 16 * C41H_PLANE;           // 122 880 bytes
 constexpr int C41H_POS = 6 * 9 * 3;                           // 162 positions per cube
 constexpr int C41H_PIECES = 8 * 8 * 45 * 2;                   // 5 760 sixteen-byte pieces per cube
 
-struct Conv41hParams {
-  const float* in;      // [n][8][8 chunks][45][8]
-  const u32x4* wblk;    // [8 nt][9 taps][2 kb][2][64]: lane (co = 16 nt + (l & 15), kk): e: W[co][32 kb + 8 kk + e][kd][kw], tap = 3 kd + kw; H | L
-  const float* bias;    // [128]
-  const float* slope;   // [128]
-  float* out;           // [n][6 d][16 chunks][27 = 9 h x 3 w][8]
-  int32_t n_utt;
-  unsigned* queue;
-};
-
 template <bool SLOPE01>
-__global__ __launch_bounds__(512) void c3d2_conv41h_kernel(const Conv41hParams p) {
+__global__ __launch_bounds__(512) void c3d2_conv41h_kernel(const ConvParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem_c41[];
   unsigned* const reg = reinterpret_cast<unsigned*>(smem_c41);
   const int lane = threadIdx.x & 63, nt = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int i = lane & 15, kk = lane >> 4;
-  u32x4 W[9][2][2];
+  u32x4 W[9][2][2];   // [tap][kb][H | L]
 #pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      W[t][kb][0] = p.wblk[(((nt * 9 + t) * 2 + kb) * 2) * 64 + lane];
-      W[t][kb][1] = p.wblk[(((nt * 9 + t) * 2 + kb) * 2 + 1) * 64 + lane];
-    }
+  for (int t = 0; t < 9; ++t) load_wblk(p.wblk, (nt * 9 + t) * 2, lane, W[t]);
   f32x4 b4, sl4;   // channels 16 nt + 4 kk .. + 3 of ONE position
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    b4[r] = p.bias[16 * nt + 4 * kk + r];
-    sl4[r] = p.slope[16 * nt + 4 * kk + r];
-  }
+  load_bias_slope(p.bias, p.slope, nt, kk, b4, sl4);
   const int n_items = p.n_utt;
   __shared__ int q_next;
   // piece e = t + 512 k (twelve per thread, 5 760 in all): run e / 90 = d * 8 + chunk, pixel (e % 90) / 2, channels 4 (e & 1) .. + 3
@@ -1253,10 +1172,10 @@ __global__ __launch_bounds__(512) void c3d2_conv41h_kernel(const Conv41hParams p
 // The launch of one persistent two-piece kernel (conv2_1 .. conv4_1): `p` with its work-item counter (from svk_work_queue, which the
 // entry point has already called: a NULL queue = items at a fixed stride), the kernel of the pair that flags bit 1 selects, at most
 // max_per_cu workgroups of `threads` per CU.  `name` is what the entry point's errors call the launch.
-template <class P>
-int launch_conv(svk_ctx* ctx, const char* name, void (*kern_slope01)(const P), void (*kern_any)(const P), int32_t flags, P p,
-                size_t lds, int threads, int max_per_cu, int64_t items, unsigned* queue) {
-  void (*kern)(const P) = (flags & 2) ? kern_slope01 : kern_any;
+using ConvKernel = void (*)(const ConvParams);
+int launch_conv(svk_ctx* ctx, const char* name, ConvKernel kern_slope01, ConvKernel kern_any, int32_t flags, ConvParams p, size_t lds,
+                int threads, int max_per_cu, int64_t items, unsigned* queue) {
+  const ConvKernel kern = (flags & 2) ? kern_slope01 : kern_any;
   p.queue = queue;
   unsigned grid;
   if (int rc = svk_persistent_grid(ctx, name, kern, lds, threads, max_per_cu, items, &grid)) return rc;
@@ -1265,80 +1184,86 @@ int launch_conv(svk_ctx* ctx, const char* name, void (*kern_slope01)(const P), v
   return SVK_OK;
 }
 
+// The argument checks of svk_c3d2_stage2 .. svk_c3d2_conv41, in the order their errors are documented: the handle, n_utt, the
+// flags, [nothing to do: n_utt = 0], NULL buffers (`all_set`), 16-byte alignment (`addr_bits`: the buffers' addresses or-ed) and
+// the item index staying an int32: per_cube items per cube + the `ahead` grids of one workgroup per CU a ticket is drawn ahead.
+// -> SVK_OK with *launch = whether there is anything to launch
+int conv_checks(svk_ctx* ctx, int32_t n_utt, int32_t flags, bool all_set, uintptr_t addr_bits, int per_cube, int ahead, bool* launch) {
+  *launch = false;
+  if (!ctx) return SVK_ERR_BAD_ARG;
+  SVK_REQUIRE(ctx, n_utt >= 0, "n_utt negative");
+  SVK_REQUIRE(ctx, (flags & ~2) == 0, "flags: only bit 1 (slopes in [0, 1]) is defined");
+  if (n_utt == 0) return SVK_OK;
+  SVK_REQUIRE(ctx, all_set, "NULL buffer");
+  SVK_REQUIRE(ctx, (addr_bits & 15) == 0, "buffers must be 16-byte aligned");
+  SVK_REQUIRE(ctx, (int64_t)n_utt * per_cube + ahead * (int64_t)ctx->num_cu < ((int64_t)1 << 31), "too many cubes for one launch");
+  *launch = true;
+  return SVK_OK;
+}
+
+// What differs between the one-layer entry points, and their common body
+struct ConvEntry {
+  const char* name;
+  ConvKernel kern_slope01, kern_any;
+  size_t lds;
+  int threads, max_per_cu;
+  int per_cube;   // work items per cube
+  size_t slot;    // the kernel's work-item counter in the handle's scratch
+  int ahead;      // grids its tickets are drawn ahead beyond the first (bounds the item index)
+};
+int conv_entry(svk_ctx* ctx, const ConvEntry& e, const float* d_in, int32_t n_utt, const void* d_wblk, const float* d_bias,
+               const float* d_slope, int32_t flags, float* d_out) {
+  bool launch;
+  const uintptr_t addr_bits = reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_wblk) | reinterpret_cast<uintptr_t>(d_out);
+  if (int rc = conv_checks(ctx, n_utt, flags, d_in && d_wblk && d_bias && d_slope && d_out, addr_bits, e.per_cube, e.ahead, &launch)) return rc;
+  if (!launch) return SVK_OK;
+  const ConvParams p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, nullptr};
+  unsigned* queue;
+  if (int rc = svk_work_queue(ctx, e.slot, 1, &queue)) return rc;
+  return launch_conv(ctx, e.name, e.kern_slope01, e.kern_any, flags, p, e.lds, e.threads, e.max_per_cu, (int64_t)n_utt * e.per_cube, queue);
+}
+
 }  // namespace
 
 extern "C" int svk_c3d2_stage2(svk_ctx* ctx, const float* d_in, int32_t n_utt, const void* d_w21blk,
                                const float* d_bias21, const float* d_slope21, const void* d_w22blk,
                                const float* d_bias22, const float* d_slope22, int32_t flags, float* d_act2, float* d_out) {
-  if (!ctx) return SVK_ERR_BAD_ARG;
-  SVK_REQUIRE(ctx, n_utt >= 0, "n_utt negative");
-  SVK_REQUIRE(ctx, (flags & ~2) == 0, "flags: only bit 1 (slopes in [0, 1]) is defined");
-  if (n_utt == 0) return SVK_OK;
-  SVK_REQUIRE(ctx, d_in && d_w21blk && d_bias21 && d_slope21 && d_w22blk && d_bias22 && d_slope22 && d_act2 && d_out,
-              "NULL buffer");
-  SVK_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_act2) |
-                     reinterpret_cast<uintptr_t>(d_w21blk) | reinterpret_cast<uintptr_t>(d_w22blk) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
-              "buffers must be 16-byte aligned");
-  SVK_REQUIRE(ctx, (int64_t)n_utt * 21 < ((int64_t)1 << 31), "too many cubes for one launch");
+  bool launch;
+  const uintptr_t addr_bits = reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_act2) | reinterpret_cast<uintptr_t>(d_w21blk) |
+                              reinterpret_cast<uintptr_t>(d_w22blk) | reinterpret_cast<uintptr_t>(d_out);
+  if (int rc = conv_checks(ctx, n_utt, flags, d_in && d_w21blk && d_bias21 && d_slope21 && d_w22blk && d_bias22 && d_slope22 && d_act2 && d_out,
+                           addr_bits, 21, 0, &launch))
+    return rc;
+  if (!launch) return SVK_OK;
   // conv2_1 and conv2_2 share a CU between workgroups: as many as the occupancy calculator allows
   unsigned* queues;
   if (int rc = svk_work_queue(ctx, SVK_SLOT_STAGE2, 2, &queues)) return rc;
-  const Conv21hParams p21{d_in, reinterpret_cast<const u32x4*>(d_w21blk), d_bias21, d_slope21, d_act2, n_utt, nullptr};
+  const ConvParams p21{d_in, reinterpret_cast<const u32x4*>(d_w21blk), d_bias21, d_slope21, d_act2, n_utt, nullptr};
   if (int rc = launch_conv(ctx, "svk_c3d2_stage2 (conv2_1)", c3d2_conv21h_kernel<true>, c3d2_conv21h_kernel<false>, flags, p21,
                            sizeof(unsigned) * (size_t)C21H_LDS_WORDS, 256, INT_MAX, (int64_t)n_utt * (S2_H / 4), queues))
     return rc;
-  const Conv22hParams p22{d_act2, reinterpret_cast<const u32x4*>(d_w22blk), d_bias22, d_slope22, d_out, n_utt, nullptr};
+  const ConvParams p22{d_act2, reinterpret_cast<const u32x4*>(d_w22blk), d_bias22, d_slope22, d_out, n_utt, nullptr};
   return launch_conv(ctx, "svk_c3d2_stage2 (conv2_2)", c3d2_conv22h_kernel<true>, c3d2_conv22h_kernel<false>, flags, p22,
                      sizeof(unsigned) * (size_t)C22H_LDS_WORDS, 256, INT_MAX, (int64_t)n_utt * 21, queues ? queues + 1 : nullptr);
 }
 
 extern "C" int svk_c3d2_conv31(svk_ctx* ctx, const float* d_in, int32_t n_utt, const void* d_wblk, const float* d_bias,
                                const float* d_slope, int32_t flags, float* d_out) {
-  if (!ctx) return SVK_ERR_BAD_ARG;
-  SVK_REQUIRE(ctx, n_utt >= 0, "n_utt negative");
-  SVK_REQUIRE(ctx, (flags & ~2) == 0, "flags: only bit 1 (slopes in [0, 1]) is defined");
-  if (n_utt == 0) return SVK_OK;
-  SVK_REQUIRE(ctx, d_in && d_wblk && d_bias && d_slope && d_out, "NULL buffer");
-  SVK_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_wblk) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
-              "buffers must be 16-byte aligned");
-  SVK_REQUIRE(ctx, (int64_t)n_utt * 5 < ((int64_t)1 << 31), "too many cubes for one launch");
-  const Conv31Params p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, nullptr};
-  unsigned* queue;
-  if (int rc = svk_work_queue(ctx, SVK_SLOT_CONV31, 1, &queue)) return rc;
-  return launch_conv(ctx, "svk_c3d2_conv31", c3d2_conv31h_kernel<true>, c3d2_conv31h_kernel<false>, flags, p,
-                     sizeof(unsigned) * (size_t)C31H_LDS_WORDS, 256, INT_MAX, (int64_t)n_utt * 5, queue);
+  static const ConvEntry e{"svk_c3d2_conv31", c3d2_conv31h_kernel<true>, c3d2_conv31h_kernel<false>, sizeof(unsigned) * (size_t)C31H_LDS_WORDS,
+                           256, INT_MAX, 5, SVK_SLOT_CONV31, 0};
+  return conv_entry(ctx, e, d_in, n_utt, d_wblk, d_bias, d_slope, flags, d_out);
 }
 
 extern "C" int svk_c3d2_conv32t(svk_ctx* ctx, const float* d_in, int32_t n_utt, const void* d_wblk, const float* d_bias,
                                 const float* d_slope, int32_t flags, float* d_out) {
-  if (!ctx) return SVK_ERR_BAD_ARG;
-  SVK_REQUIRE(ctx, n_utt >= 0, "n_utt negative");
-  SVK_REQUIRE(ctx, (flags & ~2) == 0, "flags: only bit 1 (slopes in [0, 1]) is defined");
-  if (n_utt == 0) return SVK_OK;
-  SVK_REQUIRE(ctx, d_in && d_wblk && d_bias && d_slope && d_out, "NULL buffer");
-  SVK_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_wblk) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
-              "buffers must be 16-byte aligned");
-  SVK_REQUIRE(ctx, (int64_t)n_utt * 5 + 2 * (int64_t)ctx->num_cu < ((int64_t)1 << 31), "too many cubes for one launch");
-  const Conv32hParams p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, nullptr};
-  unsigned* queue;
-  if (int rc = svk_work_queue(ctx, SVK_SLOT_CONV32, 1, &queue)) return rc;
-  return launch_conv(ctx, "svk_c3d2_conv32t", c3d2_conv32h_kernel<true>, c3d2_conv32h_kernel<false>, flags, p,
-                     sizeof(float) * (size_t)(C32H_LDS_WORDS + C32H_XCH_FLOATS), 512, 1, (int64_t)n_utt * 5, queue);
+  static const ConvEntry e{"svk_c3d2_conv32t", c3d2_conv32h_kernel<true>, c3d2_conv32h_kernel<false>,
+                           sizeof(float) * (size_t)(C32H_LDS_WORDS + C32H_XCH_FLOATS), 512, 1, 5, SVK_SLOT_CONV32, 2};
+  return conv_entry(ctx, e, d_in, n_utt, d_wblk, d_bias, d_slope, flags, d_out);
 }
 
 extern "C" int svk_c3d2_conv41(svk_ctx* ctx, const float* d_in, int32_t n_utt, const void* d_wblk, const float* d_bias,
                                const float* d_slope, int32_t flags, float* d_out) {
-  if (!ctx) return SVK_ERR_BAD_ARG;
-  SVK_REQUIRE(ctx, n_utt >= 0, "n_utt negative");
-  SVK_REQUIRE(ctx, (flags & ~2) == 0, "flags: only bit 1 (slopes in [0, 1]) is defined");
-  if (n_utt == 0) return SVK_OK;
-  SVK_REQUIRE(ctx, d_in && d_wblk && d_bias && d_slope && d_out, "NULL buffer");
-  SVK_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_wblk) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
-              "buffers must be 16-byte aligned");
-  SVK_REQUIRE(ctx, (int64_t)n_utt + 2 * (int64_t)ctx->num_cu < ((int64_t)1 << 31), "too many cubes for one launch");
-  const Conv41hParams p{d_in, reinterpret_cast<const u32x4*>(d_wblk), d_bias, d_slope, d_out, n_utt, nullptr};
-  unsigned* queue;
-  if (int rc = svk_work_queue(ctx, SVK_SLOT_CONV41, 1, &queue)) return rc;
-  return launch_conv(ctx, "svk_c3d2_conv41", c3d2_conv41h_kernel<true>, c3d2_conv41h_kernel<false>, flags, p,
-                     sizeof(unsigned) * (size_t)C41H_LDS_WORDS, 512, 1, n_utt, queue);
+  static const ConvEntry e{"svk_c3d2_conv41", c3d2_conv41h_kernel<true>, c3d2_conv41h_kernel<false>, sizeof(unsigned) * (size_t)C41H_LDS_WORDS,
+                           512, 1, 1, SVK_SLOT_CONV41, 2};
+  return conv_entry(ctx, e, d_in, n_utt, d_wblk, d_bias, d_slope, flags, d_out);
 }

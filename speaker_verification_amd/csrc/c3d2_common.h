@@ -1,6 +1,8 @@
 // Device leaf helpers shared by the C3D2 network kernels (c3d2.hip, c3d2_tail.hip): vector types, PReLU, the (h, l) split of
-// the two-piece f16 products and the few statements every two-piece kernel repeats.  Leaf code only: item loops, staging
-// schedules, tile walks, prefetch depths, barriers and sched_barriers stay in the kernels.
+// the two-piece f16 products and the few statements every two-piece kernel repeats: the piece products of a K = 32 block
+// (mfma_pieces), the split-and-park of staged values (park_pieces), the pooled epilogue (prelu_pool_store) and the prologue's
+// loads (load_wblk, load_bias_slope).  Leaf code only: item loops, staging schedules, tile walks, prefetch depths, barriers and
+// sched_barriers stay in the kernels (c3d2.hip's first block splits its own kernel into phases; those are its own, not shared).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -72,11 +74,23 @@ __device__ __forceinline__ float max_with_lane_xor1(float x) {
   return d;
 }
 
-// acc + W x b through the three piece products of a K = 32 block, in the order H x h, H x l, L x h (W = (WH, WL), b = (bh, bl))
-__device__ __forceinline__ f32x4 mfma_pieces(u32x4 WH, u32x4 WL, u32x4 bh, u32x4 bl, f32x4 acc) {
+// acc + W x b through the three piece products of a K = 32 block, in the order H x h, H x l, L x h (W = (WH, WL), b = (bh, bl)).
+// `with_l` = false leaves H x l out: a block whose fragment bh already holds [h | l] (conv1_2's last tap)
+__device__ __forceinline__ f32x4 mfma_pieces(u32x4 WH, u32x4 WL, u32x4 bh, u32x4 bl, f32x4 acc, bool with_l = true) {
   acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, WH), __builtin_bit_cast(f16x8, bh), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, WH), __builtin_bit_cast(f16x8, bl), acc, 0, 0, 0);
+  if (with_l) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, WH), __builtin_bit_cast(f16x8, bl), acc, 0, 0, 0);
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, WL), __builtin_bit_cast(f16x8, bh), acc, 0, 0, 0);
+}
+
+// The pooled epilogue of conv1_2 and conv2_2: PReLU, max over the column pair (lanes i, i ^ 1: the same depth and row), and the
+// lane that holds the pair's maximum for the output (`store`: an even lane inside the item) stores its four channels
+template <bool SLOPE01>
+__device__ __forceinline__ void prelu_pool_store(f32x4 acc, f32x4 slope, float* dst, bool store) {
+  const f32x4 y = prelu4<SLOPE01>(acc, slope);
+  f32x4 o;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) o[r] = max_with_lane_xor1(y[r]);
+  if (store) *reinterpret_cast<f32x4*>(dst) = o;
 }
 
 // Four staged f32 values -> their h halves at dst, their l halves l_off words on.  The split is unconditional and only the two
