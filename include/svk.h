@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SVK_VERSION 114 /* 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
+#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only): + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
 
 typedef enum svk_status {
   SVK_OK = 0,
@@ -196,6 +196,34 @@ int svk_cube_gather(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t ma
 int svk_cube_gather_cmvn(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
                          const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, const double* d_stats,
                          float* d_out);
+
+/* ---- the three-channel input (constants.DERIVATIVE: static, delta, delta-delta) from STATIC features ------------
+ * feature.py:261-282 (extract_derivative_feature) stacks the static features with processing.py:201-236 applied once and
+ * twice; utils.py:382-397 (CMVN) then normalises each channel by itself (processing.py:239-271) and utils.py:325-348
+ * (FeatureCube3C) crops all three.  The reference's derivative runs along the FEATURE axis (Q11, reproduced by
+ * svk_derivative), so the three channels of a frame depend on that frame's static row alone: the entries below form the
+ * delta values where they are needed instead of writing, re-reading and stacking delta planes.  Every delta value is
+ * svk_derivative's (f32, the same expression and order, edge clamp min(c + k, n_cols - 1)); delta-delta is taken from the
+ * F32 delta values.  `delta` >= 1 is both steps' window (the reference uses 2).  max_frames * n_cols must stay below 2^31.
+ *
+ * d_stats float64 [n_utt][3][2][n_cols]: for channel ch (0 static, 1 delta, 2 delta-delta)
+ * [u][ch][0][c] = mean, [u][ch][1][c] = 1 / (std + 2^-30) (1 when variance == 0) over rows < n_frames[u]; clips with no
+ * rows are left untouched.  ONE pass over d_feat [n_utt][max_frames][n_cols]; bit-identical to svk_cmvn_stats on plane ch
+ * of svk_delta_planes (the same launch paths, SVK_CMVN_SPLIT included, the same summation order). */
+int svk_delta_cmvn_stats(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
+                         const int32_t* d_n_frames, int32_t delta, int32_t variance, double* d_stats);
+/* d_out [n_utt][3][max_frames][n_cols] (svk_c3d2_stage1_c3's d_feat layout): plane 0 = d_feat, 1 = derivative(d_feat),
+ * 2 = derivative(plane 1); with d_stats != NULL each value is (float)(((double)v - mean) * inv), svk_cmvn's expression.
+ * Rows >= n_frames[u] (NULL = max_frames) are written as zeros in all three planes.  d_out must not alias d_feat. */
+int svk_delta_planes(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
+                     const int32_t* d_n_frames, int32_t delta, const double* d_stats, float* d_out);
+/* FeatureCube3C (utils.py:325-348) from STATIC features: d_out [n_utt][3][n_crops][crop_frames][n_cols],
+ * out[u][ch][k][r][:] = channel ch of row crop[u][k] + r, normalised when d_stats != NULL; crop -1 / rows outside the
+ * clip's max_frames rows -> zeros, as svk_cube_gather / svk_cube_gather_cmvn (like those, it does not know n_frames: crop
+ * starts are expected to keep their rows below it, as svk_cube_draw_crops' do). */
+int svk_cube_gather_delta(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
+                          const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, int32_t delta,
+                          const double* d_stats, float* d_out);
 
 /* Crop starts drawn ON THE DEVICE (no host round trip for the per-clip frame count):
  * crop[u][c] = floor(uniform(seed, u, c) * (n_frames[u] - crop_frames)), a counter-based

@@ -2,7 +2,9 @@
 // the reference's processing module can be routed to the GPU on its own.
 //   svk_preemphasis  <- processing.py:45-58      svk_stack_frames <- processing.py:61-139
 //   svk_spectrum     <- processing.py:142-174    svk_cmvn         <- processing.py:239-271
-//   svk_cube_gather  <- /root/reference/utils.py:351-379
+//   svk_cube_gather  <- utils.py:351-379
+//   svk_delta_cmvn_stats / svk_delta_planes / svk_cube_gather_delta <- feature.py:261-282 + processing.py:201-236, :239-271 +
+//   utils.py:382-397, :325-348 (the three-channel input from static rows)
 // All of these are HBM-streaming kernels: 16-byte accesses where alignment allows,
 // grid capped at a few workgroups per CU with a grid-stride loop.
 #include <algorithm>
@@ -21,6 +23,13 @@ inline unsigned capped_grid(const svk_ctx* ctx, int64_t work_items, int per_bloc
   int64_t blocks = (work_items + per_block - 1) / per_block;
   int64_t cap = (int64_t)ctx->num_cu * 8;
   return (unsigned)std::max<int64_t>(1, std::min(blocks, cap));
+}
+
+// 1 / sum_k 2 k^2 (processing.py:233), rounded to f32 once: the scale of every kernel that forms a delta value
+inline float derivative_inv_scale(int32_t delta) {
+  double scale = 0.0;
+  for (int k = 1; k <= delta; ++k) scale += 2.0 * k * k;
+  return (float)(1.0 / scale);
 }
 
 // ---- pre-emphasis ---------------------------------------------------------------
@@ -249,6 +258,41 @@ __global__ __launch_bounds__(256) void twiddle_table_kernel(cplx* __restrict__ t
   }
 }
 
+// ---- 'derivative' features, bug-compatible (Q11): the sum every kernel that forms a delta value shares -----------
+// sum_{k=1..delta} k * tap(k) / sum_k 2 k^2 in f32, in this order (processing.py:201-236; tap(k) = the row's value at column
+// min(c + k, ncols - 1)).  derivative_kernel, the three-channel statistics and the plane / cube writers all call it, so a
+// delta value is the same bits wherever it is formed.
+template <class Tap>
+__device__ __forceinline__ float derivative_sum(int delta, float inv_scale, Tap tap) {
+  float acc = 0.f;
+  for (int k = 1; k <= delta; ++k) acc += (float)k * tap(k);
+  return acc * inv_scale;
+}
+__device__ __forceinline__ float derivative_at(const float* __restrict__ row, int c, int ncols, int delta, float inv_scale) {
+  return derivative_sum(delta, inv_scale, [&](int k) { return row[min(c + k, ncols - 1)]; });
+}
+// static, delta and delta-delta (the derivative of the F32 delta values) of column c of one static row
+__device__ __forceinline__ void delta_channels(const float* __restrict__ row, int c, int ncols, int delta, float inv_scale,
+                                               float (&v)[3]) {
+  v[0] = row[c];
+  v[1] = derivative_at(row, c, ncols, delta, inv_scale);
+  v[2] = derivative_sum(delta, inv_scale,
+                        [&](int k) { return derivative_at(row, min(c + k, ncols - 1), ncols, delta, inv_scale); });
+}
+
+// ---- CMVN: the pieces the one-channel and the three-channel kernels share (same expressions -> same bits) -----------
+__device__ __forceinline__ void cmvn_acc(double& s1, double& s2, float v) {
+  s1 += (double)v;
+  s2 += (double)v * (double)v;
+}
+// 1 / (std + 2^-30) from the column's sum of squares q, its mean and its row count (processing.py:250,266)
+__device__ __forceinline__ double cmvn_inv_std(double q, double mean, int T) {
+  double var = q / (double)T - mean * mean;
+  var = var > 0.0 ? var : 0.0;
+  return 1.0 / (sqrt(var) + 9.313225746154785e-10);
+}
+__device__ __forceinline__ float cmvn_apply(float v, double mean, double inv) { return (float)(((double)v - mean) * inv); }
+
 // ---- CMVN: one workgroup per clip ------------------------------------------------------
 // Threads form a [R rows][cb cols] grid over a column block; column sums are kept in float64.
 // APPLY = false: the clip's statistics only, stats[utt][0][c] = mean, stats[utt][1][c] = 1 / (std + 2^-30) (svk_cmvn_stats:
@@ -279,20 +323,12 @@ __global__ __launch_bounds__(256) void cmvn_kernel(float* __restrict__ feat, int
       for (; t + 3 * R < T; t += 4 * R) {
         const float v0 = col[(int64_t)t * ncols], v1 = col[(int64_t)(t + R) * ncols], v2 = col[(int64_t)(t + 2 * R) * ncols],
                     v3 = col[(int64_t)(t + 3 * R) * ncols];
-        s1 += (double)v0;
-        s2 += (double)v0 * (double)v0;
-        s1 += (double)v1;
-        s2 += (double)v1 * (double)v1;
-        s1 += (double)v2;
-        s2 += (double)v2 * (double)v2;
-        s1 += (double)v3;
-        s2 += (double)v3 * (double)v3;
+        cmvn_acc(s1, s2, v0);
+        cmvn_acc(s1, s2, v1);
+        cmvn_acc(s1, s2, v2);
+        cmvn_acc(s1, s2, v3);
       }
-      for (; t < T; t += R) {
-        const double v = (double)col[(int64_t)t * ncols];
-        s1 += v;
-        s2 += v * v;
-      }
+      for (; t < T; t += R) cmvn_acc(s1, s2, col[(int64_t)t * ncols]);
     }
     red[threadIdx.x] = active ? s1 : 0.0;
     __syncthreads();
@@ -309,9 +345,7 @@ __global__ __launch_bounds__(256) void cmvn_kernel(float* __restrict__ feat, int
       if (active) {
         double q = 0.0;
         for (int r = 0; r < R; ++r) q += red[r * cb + tc];
-        double var = q / (double)T - mean * mean;
-        var = var > 0.0 ? var : 0.0;
-        inv = 1.0 / (sqrt(var) + 9.313225746154785e-10);  // + 2^-30, processing.py:250,266
+        inv = cmvn_inv_std(q, mean, T);
       }
       __syncthreads();
     }
@@ -324,9 +358,9 @@ __global__ __launch_bounds__(256) void cmvn_kernel(float* __restrict__ feat, int
 #pragma unroll
           for (int k = 0; k < 4; ++k) v[k] = col[(int64_t)(t + k * R) * ncols];
 #pragma unroll
-          for (int k = 0; k < 4; ++k) col[(int64_t)(t + k * R) * ncols] = (float)(((double)v[k] - mean) * inv);
+          for (int k = 0; k < 4; ++k) col[(int64_t)(t + k * R) * ncols] = cmvn_apply(v[k], mean, inv);
         }
-        for (; t < T; t += R) col[(int64_t)t * ncols] = (float)(((double)col[(int64_t)t * ncols] - mean) * inv);
+        for (; t < T; t += R) col[(int64_t)t * ncols] = cmvn_apply(col[(int64_t)t * ncols], mean, inv);
       }
     } else if (active && tr == 0) {
       stats[((int64_t)utt * 2) * ncols + c0 + tc] = mean;
@@ -359,11 +393,7 @@ __global__ __launch_bounds__(256) void cmvn_partial_kernel(const float* __restri
     const int tc = threadIdx.x % cb, tr = threadIdx.x / cb;
     double s = 0.0, q = 0.0;
     if (tr < R)
-      for (int t = t0 + tr; t < t1; t += R) {
-        const double v = (double)base[(int64_t)t * ncols + c0 + tc];
-        s += v;
-        q += v * v;
-      }
+      for (int t = t0 + tr; t < t1; t += R) cmvn_acc(s, q, base[(int64_t)t * ncols + c0 + tc]);
     red[0][threadIdx.x] = tr < R ? s : 0.0;
     red[1][threadIdx.x] = tr < R ? q : 0.0;
     __syncthreads();
@@ -382,9 +412,10 @@ __global__ __launch_bounds__(256) void cmvn_partial_kernel(const float* __restri
 
 __global__ __launch_bounds__(256) void cmvn_stats_kernel(const double* __restrict__ part, int max_frames, int ncols,
                                                          const int32_t* __restrict__ n_frames, int n_chunks, int variance,
-                                                         double* __restrict__ stats /* [utt][2][ncols]: mean, inv */) {
+                                                         int planes, double* __restrict__ stats /* [utt][2][ncols]: mean, inv */) {
+  // planes = 3 (svk_delta_cmvn_stats): `utt` counts (clip, channel) pairs, part and stats are [clip][channel][..]
   const int utt = blockIdx.x;
-  int T = n_frames ? n_frames[utt] : max_frames;
+  int T = n_frames ? n_frames[utt / planes] : max_frames;
   T = T < max_frames ? T : max_frames;
   if (T <= 0) return;
   const int used = (T + CMVN_CHUNK - 1) / CMVN_CHUNK;
@@ -396,12 +427,7 @@ __global__ __launch_bounds__(256) void cmvn_stats_kernel(const double* __restric
       q += pk[ncols + c];
     }
     const double mean = s / (double)T;
-    double inv = 1.0;
-    if (variance) {
-      double var = q / (double)T - mean * mean;
-      var = var > 0.0 ? var : 0.0;
-      inv = 1.0 / (sqrt(var) + 9.313225746154785e-10);   // + 2^-30, processing.py:250,266
-    }
+    const double inv = variance ? cmvn_inv_std(q, mean, T) : 1.0;
     stats[((int64_t)utt * 2) * ncols + c] = mean;
     stats[((int64_t)utt * 2 + 1) * ncols + c] = inv;
   }
@@ -420,7 +446,7 @@ __global__ __launch_bounds__(256) void cmvn_apply_kernel(float* __restrict__ fea
   const int n = (t1 - t0) * ncols;
   for (int e = threadIdx.x; e < n; e += 256) {
     const int c = e % ncols;
-    base[e] = (float)(((double)base[e] - st[c]) * st[ncols + c]);
+    base[e] = cmvn_apply(base[e], st[c], st[ncols + c]);
   }
 }
 
@@ -805,16 +831,13 @@ __global__ __launch_bounds__(256) void cmvnw_tile_kernel(const float* __restrict
   }
 }
 
-// ---- 'derivative' features, bug-compatible (Q11) -------------------------------------------------
+// ---- 'derivative' features, bug-compatible (Q11): derivative_sum above ---------------------------
 __global__ __launch_bounds__(256) void derivative_kernel(const float* __restrict__ in, int64_t total, int ncols,
                                                          int delta, float inv_scale, float* __restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = i / ncols;
     const int c = (int)(i - r * ncols);
-    const float* row = in + r * ncols;
-    float acc = 0.f;
-    for (int k = 1; k <= delta; ++k) acc += (float)k * row[min(c + k, ncols - 1)];
-    out[i] = acc * inv_scale;
+    out[i] = derivative_at(in + r * ncols, c, ncols, delta, inv_scale);
   }
 }
 
@@ -876,13 +899,13 @@ __global__ __launch_bounds__(256) void cube_gather_kernel(const float* __restric
           const f32x4 v = s4[i];
           f32x4 o;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (float)(((double)v[e] - st[c + e]) * st[ncols + c + e]);
+          for (int e = 0; e < 4; ++e) o[e] = cmvn_apply(v[e], st[c + e], st[ncols + c + e]);
           d4[i] = o;
         }
       } else {
         for (int i = threadIdx.x; i < run; i += blockDim.x) {
           const int c = i % ncols;
-          dst[i] = i < avail ? (float)(((double)src[i] - st[c]) * st[ncols + c]) : 0.f;
+          dst[i] = i < avail ? cmvn_apply(src[i], st[c], st[ncols + c]) : 0.f;
         }
       }
     } else if (vec) {
@@ -891,6 +914,265 @@ __global__ __launch_bounds__(256) void cube_gather_kernel(const float* __restric
       for (int i = threadIdx.x; i < run / 4; i += blockDim.x) d4[i] = s4[i];
     } else {
       for (int i = threadIdx.x; i < run; i += blockDim.x) dst[i] = i < avail ? src[i] : 0.f;
+    }
+  }
+}
+
+// ---- the three-channel input (static, delta, delta-delta: feature.py:261-282, utils.py:382-397, :325-348) from STATIC rows --
+// The reference's derivative runs along the FEATURE axis (Q11), so all three channels of a frame are functions of that
+// frame's static row alone: no delta plane has to exist before the statistics are summed or the cube is written.
+
+// svk_delta_cmvn_stats, clips of up to 1024 frames: cmvn_kernel<false> over the three channels in ONE pass over the static
+// rows.  The thread <-> (row group, column) map, the order of the rows inside a thread and of the row groups in the
+// reduction are cmvn_kernel's, the values are derivative_kernel's: channel ch's statistics are bit-identical to
+// svk_cmvn_stats on plane ch.  stats [utt][3][2][ncols].
+__global__ __launch_bounds__(256) void delta_cmvn_kernel(const float* __restrict__ feat, int max_frames, int ncols,
+                                                         const int32_t* __restrict__ n_frames, int delta, float inv_scale,
+                                                         int variance, double* __restrict__ stats) {
+  __shared__ double red[256];
+  const int utt = blockIdx.x;
+  int T = n_frames ? n_frames[utt] : max_frames;
+  T = T < max_frames ? T : max_frames;
+  if (T <= 0) return;
+  const float* base = feat + (int64_t)utt * max_frames * ncols;
+  for (int c0 = 0; c0 < ncols; c0 += 256) {
+    const int cb = min(256, ncols - c0);
+    const int R = 256 / cb;
+    const int tc = threadIdx.x % cb, tr = threadIdx.x / cb;
+    const bool active = tr < R;
+    double s1[3] = {0.0, 0.0, 0.0}, s2[3] = {0.0, 0.0, 0.0};
+    if (active) {
+      int t = tr;
+      for (; t + 3 * R < T; t += 4 * R) {   // four rows in flight, summed in row order (cmvn_kernel)
+        float v[4][3];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) delta_channels(base + (int64_t)(t + j * R) * ncols, c0 + tc, ncols, delta, inv_scale, v[j]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) cmvn_acc(s1[ch], s2[ch], v[j][ch]);
+      }
+      for (; t < T; t += R) {
+        float v[3];
+        delta_channels(base + (int64_t)t * ncols, c0 + tc, ncols, delta, inv_scale, v);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) cmvn_acc(s1[ch], s2[ch], v[ch]);
+      }
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      red[threadIdx.x] = active ? s1[ch] : 0.0;
+      __syncthreads();
+      double mean = 0.0;
+      if (active) {
+        for (int r = 0; r < R; ++r) mean += red[r * cb + tc];
+        mean /= (double)T;
+      }
+      __syncthreads();
+      double inv = 1.0;
+      if (variance) {
+        red[threadIdx.x] = active ? s2[ch] : 0.0;
+        __syncthreads();
+        if (active) {
+          double q = 0.0;
+          for (int r = 0; r < R; ++r) q += red[r * cb + tc];
+          inv = cmvn_inv_std(q, mean, T);
+        }
+        __syncthreads();
+      }
+      if (active && tr == 0) {
+        stats[(((int64_t)utt * 3 + ch) * 2) * ncols + c0 + tc] = mean;
+        stats[(((int64_t)utt * 3 + ch) * 2 + 1) * ncols + c0 + tc] = inv;
+      }
+    }
+  }
+}
+
+// svk_delta_cmvn_stats, long clips: cmvn_partial_kernel over the three channels; part [utt][3][chunk][2][ncols], which
+// cmvn_stats_kernel (planes = 3) reduces over the chunks in order.
+__global__ __launch_bounds__(256) void delta_cmvn_partial_kernel(const float* __restrict__ feat, int max_frames, int ncols,
+                                                                 const int32_t* __restrict__ n_frames, int n_chunks, int delta,
+                                                                 float inv_scale, double* __restrict__ part) {
+  __shared__ double red[2][256];
+  const int utt = blockIdx.y, chunk = blockIdx.x;
+  int T = n_frames ? n_frames[utt] : max_frames;
+  T = T < max_frames ? T : max_frames;
+  const int t0 = chunk * CMVN_CHUNK, t1 = min(T, t0 + CMVN_CHUNK);
+  const float* base = feat + (int64_t)utt * max_frames * ncols;
+  for (int c0 = 0; c0 < ncols; c0 += 256) {
+    const int cb = min(256, ncols - c0), R = 256 / cb;
+    const int tc = threadIdx.x % cb, tr = threadIdx.x / cb;
+    double s[3] = {0.0, 0.0, 0.0}, q[3] = {0.0, 0.0, 0.0};
+    if (tr < R)
+      for (int t = t0 + tr; t < t1; t += R) {
+        float v[3];
+        delta_channels(base + (int64_t)t * ncols, c0 + tc, ncols, delta, inv_scale, v);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) cmvn_acc(s[ch], q[ch], v[ch]);
+      }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      red[0][threadIdx.x] = tr < R ? s[ch] : 0.0;
+      red[1][threadIdx.x] = tr < R ? q[ch] : 0.0;
+      __syncthreads();
+      if (tr == 0) {
+        double* out = part + (((int64_t)utt * 3 + ch) * n_chunks + chunk) * 2 * ncols;
+        double ss = 0.0, qq = 0.0;
+        for (int r = 0; r < R; ++r) {
+          ss += red[0][r * cb + tc];
+          qq += red[1][r * cb + tc];
+        }
+        out[c0 + tc] = ss;
+        out[ncols + c0 + tc] = qq;
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// The three channels of columns c .. c + 3 of one static row (ncols a multiple of 4, the row 16-byte aligned), normalised with
+// the clip's statistics st [3][2][ncols] when given, as three 16-byte stores.  DELTA = 2 (extract_derivative_feature's window):
+// the row's columns c .. c + 7 are two 16-byte reads (the second is the neighbouring lane's first: a cache hit) and every tap
+// is a register; DELTA = 0: any window, the taps are re-read from cache one by one.
+template <int DELTA>
+__device__ __forceinline__ void delta_store4(const float* __restrict__ row, int c, int ncols, int delta, float inv_scale,
+                                             const double* __restrict__ st, float* __restrict__ d0, float* __restrict__ d1,
+                                             float* __restrict__ d2) {
+  const f32x4 x = *reinterpret_cast<const f32x4*>(row + c);
+  f32x4 o[3];
+  o[0] = x;
+  if (DELTA == 2) {
+    float w[8];   // w[i] = row[min(c + i, ncols - 1)]
+    f32x4 y = {x[3], x[3], x[3], x[3]};
+    if (c + 4 < ncols) y = *reinterpret_cast<const f32x4*>(row + c + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      w[e] = x[e];
+      w[4 + e] = y[e];
+    }
+    float d[6];   // d[i] = delta at column min(c + i, ncols - 1): its taps clamp to the same last column
+#pragma unroll
+    for (int i = 0; i < 6; ++i) d[i] = derivative_sum(2, inv_scale, [&](int k) { return w[i + k]; });
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      o[1][e] = d[e];
+      o[2][e] = derivative_sum(2, inv_scale, [&](int k) { return d[e + k]; });
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float v[3];
+      delta_channels(row, c + e, ncols, delta, inv_scale, v);
+      o[1][e] = v[1];
+      o[2][e] = v[2];
+    }
+  }
+  if (st) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const double* mean = st + (int64_t)(2 * ch) * ncols + c;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[ch][e] = cmvn_apply(o[ch][e], mean[e], mean[ncols + e]);
+    }
+  }
+  *reinterpret_cast<f32x4*>(d0) = o[0];
+  *reinterpret_cast<f32x4*>(d1) = o[1];
+  *reinterpret_cast<f32x4*>(d2) = o[2];
+}
+
+// one column, any ncols / alignment
+__device__ __forceinline__ void delta_store1(const float* __restrict__ row, int c, int ncols, int delta, float inv_scale,
+                                             const double* __restrict__ st, float* __restrict__ d0, float* __restrict__ d1,
+                                             float* __restrict__ d2) {
+  float v[3];
+  delta_channels(row, c, ncols, delta, inv_scale, v);
+  if (st) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) v[ch] = cmvn_apply(v[ch], st[(int64_t)(2 * ch) * ncols + c], st[(int64_t)(2 * ch + 1) * ncols + c]);
+  }
+  *d0 = v[0];
+  *d1 = v[1];
+  *d2 = v[2];
+}
+
+// svk_delta_planes: out [utt][3][max_frames][ncols] from feat [utt][max_frames][ncols]; rows >= n_frames are zeros.  A job is
+// DP_ITEMS consecutive items of one clip (VEC: an item is a 16-byte piece of a row, else one value); the static row is read
+// once, from HBM, by the lanes that own its pieces.
+constexpr int DP_ITEMS = 1024;
+template <bool VEC, int DELTA>
+__global__ __launch_bounds__(256) void delta_planes_kernel(const float* __restrict__ feat, int max_frames, int ncols,
+                                                           const int32_t* __restrict__ n_frames, int delta, float inv_scale,
+                                                           const double* __restrict__ stats, int jobs_per_clip, int64_t n_jobs,
+                                                           float* __restrict__ out) {
+  const int per_row = VEC ? ncols / 4 : ncols;     // items of a row
+  const int width = VEC ? 4 : 1;                   // values of an item
+  const int n_items = max_frames * per_row;        // of a clip (the launcher keeps max_frames * ncols below 2^31)
+  const int64_t plane = (int64_t)max_frames * ncols;
+  for (int64_t job = blockIdx.x; job < n_jobs; job += gridDim.x) {
+    const int64_t utt = job / jobs_per_clip;
+    const int first = (int)(job - utt * jobs_per_clip) * DP_ITEMS;
+    int T = n_frames ? n_frames[utt] : max_frames;
+    T = T < max_frames ? T : max_frames;
+    const float* src = feat + utt * plane;
+    float* dst = out + utt * 3 * plane;
+    const double* st = stats ? stats + utt * 6 * ncols : nullptr;
+#pragma unroll
+    for (int j = 0; j < DP_ITEMS / 256; ++j) {
+      const int item = first + j * 256 + (int)threadIdx.x;
+      if (item >= n_items) break;
+      const int t = item / per_row, c = (item - t * per_row) * width;
+      const int64_t at = (int64_t)t * ncols + c;
+      if (t >= T) {
+        if (VEC) {
+          const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) *reinterpret_cast<f32x4*>(dst + ch * plane + at) = z;
+        } else {
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) dst[ch * plane + at] = 0.f;
+        }
+      } else if (VEC) {
+        delta_store4<DELTA>(src + (int64_t)t * ncols, c, ncols, delta, inv_scale, st, dst + at, dst + plane + at, dst + 2 * plane + at);
+      } else {
+        delta_store1(src + (int64_t)t * ncols, c, ncols, delta, inv_scale, st, dst + at, dst + plane + at, dst + 2 * plane + at);
+      }
+    }
+  }
+}
+
+// svk_cube_gather_delta: cube_gather_kernel's jobs (one crop = one run of crop_frames rows) with the three channels formed on
+// the way; out [utt][3][n_crops][crop_frames][ncols].  crop -1 and rows at or past max_frames are zeros.
+template <int DELTA>
+__global__ __launch_bounds__(256) void cube_gather_delta_kernel(const float* __restrict__ feat, int max_frames, int ncols,
+                                                                const int32_t* __restrict__ crop, int n_crops, int crop_frames,
+                                                                int64_t n_jobs, int delta, float inv_scale, bool aligned,
+                                                                const double* __restrict__ stats, float* __restrict__ out) {
+  const int run = crop_frames * ncols;
+  for (int64_t job = blockIdx.x; job < n_jobs; job += gridDim.x) {
+    const int64_t utt = job / n_crops;
+    const int k = (int)(job - utt * n_crops);
+    int start = crop[job];
+    start = start < 0 ? max_frames : (start > max_frames ? max_frames : start);   // -1: svk_cube_draw_crops' too-short mark
+    const float* src = feat + (utt * max_frames + start) * ncols;
+    const int64_t chan = (int64_t)n_crops * run;                                  // one channel of a clip's cube
+    float* dst = out + utt * 3 * chan + (int64_t)k * run;
+    const int avail = (max_frames - start) * ncols;                               // never read past the clip's rows
+    const double* st = stats ? stats + utt * 6 * ncols : nullptr;
+    if (aligned && avail >= run) {   // aligned: ncols % 4 == 0 and both bases 16-byte aligned -> so is every row
+      for (int i = threadIdx.x; i < run / 4; i += blockDim.x) {
+        const int r = (4 * i) / ncols, c = 4 * i - r * ncols;
+        delta_store4<DELTA>(src + (int64_t)r * ncols, c, ncols, delta, inv_scale, st, dst + 4 * i, dst + chan + 4 * i,
+                            dst + 2 * chan + 4 * i);
+      }
+    } else {
+      for (int i = threadIdx.x; i < run; i += blockDim.x) {
+        if (i < avail) {
+          const int r = i / ncols, c = i - r * ncols;
+          delta_store1(src + (int64_t)r * ncols, c, ncols, delta, inv_scale, st, dst + i, dst + chan + i, dst + 2 * chan + i);
+        } else {
+          dst[i] = dst[chan + i] = dst[2 * chan + i] = 0.f;
+        }
+      }
     }
   }
 }
@@ -1061,7 +1343,7 @@ static int cmvn_launch(svk_ctx* ctx, float* d_feat, int32_t n_utt, int32_t max_f
                        d_n_frames, n_chunks, part);
     SVK_LAUNCH_CHECK(ctx);
     hipLaunchKernelGGL(cmvn_stats_kernel, dim3(n_utt), dim3(256), 0, ctx->stream, part, max_frames, n_cols, d_n_frames, n_chunks,
-                       variance, stats);
+                       variance, 1, stats);
     SVK_LAUNCH_CHECK(ctx);
     if (!d_stats_out) {
       hipLaunchKernelGGL(cmvn_apply_kernel, dim3(n_chunks, n_utt), dim3(256), 0, ctx->stream, d_feat, max_frames, n_cols,
@@ -1173,10 +1455,8 @@ int svk_derivative(svk_ctx* ctx, const float* d_in, int64_t n_rows, int32_t n_co
   const int64_t total = n_rows * n_cols;
   if (total == 0) return SVK_OK;
   SVK_REQUIRE(ctx, d_in && d_out && d_in != d_out, "NULL or aliased buffer");
-  double scale = 0.0;
-  for (int k = 1; k <= delta; ++k) scale += 2.0 * k * k;  // processing.py:233
   hipLaunchKernelGGL(derivative_kernel, dim3(capped_grid(ctx, total, 256)), dim3(256), 0, ctx->stream, d_in, total,
-                     n_cols, delta, (float)(1.0 / scale), d_out);
+                     n_cols, delta, derivative_inv_scale(delta), d_out);
   SVK_LAUNCH_CHECK(ctx);
   return SVK_OK;
 }
@@ -1236,6 +1516,79 @@ int svk_cube_gather_cmvn(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32
   if (!ctx) return SVK_ERR_BAD_ARG;
   SVK_REQUIRE(ctx, d_stats || n_utt == 0, "d_stats is NULL");
   return cube_gather_launch(ctx, d_feat, n_utt, max_frames, n_cols, d_crop_idx, n_crops, crop_frames, d_stats, d_out);
+}
+
+int svk_delta_cmvn_stats(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
+                         const int32_t* d_n_frames, int32_t delta, int32_t variance, double* d_stats) {
+  if (!ctx) return SVK_ERR_BAD_ARG;
+  SVK_REQUIRE(ctx, n_utt >= 0 && max_frames >= 0 && n_cols >= 0, "negative shape");
+  SVK_REQUIRE(ctx, delta >= 1, "delta");
+  if (n_utt == 0 || max_frames == 0 || n_cols == 0) return SVK_OK;
+  SVK_REQUIRE(ctx, d_feat && d_stats, "NULL buffer");
+  const float inv_scale = derivative_inv_scale(delta);
+  // the two paths of cmvn_launch, chosen the same way
+  const char* force = getenv("SVK_CMVN_SPLIT");
+  const bool split = force ? force[0] == '1' : max_frames > 1024;
+  if (split && n_utt <= 65535) {
+    const int n_chunks = (max_frames + CMVN_CHUNK - 1) / CMVN_CHUNK;
+    const int rc = svk_ensure_work(ctx, sizeof(double) * (size_t)n_utt * 3 * n_chunks * 2 * n_cols);
+    if (rc != SVK_OK) return rc;
+    double* part = reinterpret_cast<double*>(ctx->work);
+    hipLaunchKernelGGL(delta_cmvn_partial_kernel, dim3(n_chunks, n_utt), dim3(256), 0, ctx->stream, d_feat, max_frames, n_cols,
+                       d_n_frames, n_chunks, delta, inv_scale, part);
+    SVK_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(cmvn_stats_kernel, dim3(3 * n_utt), dim3(256), 0, ctx->stream, part, max_frames, n_cols, d_n_frames,
+                       n_chunks, variance, 3, d_stats);
+    SVK_LAUNCH_CHECK(ctx);
+    return SVK_OK;
+  }
+  hipLaunchKernelGGL(delta_cmvn_kernel, dim3(n_utt), dim3(256), 0, ctx->stream, d_feat, max_frames, n_cols, d_n_frames, delta,
+                     inv_scale, variance, d_stats);
+  SVK_LAUNCH_CHECK(ctx);
+  return SVK_OK;
+}
+
+int svk_delta_planes(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
+                     const int32_t* d_n_frames, int32_t delta, const double* d_stats, float* d_out) {
+  if (!ctx) return SVK_ERR_BAD_ARG;
+  SVK_REQUIRE(ctx, n_utt >= 0 && max_frames >= 0 && n_cols >= 0, "negative shape");
+  SVK_REQUIRE(ctx, delta >= 1, "delta");
+  if (n_utt == 0 || max_frames == 0 || n_cols == 0) return SVK_OK;
+  SVK_REQUIRE(ctx, d_feat && d_out && d_feat != d_out, "NULL or aliased buffer");
+  if ((int64_t)max_frames * n_cols > INT32_MAX)
+    return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "a clip of %d x %d values: max_frames * n_cols must stay below 2^31", max_frames, n_cols);
+  const bool vec = (n_cols & 3) == 0 && ((reinterpret_cast<uintptr_t>(d_feat) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0;
+  const int64_t n_items = (int64_t)max_frames * (vec ? n_cols / 4 : n_cols);
+  const int jobs_per_clip = (int)((n_items + DP_ITEMS - 1) / DP_ITEMS);
+  const int64_t jobs = (int64_t)n_utt * jobs_per_clip;
+  const dim3 grid((unsigned)std::min<int64_t>(jobs, (int64_t)ctx->num_cu * 16));
+  const float inv_scale = derivative_inv_scale(delta);
+  auto kern = !vec ? delta_planes_kernel<false, 0> : delta == 2 ? delta_planes_kernel<true, 2> : delta_planes_kernel<true, 0>;
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, ctx->stream, d_feat, max_frames, n_cols, d_n_frames, delta, inv_scale, d_stats,
+                     jobs_per_clip, jobs, d_out);
+  SVK_LAUNCH_CHECK(ctx);
+  return SVK_OK;
+}
+
+int svk_cube_gather_delta(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
+                          const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, int32_t delta, const double* d_stats,
+                          float* d_out) {
+  if (!ctx) return SVK_ERR_BAD_ARG;
+  SVK_REQUIRE(ctx, n_utt >= 0 && n_crops >= 0 && crop_frames >= 0 && n_cols >= 0 && max_frames >= 0, "negative shape");
+  SVK_REQUIRE(ctx, delta >= 1, "delta");
+  const int64_t jobs = (int64_t)n_utt * n_crops;
+  if (jobs == 0 || crop_frames == 0 || n_cols == 0) return SVK_OK;
+  SVK_REQUIRE(ctx, d_feat && d_crop_idx && d_out && d_feat != d_out, "NULL or aliased buffer");
+  SVK_REQUIRE(ctx, crop_frames <= max_frames, "crop_frames exceeds max_frames");
+  if ((int64_t)max_frames * n_cols > INT32_MAX)
+    return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "a clip of %d x %d values: max_frames * n_cols must stay below 2^31", max_frames, n_cols);
+  const bool aligned = (n_cols & 3) == 0 && ((reinterpret_cast<uintptr_t>(d_feat) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0;
+  const unsigned grid = (unsigned)std::min<int64_t>(jobs, (int64_t)ctx->num_cu * 16);
+  auto kern = delta == 2 ? cube_gather_delta_kernel<2> : cube_gather_delta_kernel<0>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, ctx->stream, d_feat, max_frames, n_cols, d_crop_idx, n_crops, crop_frames,
+                     jobs, delta, derivative_inv_scale(delta), aligned, d_stats, d_out);
+  SVK_LAUNCH_CHECK(ctx);
+  return SVK_OK;
 }
 
 }  // extern "C"

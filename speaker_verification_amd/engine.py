@@ -320,6 +320,50 @@ class Engine:
                                       int(bool(variance)), self._ptr(stats)), self.ctx)
         return stats
 
+    def _static_rows(self, feat, who):
+        feat = self.to_device(feat, _torch().float32)
+        if feat.dim() != 3:
+            raise ValueError("%s wants static features [n_utt, max_frames, cols]" % who)
+        return feat
+
+    def _stats3(self, stats, n, cols):
+        torch = _torch()
+        if stats is not None and (not isinstance(stats, torch.Tensor) or stats.dtype != torch.float64 or not stats.is_cuda
+                                  or tuple(stats.shape) != (n, 3, 2, cols) or not stats.is_contiguous()):
+            raise ValueError("stats must be the float64 [n, 3, 2, cols] tensor of delta_cmvn_stats")
+        return stats
+
+    def delta_cmvn_stats(self, feat, n_frames=None, delta=2, variance=False):
+        """svk_delta_cmvn_stats: the CMVN statistics of the three channels (static, delta, delta-delta: feature.py:261-282)
+        of STATIC features [n_utt, max_frames, cols], one pass, as float64 [n_utt, 3, 2, cols] (mean, 1 / (std + 2^-30));
+        [:, ch] is bit-identical to cmvn_stats of plane ch.  delta_planes / cube_gather_delta(..., stats=...) apply them."""
+        torch = _torch()
+        feat = self._static_rows(feat, "delta_cmvn_stats")
+        nf = self.to_device(n_frames, torch.int32) if n_frames is not None else None
+        stats = torch.zeros((feat.shape[0], 3, 2, feat.shape[2]), dtype=torch.float64, device=self.device)
+        self._stream()
+        check(self.lib.svk_delta_cmvn_stats(self.ctx, self._ptr(feat), feat.shape[0], feat.shape[1], feat.shape[2], self._ptr(nf),
+                                            int(delta), int(bool(variance)), self._ptr(stats)), self.ctx)
+        return stats
+
+    def delta_planes(self, feat, n_frames=None, delta=2, stats=None, out=None):
+        """svk_delta_planes: STATIC features [n, T, C] -> [n, 3, T, C] (static, derivative, derivative of the derivative: the
+        feature rows svk_c3d2_stage1_c3 reads), CMVN-normalised per channel with `stats` (delta_cmvn_stats); rows at or past
+        n_frames are zeros."""
+        torch = _torch()
+        feat = self._static_rows(feat, "delta_planes")
+        n, T, Cc = feat.shape
+        nf = self.to_device(n_frames, torch.int32) if n_frames is not None else None
+        stats = self._stats3(stats, n, Cc)
+        if out is None:
+            out = torch.empty((n, 3, T, Cc), dtype=torch.float32, device=self.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 3, T, Cc)):
+            raise ValueError("out must be a contiguous float32 CUDA tensor [n, 3, max_frames, cols]")
+        self._stream()
+        check(self.lib.svk_delta_planes(self.ctx, self._ptr(feat), n, T, Cc, self._ptr(nf), int(delta), self._ptr(stats),
+                                        self._ptr(out)), self.ctx)
+        return out
+
     def mel_features(self, power, bank, out_kind, num_ceps=13, dc_elimination=True, want_energy=False):
         """General mel / log / DCT stage on a device power spectrum [T, bins] (any fft length)."""
         torch = _torch()
@@ -456,6 +500,28 @@ class Engine:
             return out
         check(self.lib.svk_cube_gather(self.ctx, self._ptr(feat), n, T, Cc, self._ptr(idx), n_crops, crop_frames,
                                        self._ptr(out)), self.ctx)
+        return out
+
+    def cube_gather_delta(self, feat, crop_idx, crop_frames=80, delta=2, stats=None, out=None):
+        """svk_cube_gather_delta: STATIC feat [n, T, C] + crop_idx [n, n_crops] -> the three-channel cube
+        [n, 3, n_crops, crop_frames, C] (utils.py:325-348), normalised per channel with `stats` (delta_cmvn_stats): the delta
+        channels exist only for the rows the crops read."""
+        torch = _torch()
+        feat = self._static_rows(feat, "cube_gather_delta")
+        idx = self.to_device(crop_idx, torch.int32)
+        n, T, Cc = feat.shape
+        if idx.dim() != 2 or idx.shape[0] != n or not idx.is_contiguous():
+            raise ValueError("crop_idx must be [n, n_crops] int32")
+        n_crops = idx.shape[1]
+        stats = self._stats3(stats, n, Cc)
+        shape = (n, 3, n_crops, crop_frames, Cc)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+            raise ValueError("out must be a contiguous float32 CUDA tensor [n, 3, n_crops, crop_frames, cols]")
+        self._stream()
+        check(self.lib.svk_cube_gather_delta(self.ctx, self._ptr(feat), n, T, Cc, self._ptr(idx), n_crops, int(crop_frames),
+                                             int(delta), self._ptr(stats), self._ptr(out)), self.ctx)
         return out
 
     def c3d2_stage1(self, feat, crop_idx, tables, crop_frames=80):

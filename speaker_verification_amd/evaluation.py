@@ -188,8 +188,9 @@ def dataset_embeddings(dataset, model, batch=256):
     utils.py:351-379 FeatureCube with crop starts from the GLOBAL NumPy RNG, drawn in file order;
     `model(cube, development=False)`) run `batch` files at a time: one ragged front-end launch, one CMVN and the seven
     libsvk network kernels per batch -- the cube is never built (`svk_c3d2_stage1` reads feature rows + crop starts).
-    With `constants.DERIVATIVE` (a `C3D2(n, 3)` model, utils.py:325-348 FeatureCube3C): the two derivative launches and a
-    CMVN per channel in front, `svk_c3d2_stage1_c3` on the three channel planes."""
+    With `constants.DERIVATIVE` (a `C3D2(n, 3)` model, utils.py:325-348 FeatureCube3C): one statistics pass over the static
+    features (`svk_delta_cmvn_stats`) and one pass that writes the three normalised channel planes (`svk_delta_planes`),
+    then `svk_c3d2_stage1_c3` on those planes."""
     from . import _lib
     from . import constants as c
     from .engine import spec_from_seconds
@@ -209,12 +210,8 @@ def dataset_embeddings(dataset, model, batch=256):
         if c.DERIVATIVE:
             # utils.py:385-391: static, delta and the delta of delta (extract_derivative_feature, Q11 included), then CMVN per
             # channel; [n, 3, T, 40] is the layout svk_c3d2_stage1_c3 reads (FeatureCube3C's crops of it)
-            chans = [feat, eng.derivative(feat, 2)]
-            chans.append(eng.derivative(chans[1], 2))
-            if c.NORMALIZE:
-                for ch in chans:
-                    eng.cmvn_(ch, n_frames, variance=True)
-            feat = torch.stack(chans, 1)
+            stats = eng.delta_cmvn_stats(feat, n_frames, delta=2, variance=True) if c.NORMALIZE else None
+            feat = eng.delta_planes(feat, n_frames, delta=2, stats=stats)
         elif c.NORMALIZE:
             eng.cmvn_(feat, n_frames, variance=True)
         # utils.py:372, one draw per file in file order (numpy raises for clips of <= 80 frames, as there)

@@ -1,5 +1,7 @@
 """End-to-end hot path on one GPU: 16 kHz PCM -> energy VAD -> log-mel front end
-(-> CMVN) -> 20 x 80 x 40 feature cube -> C3D2 embedding -> cosine scores.
+(-> CMVN) -> 20 x 80 x 40 feature cube -> C3D2 embedding -> cosine scores.  A three-channel model (constants.DERIVATIVE:
+static, delta, delta-delta) gets its channels from the static features inside the same two steps: one statistics pass
+(`svk_delta_cmvn_stats`) and one writing pass (`svk_delta_planes`, or `svk_cube_gather_delta` on the ragged paths).
 
 This is the batched, device-resident form of what the reference does one
 utterance at a time on the host:
@@ -97,7 +99,9 @@ class VerificationPipeline:
     def __init__(self, model, use_vad=True, vad_threshold=c.VAD_ENERGY_THRESHOLD, normalize=c.NORMALIZE,
                  crop_seed=12345, micro_batch=1024, preemph_cof=None, crop_rng="reference", overlap_front=False,
                  pcm_scale=1.0 / 32768.0):
-        """model: a `model.C3D2` (one-channel cubes): its inference form is `model.fused_inference()`, seven libsvk kernels.
+        """model: a `model.C3D2` with one channel, or with three (static, delta, delta-delta features: utils.py:325-348,
+        :382-397; every method then carries [n, 3, T, 40] feature rows and [n, 3, 20, 80, 40] cubes): its inference form is
+        `model.fused_inference()`, seven libsvk kernels.  Any other channel count raises ValueError.
         crop_rng: "reference" draws crop starts on the host exactly like utils.py:372 (needs the
         per-clip frame counts on the host: one small D2H per micro-batch); "device" draws them
         in a kernel keyed by (crop_seed, global clip index) -- no host round trip.
@@ -110,6 +114,10 @@ class VerificationPipeline:
         speechpy-on-raw-int16 values.
         overlap_front: run VAD, front end, CMVN and the crop draw of micro-batch k+1 on a second HIP stream
         while the network runs on micro-batch k (device-drawn crops only)."""
+        self.channels = int(getattr(model, "num_channels", 0))
+        if self.channels not in (1, 3):
+            raise ValueError("VerificationPipeline runs C3D2 models with 1 or 3 input channels, got num_channels = %r"
+                             % (getattr(model, "num_channels", None),))
         self.eng = get_engine()
         # bench.py sets this to a list: one {kernel name: (start, end) HIP events on the launch stream, "cubes": n} per
         # micro-batch, around every network kernel
@@ -179,7 +187,13 @@ class VerificationPipeline:
         return res["voiced_len"], (res["src_frame"], res["frame_samples"])
 
     def features(self, pcm, lengths=None, gather=None):
+        """-> (feature rows, n_frames): [n, T, 40], or [n, 3, T, 40] for a three-channel model (static, delta, delta-delta,
+        each CMVN-normalised by itself with `normalize`: utils.py:385-395) -- statistics and planes straight from the static
+        features, no delta plane in between."""
         feat, n_frames, _ = self.eng.features(pcm, self.spec, lengths=lengths, gather=gather)
+        if self.channels == 3:
+            stats = self.eng.delta_cmvn_stats(feat, n_frames, variance=True) if self.normalize else None
+            return self.eng.delta_planes(feat, n_frames, stats=stats), n_frames
         if self.normalize:                                 # utils.CMVN with c.NORMALIZE (utils.py:394-395)
             self.eng.cmvn_(feat, n_frames, variance=True)
         return feat, n_frames
@@ -194,12 +208,23 @@ class VerificationPipeline:
             out[i] = self.rng.randint(int(T) - c.CUBE_FRAMES, size=c.CUBE_CROPS)
         return out
 
-    def cubes(self, feat, crop_idx):
-        return self.eng.cube_gather(feat, crop_idx, c.CUBE_FRAMES)
+    def cubes(self, feat, crop_idx, stats=None):
+        """feature rows + crop starts -> cubes [n, channels, 20, 80, 40].  Three-channel model: `feat` is either the planes
+        `features` returns ([n, 3, T, 40]: only rows move -- the planes read as 3 n clips, each clip's starts three times) or
+        STATIC features [n, T, 40] (+ `stats` of delta_cmvn_stats): the channels are formed for the cropped rows only."""
+        if self.channels == 1:
+            return self.eng.cube_gather(feat, crop_idx, c.CUBE_FRAMES, stats=stats)
+        if feat.dim() == 3:
+            return self.eng.cube_gather_delta(feat, crop_idx, c.CUBE_FRAMES, stats=stats)
+        if stats is not None:
+            raise ValueError("statistics apply to static features; planes are normalised already")
+        n, ch, T, cols = feat.shape
+        idx = self.eng.to_device(crop_idx, torch.int32).repeat_interleave(ch, dim=0)
+        return self.eng.cube_gather(feat.reshape(n * ch, T, cols), idx, c.CUBE_FRAMES).view(n, ch, idx.shape[1], c.CUBE_FRAMES, cols)
 
     def crops_and_cubes(self, pcm, first_utt=0, want_cubes=True):
         """The crop starts `embed` would draw for `pcm` ([n, 20] int32 on the host) and, with `want_cubes`, the
-        20 x 80 x 40 cubes themselves ([n, 1, 20, 80, 40], device) -- VAD, front end, CMVN, crop draw and gather only, no
+        20 x 80 x 40 cubes themselves ([n, 1, 20, 80, 40], or [n, 3, 20, 80, 40] for a three-channel model; device) -- VAD, front end, CMVN, crop draw and gather only, no
         network: what BatchNorm calibration and the parity legs feed to the CPU oracle."""
         pcm = self.eng.to_device(pcm)
         crops, cubes = [], []
@@ -212,7 +237,7 @@ class VerificationPipeline:
         return (crops, torch.cat(cubes)) if want_cubes else crops
 
     def embed_cubes(self, cubes):
-        """[n, 1, 20, 80, 40] cubes -> [n, 128]: the cube read as feature rows by the first-block kernel (no copy)."""
+        """[n, channels, 20, 80, 40] cubes -> [n, 128]: the cube read as feature rows by the first-block kernel (no copy)."""
         return self.embedder(cubes)
 
     def embed_features(self, feat, crop_idx):
@@ -236,7 +261,7 @@ class VerificationPipeline:
 
     def _front(self, chunk, first, crop_idx=None):
         """The front step of a [n, L] device chunk of uniform clips whose row 0 is clip `first`: VAD (index form, nothing
-        copied) -> front end -> CMVN -> crop starts.  Returns (feat, n_frames, crop starts)."""
+        copied) -> front end -> CMVN (three-channel model: + the delta planes) -> crop starts.  Returns (feat, n_frames, crop starts)."""
         vlen, gather = self.vad(chunk)
         feat, n_frames = self.features(chunk, vlen, gather)
         return feat, n_frames, self._crop_starts(n_frames, first, crop_idx)
@@ -370,14 +395,17 @@ class VerificationPipeline:
         (they key the crop draw).  Returns (RAW features [n, T, 40], crop starts [n, 20], CMVN statistics or None): the VAD
         copies nothing (the front end reads the kept frames where they lie, svk_frontend_run's d_src_chunk) and the
         normalisation (utils.py:382-397) is applied by the cube gather to the 20 x 80 rows the network reads, not to every row
-        of a clip.  Nothing here touches the host."""
+        of a clip.  A three-channel model gets the same RAW static features and the statistics of its three channels
+        ([n, 3, 2, 40], svk_delta_cmvn_stats): the gather forms the delta channels for the rows it copies, and no per-clip
+        plane is ever written.  Nothing here touches the host."""
         timed = partial(_timed, spans)
         dev_lens, gather = lens, None
         if self.use_vad:
             dev_lens, gather = timed("vad", lambda: self.vad(dev_buf, lengths=lens, offsets=offs, longest=longest))
         feat, n_frames, _ = timed("frontend", lambda: self.eng.features(dev_buf, self.spec, lengths=dev_lens, offsets=offs,
                                                                          max_frames=self.spec.num_frames(int(longest)), gather=gather))
-        stats = timed("cmvn", lambda: self.eng.cmvn_stats(feat, n_frames, variance=True)) if self.normalize else None
+        cmvn_stats = self.eng.delta_cmvn_stats if self.channels == 3 else self.eng.cmvn_stats
+        stats = timed("cmvn", lambda: cmvn_stats(feat, n_frames, variance=True)) if self.normalize else None
         idx = timed("crops", lambda: self.eng.draw_crops(n_frames, c.CUBE_CROPS, c.CUBE_FRAMES, self.crop_seed, 0, self.bad_clips,
                                                          utt_index=rows))
         return feat, idx, stats
@@ -393,12 +421,14 @@ class VerificationPipeline:
         def __init__(self, pipe, step, emb, order_dev, spans):
             self.pipe, self.step, self.cap = pipe, int(step), 2 * int(step)
             self.emb, self.order, self.spans = emb, order_dev, spans
+            self.channels = getattr(pipe, "channels", 1)       # 3: the ring holds three-channel cubes
             hit = getattr(pipe, "_ring_buf", None)
-            if hit is None or hit.shape[0] != self.cap:
-                hit = pipe._ring_buf = torch.empty((self.cap, 1, c.CUBE_CROPS, c.CUBE_FRAMES, c.NUM_COEF), dtype=torch.float32,
-                                                   device=pipe.eng.device)
+            if hit is None or tuple(hit.shape[:2]) != (self.cap, self.channels):
+                hit = pipe._ring_buf = torch.empty((self.cap, self.channels, c.CUBE_CROPS, c.CUBE_FRAMES, c.NUM_COEF),
+                                                   dtype=torch.float32, device=pipe.eng.device)
             self.cubes = hit
-            self.rows = hit.view(self.cap, c.CUBE_CROPS * c.CUBE_FRAMES, c.NUM_COEF)
+            # what the first block reads: [cap, 1 600, 40] rows, [cap, 3, 1 600, 40] for a three-channel model
+            self.rows = hit.view((self.cap,) + ((3,) if self.channels == 3 else ()) + (c.CUBE_CROPS * c.CUBE_FRAMES, c.NUM_COEF))
             self.at = self.done = 0            # cubes gathered / handed to the network so far (absolute counts)
 
         def push(self, feat, idx, stats=None):
@@ -407,12 +437,15 @@ class VerificationPipeline:
             w = self.at % self.cap
             first = min(n, self.cap - w)
 
+            # three-channel model: the static rows become the three-channel cube on the way (svk_cube_gather_delta)
+            cube_gather = self.pipe.eng.cube_gather_delta if self.channels == 3 else self.pipe.eng.cube_gather
+
             def gather():
-                self.pipe.eng.cube_gather(feat[:first], idx[:first], c.CUBE_FRAMES, out=self.cubes[w:w + first],
-                                          stats=None if stats is None else stats[:first])
+                cube_gather(feat[:first], idx[:first], c.CUBE_FRAMES, out=self.cubes[w:w + first],
+                            stats=None if stats is None else stats[:first])
                 if first < n:                    # the batch wraps around the end of the ring
-                    self.pipe.eng.cube_gather(feat[first:], idx[first:], c.CUBE_FRAMES, out=self.cubes[:n - first],
-                                              stats=None if stats is None else stats[first:])
+                    cube_gather(feat[first:], idx[first:], c.CUBE_FRAMES, out=self.cubes[:n - first],
+                                stats=None if stats is None else stats[first:])
             _timed(self.spans, "gather", gather)
             self.at += n
             while self.at - self.done >= self.step:
