@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only): + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
+#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only): + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
 
 typedef enum svk_status {
   SVK_OK = 0,
@@ -232,7 +232,9 @@ int svk_cube_gather_delta(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int3
  * the clip's global index.  utils.py:372 draws `np.random.randint(T - 80, size=20)` from the process-global
  * NumPy RNG instead; hosts that need that exact sequence pass their own d_crop_idx to
  * svk_cube_gather.  Clips with n_frames <= crop_frames get -1 (svk_cube_gather then emits zeros)
- * and are counted in *d_bad_count (int32, may be NULL; the caller zeroes it).               */
+ * and are counted in *d_bad_count (int32, may be NULL; the caller zeroes it).
+ * Several cubes per clip (svk_c3d2_stage1_multi) need nothing new here: n_crops = 20 K yields d_crop_idx [n_utt][K][20], still
+ * keyed by (seed, clip, c), and its first 20 starts per clip are the one-cube draw.               */
 int svk_cube_draw_crops(svk_ctx* ctx, const int32_t* d_n_frames, int32_t n_utt, int64_t first_utt,
                         const int64_t* d_utt_index, int32_t n_crops, int32_t crop_frames, uint64_t seed,
                         int32_t* d_crop_idx, int32_t* d_bad_count);
@@ -261,6 +263,31 @@ int svk_cosine_scores(svk_ctx* ctx, const float* d_test, const float* d_enroll, 
                       int32_t n_enroll, int32_t dim, float* d_out);
 /* siamese.py:29-30: out[i] = || a[i] - b[i] ||_2 */
 int svk_l2_dist(svk_ctx* ctx, const float* d_a, const float* d_b, int32_t n, int32_t dim, float* d_out);
+
+/* The mean over groups of embedding rows (csrc/pool.hip): the K cubes of a clip -> the clip's embedding, and the utterances of
+ * a speaker -> the speaker's model (the mean the d-vector method describes; the reference itself keeps a speaker's LAST
+ * utterance, model.py:374-388, Q17 -- pipeline.enroll_last_utterance).
+ *   d_emb         [n_rows][dim] f32, 4-byte aligned (16-byte loads when dim % 4 == 0 and d_emb, d_out are 16-byte aligned: same bits)
+ *   segments      d_seg_start == NULL: uniform, segment s = rows [s * rows_per_seg, (s + 1) * rows_per_seg), rows_per_seg >= 1,
+ *                 n_seg * rows_per_seg <= n_rows;  else d_seg_start int64 [n_seg + 1], CSR offsets (rows_per_seg is ignored):
+ *                 segment s = rows [start[s], start[s + 1]), non-decreasing and within [0, n_rows] -- the caller's duty, as for
+ *                 the crop starts; offsets outside that are clamped, never followed
+ *   d_row_index   NULL, or int64 [n_rows]: segment s's rows are d_emb[d_row_index[i]] for i in its range (either form) -- a
+ *                 speaker's utterances lie anywhere in d_emb.  An index outside [0, n_rows) is the caller's error: it is not
+ *                 read, and its segment comes out NaN
+ *   flags         bit 0 (1): every row enters as x / ||x||, a row of norm zero as zeros;  bit 1 (2): the mean leaves divided
+ *                 by its own norm, a zero mean stays zero;  every other bit must be 0
+ *   d_out         [n_seg][dim] f32 = (float)(sum / count);  an EMPTY segment writes zeros and adds 1 to *d_empty_count (int32,
+ *                 may be NULL; the caller zeroes it)
+ * Sums, norms and divisions are float64; NaN propagates to its own segment and no other.  The order of additions in a segment
+ * depends on that segment's length alone (rows in order inside blocks of 64 rows, the blocks' partial sums in order), not on
+ * n_seg, the launch geometry or the other segments: runs are bit-identical, and a segment pooled alone gives the bits it gives
+ * inside a batch.  One team of threads per segment, eight segments of dim 128 per workgroup: many short segments are the
+ * case it is laid out for.  1 <= dim <= 4096; n_seg == 0 launches nothing.  SVK_ERR_BAD_ARG: NULL context or buffer, negative
+ * size, dim outside [1, 4096], rows_per_seg < 1 or n_seg * rows_per_seg > n_rows (uniform form), misalignment, undefined flag bits. */
+int svk_embedding_pool(svk_ctx* ctx, const float* d_emb, int64_t n_rows, int32_t dim, int64_t n_seg, int32_t rows_per_seg,
+                       const int64_t* d_seg_start, const int64_t* d_row_index, int32_t flags, float* d_out,
+                       int32_t* d_empty_count);
 
 /* ---- ROC / EER / AUC on the device ------------------------------------------------------------
  * evaluation.py:47-52 (sklearn roc_curve + roc_auc_score + brentq on interp1d) for pair sets too
@@ -346,6 +373,27 @@ int svk_c3d2_stage1_c3(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t
                        const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, const void* d_w1blk,
                        const float* d_bias1, const float* d_slope1, const void* d_w2blk, const float* d_bias2,
                        const float* d_slope2, int32_t flags, float* d_out);
+
+/* K CUBES PER CLIP: the two first-block entries above with one more argument, cubes_per_clip = K >= 1.  A cube is 20 random
+ * 0.8 s crops, so one cube stands for at most 16 s of a clip that may run to 145 s; K cubes of the same clip read the same
+ * feature rows with K sets of crop starts, without those rows being copied K times:
+ *   d_feat      [n_clips][max_frames][40] (svk_c3d2_stage1_multi) or [n_clips][3][max_frames][40] (svk_c3d2_stage1_c3_multi)
+ *   d_crop_idx  [n_clips][K][20]: cube u = K clip + k reads clip u / K with the starts d_crop_idx[u][0 .. 19]
+ *   d_out       [n_clips * K][16][36][18][16]: cube-major, what svk_c3d2_stage2 takes (cubes are independent from here on;
+ *               svk_embedding_pool with rows_per_seg = K turns the K embeddings of a clip into one)
+ * Everything else -- tables, flags, alignment, the half-pair domain, starts outside the clip -- as for the parent entry, and
+ * every check of the parent applies to the cube count n_clips * K.  The output is bit-identical to the parent entry fed with
+ * each clip's rows repeated K times (K = 1: to the parent entry itself); the parents' own kernels are untouched (the K-cube form
+ * is a separate instance of the same kernel: it differs in where the feature-row base is formed, nothing else).
+ * cubes_per_clip < 1 -> SVK_ERR_BAD_ARG. */
+int svk_c3d2_stage1_multi(svk_ctx* ctx, const float* d_feat, int32_t n_clips, int32_t max_frames, int32_t n_cols,
+                          const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, const void* d_w1blk,
+                          const float* d_bias1, const float* d_slope1, const void* d_w2blk, const float* d_bias2,
+                          const float* d_slope2, int32_t flags, float* d_out, int32_t cubes_per_clip);
+int svk_c3d2_stage1_c3_multi(svk_ctx* ctx, const float* d_feat, int32_t n_clips, int32_t max_frames, int32_t n_cols,
+                             const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, const void* d_w1blk,
+                             const float* d_bias1, const float* d_slope1, const void* d_w2blk, const float* d_bias2,
+                             const float* d_slope2, int32_t flags, float* d_out, int32_t cubes_per_clip);
 
 /* The second block, model.py:119-124 + :151-158: conv2_1 (16 -> 32, kernel (3,1,4)) -> BN -> PReLU -> conv2_2
  * (32 -> 32, kernel (3,8,1), stride (1,2,1)) -> BN -> PReLU -> MaxPool3d((1,1,2)), two kernels on v_mfma_f32_16x16x32_f16

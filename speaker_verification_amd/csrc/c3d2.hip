@@ -49,8 +49,8 @@ constexpr int DIN = TD + 2;                          // act1 depths per item
 constexpr int PD = TD + 4;                           // cube patch depths per item
 constexpr int OD = 16, OH = 36, OWP = 18;            // output: depths, rows, pooled columns
 // output strides (floats) of [n][16 d][36 h][18 w][16 c] (channels-last memory of a (n, 16, 16, 36, 18) tensor): pooled column,
-// row parity, row pair, depth, cube.  Compile-time: as kernel parameters they were 64-bit scalar multiplies per item
-constexpr int S_W = 16, S_PAR = OWP * 16, S_HP = 2 * OWP * 16, S_D = OH * OWP * 16, S_N = OD * OH * OWP * 16;
+// row parity, depth, cube.  Compile-time: as kernel parameters they were 64-bit scalar multiplies per item
+constexpr int S_W = 16, S_PAR = OWP * 16, S_D = OH * OWP * 16, S_N = OD * OH * OWP * 16;
 // A work item (cube u, rem = 18 q + j: half q of the output depths, pooled column j), decoded ONCE when its index is known (two
 // items ahead) and handed down: item / 36, % 36, / 18 for the item, the next one (patch fetch) and the one after (crop starts)
 // were three division chains of scalar instructions per item, in front of the barrier where nothing hides them.
@@ -77,6 +77,7 @@ struct Stage1Params {
   const float* slope2;
   float* out;
   unsigned* queue;
+  int32_t cubes_per_clip;   // the *_multi entries (MULTI instances of the kernel) only: cube u reads the feature rows of clip u / K
 };
 
 // a per-thread constant plus an immediate.
@@ -220,15 +221,26 @@ constexpr int conv12_unit_step(int n) { return n < 8 ? n / 4 : 2 + (n - 8) / 6; 
 constexpr int conv12_unit_sub(int n) { return n < 8 ? n % 4 : (n - 8) % 6; }   // 0 .. 3: pair m of the step; 4, 5: pairs 12, 13
 static_assert(2 * CONV12_CHAIN == TD, "two chains cover an item's output depths");
 
+// Where an item's feature rows lie: the item with u = the CLIP its cube reads -- the cube itself, or cube / K for the K cubes per
+// clip of svk_c3d2_stage1_multi / svk_c3d2_stage1_c3_multi (a MULTI instance of the kernel: the one-cube-per-clip instances carry
+// no division).  dma_patch_w and dma_patch_plane form the row base from it (plane = 3 clip + c); the crop table and the output
+// stay indexed by the cube.
+template <bool MULTI>
+__device__ __forceinline__ ItemPos feat_pos(const Stage1Params& p, ItemPos it) {
+  if constexpr (MULTI) it.u = (int)((unsigned)it.u / (unsigned)p.cubes_per_clip);
+  return it;
+}
+
 // A lane's place in the workgroup of eight waves: lane = 16 kk + i, wave = 4 part + pair (wave-uniform).  Part 0 are the four
 // OLDER waves, which fetch and convert the patches (see dma_patch_w)
 struct Lane1 { int lane, wave, i, kk, pair, part; };
 
 // the item's channel-0 patch (the one-channel kernel's only one): plane NCH u of [n][NCH][max_frames][40]
-template <int NCH>
+template <int NCH, bool MULTI>
 __device__ __forceinline__ void dma_patch_ch0(const Stage1Params& p, ItemPos it, int starts_v, const Lane1& L, float* patch) {
-  if constexpr (NCH == 1) dma_patch_w(p, it, starts_v, L.pair, L.lane, patch);
-  else dma_patch_plane(p, it, (int64_t)NCH * it.u, starts_v, L.pair, L.lane, patch);
+  const ItemPos src = feat_pos<MULTI>(p, it);
+  if constexpr (NCH == 1) dma_patch_w(p, src, starts_v, L.pair, L.lane, patch);
+  else dma_patch_plane(p, src, (int64_t)NCH * src.u, starts_v, L.pair, L.lane, patch);
 }
 
 // ---- phase 1: the patch at `buf` in place, f32 -> (l << 16 | h) words: by the wave that FETCHED the words (its own vmcnt(0) is
@@ -315,14 +327,15 @@ __device__ __forceinline__ void conv11_chan_pass(const unsigned* src, int pov, i
 // The three-channel form, with its two barriers: channel 0 from the patch buffer; channels 1 and 2 of this item -> the act1 tile's
 // first 2 x 30 KB (nobody reads act1 between the last item's final barrier and this item's epilogue), by the waves that fetch
 // channel 0; they land while channel 0 is multiplied
-template <bool SLOPE01, int NCH>
+template <bool SLOPE01, int NCH, bool MULTI>
 __device__ __forceinline__ void conv11_three_channels(const Stage1Params& p, ItemPos cur, int starts_cur, unsigned* act, const float* patch,
                                                       int pov, int poh, unsigned* aw, const Lane1& L, f32x4 bias, f32x4 slope) {
   float* const chan12 = reinterpret_cast<float*>(act);
   if (L.part == 0) {
+    const ItemPos src = feat_pos<MULTI>(p, cur);
 #pragma unroll
     for (int ch = 1; ch < NCH; ++ch)
-      dma_patch_plane(p, cur, (int64_t)NCH * cur.u + ch, starts_cur, L.pair, L.lane, chan12 + (ch - 1) * WP_FLOATS);
+      dma_patch_plane(p, src, (int64_t)NCH * src.u + ch, starts_cur, L.pair, L.lane, chan12 + (ch - 1) * WP_FLOATS);
   }
   f32x4 acc[13];   // tile wave + 8 m; m = 12 for waves 0 - 3 only
   // conv1_1's weight blocks are gathered per item (L1-resident, 16 halves per lane per channel): held across the item loop as
@@ -462,7 +475,8 @@ __device__ __forceinline__ void conv12_chain(const unsigned* act, const u32x4 (&
 // item's patch, then the item loop over phases 2 - 4 with phase 1 of the NEXT item inside.  Items: `item` is multiplied, item1's
 // patch is fetched (crop starts: `starts`), item2's crop starts are fetched, item3 is drawn from the device-wide counter.
 // (NCH = 3 keeps conv1_2's tile loop: with 13 conv1_1 accumulators behind it the chain takes its spill from 6 to 16 VGPRs)
-template <bool SLOPE01, int NCH = 1>
+// MULTI: p.n_utt counts CUBES, K = p.cubes_per_clip of them per clip's feature rows (feat_pos); nothing else differs.
+template <bool SLOPE01, int NCH = 1, bool MULTI = false>
 __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p) {
   constexpr bool CONV12_CHAINS = NCH == 1;
   extern __shared__ __attribute__((aligned(16))) float smem_c3d2[];
@@ -488,7 +502,7 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
   ItemPos cur = ItemPos::of(item), nx = ItemPos::of(item1), nx2 = ItemPos::of(item2);
   if (item < n_items) {
     starts = fetch_starts(p, cur, lane);
-    if (L.part == 0) dma_patch_ch0<NCH>(p, cur, starts, L, patch);
+    if (L.part == 0) dma_patch_ch0<NCH, MULTI>(p, cur, starts, L, patch);
     starts_cur = starts;
     if (item1 < n_items) starts = fetch_starts(p, nx, lane);
   }
@@ -505,14 +519,14 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
     if constexpr (NCH == 1)
       conv11_one_channel<SLOPE01>(reinterpret_cast<const unsigned*>(patch), pov, poh, aw, L, W1a, W1b, b1v, sl1v);
     else
-      conv11_three_channels<SLOPE01, NCH>(p, cur, starts_cur, act, patch, pov, poh, aw, L, b1v, sl1v);
+      conv11_three_channels<SLOPE01, NCH, MULTI>(p, cur, starts_cur, act, patch, pov, poh, aw, L, b1v, sl1v);
     if (threadIdx.x == 0) q_item3 = p.queue ? (int)q_ticket + 3 * (int)gridDim.x : item2 + (int)gridDim.x;
     __syncthreads();   // act1 is complete; the patch buffer is free
     const int item3 = q_item3;
 
     // ---- the next item's patch (it lands inside this item's conv1_2), the crop starts of the one after ----
     if (L.part == 0 && next < n_items) {
-      dma_patch_ch0<NCH>(p, nx, starts, L, patch);
+      dma_patch_ch0<NCH, MULTI>(p, nx, starts, L, patch);
       starts_cur = starts;
       if (item2 < n_items) starts = fetch_starts(p, nx2, lane);
     }
@@ -544,14 +558,20 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
   }
 }
 
-// svk_c3d2_stage1 (NCH = 1) and svk_c3d2_stage1_c3 (NCH = 3): the same arguments, checks and launch
-template <int NCH>
-int stage1(svk_ctx* ctx, const char* name, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
+// svk_c3d2_stage1 (NCH = 1) and svk_c3d2_stage1_c3 (NCH = 3): the same arguments, checks and launch.  Their *_multi forms
+// (MULTI) take `n_clips` feature matrices and K = cubes_per_clip cubes of each: every check below then applies to the cube count
+// n_clips K, which is what the kernel calls n_utt.
+template <int NCH, bool MULTI = false>
+int stage1(svk_ctx* ctx, const char* name, const float* d_feat, int32_t n_clips, int32_t max_frames, int32_t n_cols,
            const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, const void* d_w1blk, const float* d_bias1,
-           const float* d_slope1, const void* d_w2blk, const float* d_bias2, const float* d_slope2, int32_t flags, float* d_out) {
+           const float* d_slope1, const void* d_w2blk, const float* d_bias2, const float* d_slope2, int32_t flags, float* d_out,
+           int32_t cubes_per_clip = 1) {
   if (!ctx) return SVK_ERR_BAD_ARG;
   SVK_REQUIRE(ctx, (flags & ~2) == 0, "flags: only bit 1 (slopes in [0, 1]) is defined");
-  SVK_REQUIRE(ctx, n_utt >= 0 && max_frames >= 1, "shape");
+  SVK_REQUIRE(ctx, cubes_per_clip >= 1, "cubes_per_clip must be at least 1");
+  SVK_REQUIRE(ctx, n_clips >= 0 && max_frames >= 1, "shape");
+  SVK_REQUIRE(ctx, (int64_t)n_clips * cubes_per_clip <= INT32_MAX, "too many cubes for one launch");   // (the item count: below)
+  const int32_t n_utt = n_clips * cubes_per_clip;
   if (n_cols != NCOEF || n_crops != NCROP || crop_frames != NFRAME)
     return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "%s is built for the %s20 x 80 x 40 cube of utils.py:%s (got %d x %d x %d)", name,
                     NCH == 3 ? "3 x " : "", NCH == 3 ? "325-348" : "20-21", n_crops, crop_frames, n_cols);
@@ -574,7 +594,8 @@ int stage1(svk_ctx* ctx, const char* name, const float* d_feat, int32_t n_utt, i
   p.bias2 = d_bias2;
   p.slope2 = d_slope2;
   p.out = d_out;
-  void (*kern)(const Stage1Params) = (flags & 2) ? c3d2_stage1h_kernel<true, NCH> : c3d2_stage1h_kernel<false, NCH>;
+  p.cubes_per_clip = cubes_per_clip;
+  void (*kern)(const Stage1Params) = (flags & 2) ? c3d2_stage1h_kernel<true, NCH, MULTI> : c3d2_stage1h_kernel<false, NCH, MULTI>;
   unsigned grid;
   if (int rc = svk_persistent_grid(ctx, name, kern, svk_c3d2_stage1_lds_bytes(), 512, 1, (int64_t)n_utt * 36, &grid)) return rc;
   if (int rc = svk_work_queue(ctx, SVK_SLOT_STAGE1, 1, &p.queue)) return rc;
@@ -606,6 +627,22 @@ int svk_c3d2_stage1_c3(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t
                        const float* d_slope2, int32_t flags, float* d_out) {
   return stage1<3>(ctx, "svk_c3d2_stage1_c3", d_feat, n_utt, max_frames, n_cols, d_crop_idx, n_crops, crop_frames, d_w1blk,
                    d_bias1, d_slope1, d_w2blk, d_bias2, d_slope2, flags, d_out);
+}
+
+int svk_c3d2_stage1_multi(svk_ctx* ctx, const float* d_feat, int32_t n_clips, int32_t max_frames, int32_t n_cols,
+                          const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, const void* d_w1blk,
+                          const float* d_bias1, const float* d_slope1, const void* d_w2blk, const float* d_bias2,
+                          const float* d_slope2, int32_t flags, float* d_out, int32_t cubes_per_clip) {
+  return stage1<1, true>(ctx, "svk_c3d2_stage1_multi", d_feat, n_clips, max_frames, n_cols, d_crop_idx, n_crops, crop_frames, d_w1blk,
+                         d_bias1, d_slope1, d_w2blk, d_bias2, d_slope2, flags, d_out, cubes_per_clip);
+}
+
+int svk_c3d2_stage1_c3_multi(svk_ctx* ctx, const float* d_feat, int32_t n_clips, int32_t max_frames, int32_t n_cols,
+                             const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, const void* d_w1blk,
+                             const float* d_bias1, const float* d_slope1, const void* d_w2blk, const float* d_bias2,
+                             const float* d_slope2, int32_t flags, float* d_out, int32_t cubes_per_clip) {
+  return stage1<3, true>(ctx, "svk_c3d2_stage1_c3_multi", d_feat, n_clips, max_frames, n_cols, d_crop_idx, n_crops, crop_frames,
+                         d_w1blk, d_bias1, d_slope1, d_w2blk, d_bias2, d_slope2, flags, d_out, cubes_per_clip);
 }
 
 }  // extern "C"

@@ -524,12 +524,14 @@ class Engine:
                                              int(delta), self._ptr(stats), self._ptr(out)), self.ctx)
         return out
 
-    def c3d2_stage1(self, feat, crop_idx, tables, crop_frames=80):
+    def c3d2_stage1(self, feat, crop_idx, tables, crop_frames=80, cubes_per_clip=1):
         """svk_c3d2_stage1: feature rows [n, T, 40] + crop starts [n, 20] -> the activation after C3D2's first block (conv1_1,
         conv1_2, pool1 with their BN + PReLU): [n, 16, 36, 18, 16] f32, channels last.  Two-piece f16 products on
         v_mfma_f32_16x16x32_f16 (x = h + l, three piece products per f32 product, f32 accumulation: ~1e-6 of the scale from the
         f32 form); tables: `FusedEmbedder.stage1_tables()`.  The tables of a three-channel model (conv1_1 block [3, 2, 64, 8])
-        run svk_c3d2_stage1_c3 on feature rows [n, 3, T, 40] (static, delta, delta-delta) instead: the same output layout."""
+        run svk_c3d2_stage1_c3 on feature rows [n, 3, T, 40] (static, delta, delta-delta) instead: the same output layout.
+        cubes_per_clip = K > 1 (or crop starts [n, K, 20]): K cubes of every clip's rows through svk_c3d2_stage1_multi /
+        svk_c3d2_stage1_c3_multi -> [n K, 16, 36, 18, 16], cube-major; K = 1 with [n, 20] starts runs the entries above."""
         torch = _torch()
         feat = self.to_device(feat, torch.float32)
         idx = self.to_device(crop_idx, torch.int32)
@@ -538,11 +540,23 @@ class Engine:
             raise ValueError("these stage-1 tables take feature rows %s, got %s"
                              % ("[n, 3, T, cols]" if three else "[n, T, cols]", tuple(feat.shape)))
         n, T, Cc = feat.shape[0], feat.shape[-2], feat.shape[-1]
-        if idx.dim() != 2 or idx.shape[0] != n:
+        K = int(cubes_per_clip)
+        multi = idx.dim() == 3 or K != 1
+        if multi and K >= 1:              # (K < 1 goes to the library as it is: SVK_ERR_BAD_ARG)
+            if idx.dim() == 2 and idx.shape[0] == n and idx.shape[1] % K == 0:
+                idx = idx.view(n, K, -1)              # [n, 20 K], as draw_crops(n_crops=20 K) returns it
+            if idx.dim() != 3 or idx.shape[0] != n or idx.shape[1] < 1 or (K != 1 and idx.shape[1] != K):
+                raise ValueError("crop_idx must be [n, K, n_crops] for K cubes of each of the n = %d clips, got %s" % (n, tuple(idx.shape)))
+            K = int(idx.shape[1])
+        elif not multi and (idx.dim() != 2 or idx.shape[0] != n):
             raise ValueError("crop_idx must be [n, n_crops] for the n = %d cubes, got %s" % (n, tuple(idx.shape)))
         layers = self._c3d2_layers(tables, ((3, 2, 64, 8) if three else (2, 64, 8), (14, 2, 64, 8)), torch.float16, 16)
-        out = torch.empty((n, 16, 36, 18, 16), dtype=torch.float32, device=self.device)
+        out = torch.empty((n * max(K, 0), 16, 36, 18, 16), dtype=torch.float32, device=self.device)
         self._stream()
+        if multi:
+            fn = self.lib.svk_c3d2_stage1_c3_multi if three else self.lib.svk_c3d2_stage1_multi
+            check(fn(self.ctx, self._ptr(feat), n, T, Cc, self._ptr(idx), idx.shape[-1], crop_frames, *layers, self._ptr(out), K), self.ctx)
+            return out
         fn = self.lib.svk_c3d2_stage1_c3 if three else self.lib.svk_c3d2_stage1
         check(fn(self.ctx, self._ptr(feat), n, T, Cc, self._ptr(idx), idx.shape[1], crop_frames, *layers, self._ptr(out)), self.ctx)
         return out
@@ -731,6 +745,46 @@ class Engine:
         check(self.lib.svk_top1(self.ctx, self._ptr(sc), n_rows, n_cols, self._ptr(tr), self._ptr(amax), self._ptr(labels),
                                 C.byref(correct)), self.ctx)
         return (amax, int(correct.value), labels) if want_labels else (amax, int(correct.value))
+
+    def embedding_pool(self, emb, rows_per_seg=None, seg_start=None, row_index=None, l2_rows=False, l2_mean=False,
+                       empty_count=None):
+        """svk_embedding_pool: the float64 mean over groups of the rows of emb [n_rows, dim] -> [n_seg, dim] f32.  Groups:
+        `rows_per_seg` = K consecutive rows each (n_rows a multiple of K), or `seg_start` int64 [n_seg + 1] CSR offsets; with
+        `row_index` int64 [n_rows] the rows of a group are emb[row_index[i]] over its range.  l2_rows: every row enters
+        L2-normalised; l2_mean: the mean leaves L2-normalised.  empty_count: an int32 [1] device tensor (the caller zeroes it)
+        that takes the number of empty groups, which come out as zeros."""
+        torch = _torch()
+        x = self.to_device(emb, torch.float32)
+        if x.dim() != 2:
+            raise ValueError("embedding_pool wants rows (n_rows, dim)")
+        n_rows, dim = int(x.shape[0]), int(x.shape[1])
+        if (rows_per_seg is None) == (seg_start is None):
+            raise ValueError("embedding_pool wants either rows_per_seg or seg_start")
+        start, K = None, 0
+        if seg_start is not None:
+            start = self.to_device(seg_start, torch.int64).reshape(-1)
+            if start.numel() < 1:
+                raise ValueError("seg_start holds n_seg + 1 offsets")
+            n_seg = start.numel() - 1
+        else:
+            K = int(rows_per_seg)
+            if K < 1 or n_rows % K:
+                raise ValueError("rows_per_seg = %d does not divide the %d rows" % (K, n_rows))
+            n_seg = n_rows // K
+        index = None
+        if row_index is not None:
+            index = self.to_device(row_index, torch.int64).reshape(-1)
+            if index.numel() != n_rows:
+                raise ValueError("row_index holds one entry per row of emb")
+        if empty_count is not None and not (isinstance(empty_count, torch.Tensor) and empty_count.is_cuda
+                                            and empty_count.dtype == torch.int32 and empty_count.numel() >= 1):
+            raise ValueError("empty_count must be an int32 device tensor")
+        out = torch.empty((n_seg, dim), dtype=torch.float32, device=self.device)
+        self._stream()
+        check(self.lib.svk_embedding_pool(self.ctx, self._ptr(x), n_rows, dim, n_seg, K, self._ptr(start), self._ptr(index),
+                                          int(bool(l2_rows)) | 2 * int(bool(l2_mean)), self._ptr(out), self._ptr(empty_count)),
+              self.ctx)
+        return out
 
     def l2_dist(self, a, b):
         torch = _torch()

@@ -301,7 +301,16 @@ def _evaluate_files(k, plot_path, device=False):
             "speaker_ids": speaker_model_ids, "test_ids": [f[0:7] for f in dataset.sound_files]}
 
 
-def evaluate(model=None, cubes=None, test_ids=None, speaker_models=None, k=1, plot_path='eer_auc.png', device=False):
+def create_speaker_models(model=None, cubes=None, speaker_ids=None, save_dir=None, batch=256, enroll="last"):
+    """`model.create_speaker_models` (model.py:351-388) under this module's name: enroll="last" keeps each speaker's last
+    listed utterance, as the reference does (Q17); enroll="mean" takes the mean of the speaker's L2-normalised utterance
+    embeddings (`pipeline.enroll_mean`).  `evaluate(..., enroll_cubes=, enroll_ids=, enroll=)` enrols through it."""
+    from .model import create_speaker_models as _create
+    return _create(model, cubes, speaker_ids, save_dir, batch, enroll=enroll)
+
+
+def evaluate(model=None, cubes=None, test_ids=None, speaker_models=None, k=1, plot_path='eer_auc.png', device=False,
+             enroll="last", enroll_cubes=None, enroll_ids=None):
     """`evaluate()` -- no arguments, like evaluation.py:90-146: read the checkpoint, the id list, the WAVs and
     the enrolled `{id}.pt` models from the paths in `constants`, score every utterance against every
     enrolled speaker (one batched front end + network + ONE cosine launch instead of the reference's
@@ -311,9 +320,17 @@ def evaluate(model=None, cubes=None, test_ids=None, speaker_models=None, k=1, pl
     device=True: the score matrix never leaves the GPU.  Accuracy comes from `svk_top1`, EER / AUC from ONE `svk_roc_k`
     call, the labels from the enrolled column of each test id (-1, an all-zero row, for an id never enrolled); the
     per-utterance lines are printed from the argmax indices.  `scores` and `labels` are then the DEVICE tensors
-    (float32 [n_test, n_speakers], uint8 one-hot)."""
+    (float32 [n_test, n_speakers], uint8 one-hot).
+    Without `speaker_models`, the in-memory form enrols `enroll_cubes` / `enroll_ids` itself through
+    `create_speaker_models(..., enroll=enroll)`: "last" (the reference, the default) or "mean"."""
+    if enroll not in ("last", "mean"):
+        raise ValueError("enroll must be 'last' or 'mean', got %r" % (enroll,))
     if model is None and cubes is None:
         return _evaluate_files(k, plot_path, device)
+    if speaker_models is None:
+        if enroll_cubes is None or enroll_ids is None:
+            raise ValueError("evaluate needs speaker_models, or enroll_cubes and enroll_ids to enrol from")
+        speaker_models = create_speaker_models(model, enroll_cubes, enroll_ids, enroll=enroll)
     ev = Evaluation(model, speaker_models)
     speaker_ids = list(ev.speaker_models.keys())
     if device:

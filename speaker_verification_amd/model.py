@@ -281,18 +281,45 @@ class FusedEmbedder:
         return hit
 
     @torch.no_grad()
-    def embed_features(self, feat, crop_idx, timed=None):
+    def embed_features(self, feat, crop_idx, timed=None, pool=None):
         """feature rows [n, T, 40] (one-channel model) or [n, 3, T, 40] (three-channel: static, delta, delta-delta) + crop
         starts [n, 20] -> embeddings [n, 128].  The cube (utils.py:351-379, :325-348) is never materialised: the first-block
         kernel gathers its patches from the feature rows.  `timed(name, fn)`: the pipeline's HIP-event hook around each
-        kernel (bench.py)."""
+        kernel (bench.py).
+        Crop starts [n, K, 20]: K cubes of every clip, read from the clip's one set of rows (svk_c3d2_stage1_multi) ->
+        [n, K, 128], each row what the [n, 20] call with crop_idx[:, k] gives; with pool="mean" (the float64 mean of a clip's K
+        embeddings) or "mean_l2" (of its L2-normalised embeddings) -> [n, 128] (svk_embedding_pool)."""
         run = timed or (lambda name, fn: fn())
         eng = self.eng
+        if pool not in (None, "mean", "mean_l2"):
+            raise ValueError("pool must be None, 'mean' or 'mean_l2', got %r" % (pool,))
+        if getattr(crop_idx, "ndim", 2) == 3:
+            K = int(crop_idx.shape[1])
+            if K < 1:
+                raise ValueError("crop starts [n, K, 20] need K >= 1")
+            emb = self._embed_multi(feat, crop_idx, run)
+            if pool is None:
+                return emb.view(-1, K, EMBED_DIM)
+            return run("pool", lambda: eng.embedding_pool(emb, rows_per_seg=K, l2_rows=pool == "mean_l2"))
+        self._check_rows(feat)
+        return self._network(run, lambda: eng.c3d2_stage1(feat, crop_idx, self.stage1_tables()))
+
+    def _check_rows(self, feat):
         want = 3 if self.num_channels == 1 else 4
         if feat.dim() != want or (want == 4 and feat.shape[1] != self.num_channels):
             raise ValueError("this %d-channel model embeds feature rows of shape %s, got %s"
                              % (self.num_channels, "[n, T, 40]" if want == 3 else "[n, 3, T, 40]", tuple(feat.shape)))
-        y = run("stage1", lambda: eng.c3d2_stage1(feat, crop_idx, self.stage1_tables()))
+
+    def _embed_multi(self, feat, crop_idx, run):
+        """[n, K, 20] crop starts -> [n K, 128], cube-major: the first block reads clip u / K for cube u, the other six kernels
+        see n K independent cubes."""
+        self._check_rows(feat)
+        return self._network(run, lambda: self.eng.c3d2_stage1(feat, crop_idx, self.stage1_tables(), cubes_per_clip=int(crop_idx.shape[1])))
+
+    def _network(self, run, stage1):
+        """The seven kernels behind `stage1()`, each through the timing hook."""
+        eng = self.eng
+        y = run("stage1", stage1)
         z = run("stage2", lambda: eng.c3d2_stage2(y, self.stage2_tables()))
         y = run("conv3_1", lambda: eng.c3d2_conv31(z, self.conv31_tables()))
         y = run("conv3_2", lambda: eng.c3d2_conv32t(y, self.conv32t_tables()))
@@ -515,10 +542,33 @@ def perturb_inference_state(state_dict, seed):
     return state_dict
 
 
-def _create_speaker_models_files():
+def _enrolled(emb, speaker_ids, enroll):
+    """{speaker id: (1, 128) CPU tensor} from utterance embeddings [n, 128] (device or host) and their ids: enroll="last" keeps
+    each speaker's LAST listed utterance (the reference, Q17), "mean" the mean of the speaker's L2-normalised utterance
+    embeddings (pipeline.enroll_mean: one svk_embedding_pool launch)."""
+    if enroll not in ("last", "mean"):
+        raise ValueError("enroll must be 'last' or 'mean', got %r" % (enroll,))
+    ids = [str(v) for v in speaker_ids]
+    if enroll == "mean":
+        from .pipeline import enroll_mean
+        uniq, models = enroll_mean(emb, ids, l2=True)
+        models = models.cpu()
+        first = {}
+        for k, sid in enumerate(ids):           # the dict keeps the order in which speakers were first listed, as "last" does
+            first.setdefault(sid, k)
+        rows = {str(sid): models[k:k + 1].clone() for k, sid in enumerate(uniq)}
+        return {sid: rows[sid] for sid in first}
+    emb = emb.cpu()
+    store = {}
+    for i, sid in enumerate(ids):
+        store[sid] = emb[i:i + 1].clone()
+    return store
+
+
+def _create_speaker_models_files(enroll="last"):
     """model.py:351-388 as written: checkpoint, enrolment list, id table and WAV tree under
     `constants.ROOT` / `constants.DATA_ORIGIN`; one `{speaker_id}.pt` (a (1, 128) tensor) per
-    speaker under ROOT/speaker_models, the LAST listed utterance winning (Q17)."""
+    speaker under ROOT/speaker_models, the LAST listed utterance winning (Q17) -- or, with enroll="mean", the speaker's mean."""
     import os
     from . import constants as c
     from .evaluation import dataset_embeddings, load_indexed_labels
@@ -531,35 +581,41 @@ def _create_speaker_models_files():
     if not os.path.exists(save_speaker_models_path):
         os.mkdir(save_speaker_models_path)
     model = C3D2(100, 1).load_checkpoint(torch.load(model_path, map_location="cpu", weights_only=True))
-    emb = dataset_embeddings(dataset, model).cpu()
-    store = {}
-    for i in range(len(dataset)):
-        store[dataset.sound_files[i][0:7]] = emb[i:i + 1].clone()
+    store = _enrolled(dataset_embeddings(dataset, model), [f[0:7] for f in dataset.sound_files], enroll)
     for sid, vec in store.items():
         torch.save(vec, '{}/{}.pt'.format(save_speaker_models_path, sid))
     return store
 
 
-def create_speaker_models(model=None, cubes=None, speaker_ids=None, save_dir=None, batch=256):
+def create_speaker_models(model=None, cubes=None, speaker_ids=None, save_dir=None, batch=256, enroll="last"):
     """Enrolment as `/root/reference/model.py:351-388` does it.  With no arguments: file-driven, the
     paths of `constants` (see `_create_speaker_models_files`).  With `(model, cubes, speaker_ids)`: the
     same on in-memory cubes.  Every utterance cube is embedded
     with `development=False`; the speaker model is the embedding of that speaker's LAST listed
     utterance -- the reference overwrites `{speaker_id}.pt` on each utterance, no averaging
     (Q17).  Returns `{speaker_id: (1, 128) CPU tensor}` and, with `save_dir`, writes the
-    reference's `{speaker_id}.pt` files (readable by `evaluation.Evaluation`)."""
+    reference's `{speaker_id}.pt` files (readable by `evaluation.Evaluation`).
+    enroll="mean": the speaker model is the mean of the speaker's L2-normalised utterance embeddings instead
+    (`pipeline.enroll_mean`, on the device); the default "last" is the reference's behaviour, unchanged."""
     import os
+    if enroll not in ("last", "mean"):
+        raise ValueError("enroll must be 'last' or 'mean', got %r" % (enroll,))
     if model is None and cubes is None:
-        return _create_speaker_models_files()
+        return _create_speaker_models_files(enroll)
     device = next(model.parameters()).device
     model.eval()
-    store = {}
+    store, rows = {}, []
     with torch.no_grad():
         for lo in range(0, len(cubes), batch):
             x = torch.as_tensor(cubes[lo:lo + batch], dtype=torch.float32).to(device)
+            if enroll == "mean":
+                rows.append(model(x, development=False))
+                continue
             emb = model(x, development=False).cpu()
             for k in range(emb.shape[0]):
                 store[str(speaker_ids[lo + k])] = emb[k:k + 1].clone()
+    if enroll == "mean":
+        store = _enrolled(torch.cat(rows), speaker_ids[:len(cubes)], "mean") if rows else {}
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
         for sid, vec in store.items():

@@ -95,10 +95,26 @@ class _Upload:
         self.worker.join()
 
 
+def clips_per_chunk(micro_batch, cubes_per_clip):
+    """`micro_batch` counts CUBES (it sizes the network's launches); with K cubes per clip a chunk holds micro_batch // K clips,
+    at least one."""
+    return max(1, int(micro_batch) // int(cubes_per_clip))
+
+
+def speaker_segments(speaker_ids):
+    """The host half of `enroll_mean`: (sorted unique ids, CSR offsets int64 [S + 1], row index int64 [n]) -- speaker s's
+    utterances are rows row_index[seg_start[s] : seg_start[s + 1]], in the order they were listed (a stable sort of the ids)."""
+    speaker_ids = np.asarray(speaker_ids)
+    row_index = np.argsort(speaker_ids, kind="stable").astype(np.int64)
+    uniq, counts = np.unique(speaker_ids, return_counts=True)
+    seg_start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return uniq, seg_start, row_index
+
+
 class VerificationPipeline:
     def __init__(self, model, use_vad=True, vad_threshold=c.VAD_ENERGY_THRESHOLD, normalize=c.NORMALIZE,
                  crop_seed=12345, micro_batch=1024, preemph_cof=None, crop_rng="reference", overlap_front=False,
-                 pcm_scale=1.0 / 32768.0):
+                 pcm_scale=1.0 / 32768.0, cubes_per_clip=1, pool="mean"):
         """model: a `model.C3D2` with one channel, or with three (static, delta, delta-delta features: utils.py:325-348,
         :382-397; every method then carries [n, 3, T, 40] feature rows and [n, 3, 20, 80, 40] cubes): its inference form is
         `model.fused_inference()`, seven libsvk kernels.  Any other channel count raises ValueError.
@@ -113,7 +129,13 @@ class VerificationPipeline:
         default reproduces it (a power of two folded into the filterbank weights: exact); 1.0 gives
         speechpy-on-raw-int16 values.
         overlap_front: run VAD, front end, CMVN and the crop draw of micro-batch k+1 on a second HIP stream
-        while the network runs on micro-batch k (device-drawn crops only)."""
+        while the network runs on micro-batch k (device-drawn crops only).
+        cubes_per_clip: K cubes (K x 20 crops) of every clip instead of the reference's one; every embed method still returns
+        ONE row per clip, the float64 mean of the clip's K embeddings (pool="mean") or of its L2-normalised embeddings
+        (pool="mean_l2"), svk_embedding_pool.  The clip's feature rows are read K times by the first block, never copied.
+        `micro_batch` keeps counting cubes: a chunk holds `clips_per_chunk(micro_batch, K)` clips.  crop_rng="device" draws
+        20 K starts per clip (the first 20 are the one-cube draw), "reference" calls randint(T - 80, size=20) K times per clip,
+        in clip order.  K = 1 (the default) is today's path: no pooling, the same kernels, the same results."""
         self.channels = int(getattr(model, "num_channels", 0))
         if self.channels not in (1, 3):
             raise ValueError("VerificationPipeline runs C3D2 models with 1 or 3 input channels, got num_channels = %r"
@@ -126,6 +148,10 @@ class VerificationPipeline:
         self.refresh_model()
         self.use_vad, self.vad_threshold, self.normalize = use_vad, int(vad_threshold), bool(normalize)
         self.micro_batch = int(micro_batch)
+        self.cubes_per_clip = int(cubes_per_clip)
+        if self.cubes_per_clip < 1 or pool not in ("mean", "mean_l2"):
+            raise ValueError("cubes_per_clip must be at least 1 and pool 'mean' or 'mean_l2', got %r, %r" % (cubes_per_clip, pool))
+        self.pool = pool
         # model front end: lmfe(signal, 16000, 0.025, 0.01, 40, 1024)  (load_data.py:64-70, Q14)
         self.spec = spec_from_seconds(c.SAMPLE_RATE, c.FRAME_LEN, c.FRAME_STEP, c.NUM_FFT, c.NUM_COEF, c.NUM_COEF,
                                       _lib.OUT_LMFE, preemph=preemph_cof is not None,
@@ -151,7 +177,7 @@ class VerificationPipeline:
         a few clips of its neighbour): every launch sequence sees the same shapes."""
         if n <= 0:
             return []
-        count = -(-n // self.micro_batch)
+        count = -(-n // clips_per_chunk(self.micro_batch, getattr(self, "cubes_per_clip", 1)))
         size = -(-n // count)
         spans = [(k * size, min(n, (k + 1) * size)) for k in range(count)]
         lo, hi = spans[-1]
@@ -199,19 +225,32 @@ class VerificationPipeline:
         return feat, n_frames
 
     def draw_crops(self, n_frames_host):
-        """idx = randint(T - 80, size=20) per utterance, in order (utils.py:372, Q15)."""
-        out = np.empty((len(n_frames_host), c.CUBE_CROPS), dtype=np.int32)
+        """idx = randint(T - 80, size=20) per utterance, in order (utils.py:372, Q15) -> [n, 20]; with K = cubes_per_clip > 1
+        that draw K times per utterance, clip-major (draw[u, 0], then draw[u, 1], ...) -> [n, K, 20]."""
+        K = self.cubes_per_clip
+        out = np.empty((len(n_frames_host), K, c.CUBE_CROPS), dtype=np.int32)
         for i, T in enumerate(n_frames_host):
             if T - c.CUBE_FRAMES <= 0:
                 raise ValueError(f"utterance {i} has {T} feature frames; FeatureCube needs more than "
                                  f"{c.CUBE_FRAMES} (numpy randint: low >= high)")
-            out[i] = self.rng.randint(int(T) - c.CUBE_FRAMES, size=c.CUBE_CROPS)
-        return out
+            for k in range(K):
+                out[i, k] = self.rng.randint(int(T) - c.CUBE_FRAMES, size=c.CUBE_CROPS)
+        return out[:, 0] if K == 1 else out
 
     def cubes(self, feat, crop_idx, stats=None):
         """feature rows + crop starts -> cubes [n, channels, 20, 80, 40].  Three-channel model: `feat` is either the planes
         `features` returns ([n, 3, T, 40]: only rows move -- the planes read as 3 n clips, each clip's starts three times) or
-        STATIC features [n, T, 40] (+ `stats` of delta_cmvn_stats): the channels are formed for the cropped rows only."""
+        STATIC features [n, T, 40] (+ `stats` of delta_cmvn_stats): the channels are formed for the cropped rows only.
+        Crop starts [n, K, 20] -> [n, K, channels, 20, 80, 40] by the same gather kernels on the table read as [n, 20 K]: a view
+        for one channel, one permute for three."""
+        if getattr(crop_idx, "ndim", 2) == 3:
+            idx = self.eng.to_device(crop_idx, torch.int32)
+            n, K = idx.shape[0], idx.shape[1]
+            if K < 1:
+                raise ValueError("crop starts [n, K, 20] need K >= 1")
+            wide = self.cubes(feat, idx.reshape(n, K * idx.shape[2]), stats)       # [n, channels, 20 K, 80, 40]
+            wide = wide.view(n, self.channels, K, idx.shape[2], c.CUBE_FRAMES, wide.shape[-1])
+            return wide.view(n, K, 1, *wide.shape[3:]) if self.channels == 1 else wide.permute(0, 2, 1, 3, 4, 5)
         if self.channels == 1:
             return self.eng.cube_gather(feat, crop_idx, c.CUBE_FRAMES, stats=stats)
         if feat.dim() == 3:
@@ -225,7 +264,8 @@ class VerificationPipeline:
     def crops_and_cubes(self, pcm, first_utt=0, want_cubes=True):
         """The crop starts `embed` would draw for `pcm` ([n, 20] int32 on the host) and, with `want_cubes`, the
         20 x 80 x 40 cubes themselves ([n, 1, 20, 80, 40], or [n, 3, 20, 80, 40] for a three-channel model; device) -- VAD, front end, CMVN, crop draw and gather only, no
-        network: what BatchNorm calibration and the parity legs feed to the CPU oracle."""
+        network: what BatchNorm calibration and the parity legs feed to the CPU oracle.  With cubes_per_clip = K > 1: crop starts
+        [n, K, 20] and cubes [n, K, channels, 20, 80, 40]."""
         pcm = self.eng.to_device(pcm)
         crops, cubes = [], []
         for lo, hi in self.chunks(pcm.shape[0]):
@@ -233,20 +273,27 @@ class VerificationPipeline:
             if want_cubes:
                 cubes.append(self.cubes(feat, idx))
             crops.append(idx.cpu().numpy() if hasattr(idx, "cpu") else np.asarray(idx))
-        crops = np.concatenate(crops).astype(np.int32) if crops else np.zeros((0, c.CUBE_CROPS), np.int32)
+        empty = (0, c.CUBE_CROPS) if self.cubes_per_clip == 1 else (0, self.cubes_per_clip, c.CUBE_CROPS)
+        crops = np.concatenate(crops).astype(np.int32) if crops else np.zeros(empty, np.int32)
         return (crops, torch.cat(cubes)) if want_cubes else crops
 
     def embed_cubes(self, cubes):
         """[n, channels, 20, 80, 40] cubes -> [n, 128]: the cube read as feature rows by the first-block kernel (no copy)."""
         return self.embedder(cubes)
 
+    def _pool_flag(self):
+        return self.pool == "mean_l2"
+
     def embed_features(self, feat, crop_idx):
         """features + crop starts -> embeddings.  The cube is never materialised: `svk_c3d2_stage1` reads the
-        feature rows and crop starts itself; the other six kernels follow (model.FusedEmbedder.embed_features)."""
+        feature rows and crop starts itself; the other six kernels follow (model.FusedEmbedder.embed_features).  Crop starts
+        [n, K, 20]: K cubes per clip, pooled to one row per clip."""
+        multi = getattr(crop_idx, "ndim", 2) == 3
+        pool = self.pool if multi else None
         if self.kernel_events is None:
-            return self.embedder.embed_features(feat, crop_idx)
-        events = {"cubes": feat.shape[0]}
-        out = self.embedder.embed_features(feat, crop_idx, partial(_timed, events))
+            return self.embedder.embed_features(feat, crop_idx, pool=pool)
+        events = {"cubes": feat.shape[0] * (crop_idx.shape[1] if multi else 1)}
+        out = self.embedder.embed_features(feat, crop_idx, partial(_timed, events), pool=pool)
         self.kernel_events.append(events)
         return out
 
@@ -256,7 +303,9 @@ class VerificationPipeline:
         if crop_idx is not None:
             return np.asarray(crop_idx, dtype=np.int32)
         if self.crop_rng == "device":
-            return self.eng.draw_crops(n_frames, c.CUBE_CROPS, c.CUBE_FRAMES, self.crop_seed, first, self.bad_clips)
+            K = self.cubes_per_clip         # 20 K starts per clip, keyed by (seed, clip, c): the first 20 are the one-cube draw
+            idx = self.eng.draw_crops(n_frames, K * c.CUBE_CROPS, c.CUBE_FRAMES, self.crop_seed, first, self.bad_clips)
+            return idx if K == 1 else idx.view(-1, K, c.CUBE_CROPS)
         return self.draw_crops(n_frames.to("cpu").numpy())      # tiny D2H: T per utterance
 
     def _front(self, chunk, first, crop_idx=None):
@@ -269,8 +318,8 @@ class VerificationPipeline:
     # ---- whole path ---------------------------------------------------------------------
     def embed(self, pcm, crop_idx=None, return_intermediates=False, first_utt=0):
         """[n, L] int16 PCM (NumPy or CUDA tensor) -> [n, 128] float32 embeddings (device).
-        `crop_idx` [n, 20] overrides the RNG draw (parity tests feed both sides the same crops);
-        `first_utt` is the global index of row 0 (keys the device-side crop draw)."""
+        `crop_idx` [n, 20] (one cube per clip) or [n, K, 20] (K cubes, pooled) overrides the RNG draw (parity tests feed both
+        sides the same crops); `first_utt` is the global index of row 0 (keys the device-side crop draw)."""
         pcm = self.eng.to_device(pcm)
         emb = torch.empty((pcm.shape[0], 128), dtype=torch.float32, device=self.eng.device)
         inter = []
@@ -285,7 +334,11 @@ class VerificationPipeline:
                 feat, n_frames = self.features(voiced, vlen)
                 idx = self._crop_starts(n_frames, first_utt + lo, given)
                 cube = self.cubes(feat, idx)
-                emb[lo:hi] = self.embed_cubes(cube)
+                if cube.dim() == 6:               # [n, K, channels, 20, 80, 40]: every cube through the network, then the pool
+                    each = self.embed_cubes(cube.reshape((-1,) + tuple(cube.shape[2:])))
+                    emb[lo:hi] = self.eng.embedding_pool(each, rows_per_seg=cube.shape[1], l2_rows=self._pool_flag())
+                else:
+                    emb[lo:hi] = self.embed_cubes(cube)
                 inter.append({"lo": lo, "hi": hi, "voiced": voiced, "voiced_len": vlen, "feat": feat,
                               "n_frames": n_frames, "crop_idx": idx, "cube": cube})
             else:
@@ -331,12 +384,13 @@ class VerificationPipeline:
         n = lengths.size
         if not n:
             return []
+        per_batch = clips_per_chunk(self.micro_batch, getattr(self, "cubes_per_clip", 1))
         order = np.argsort(lengths, kind="stable")
         slots = (lengths[order] + 7) // 8 * 8
         cum = np.concatenate([[0], np.cumsum(slots)])                   # cum[k] = samples of the first k sorted clips
         out, pos = [], 0
         while pos < n:
-            hi = min(n, pos + self.micro_batch)
+            hi = min(n, pos + per_batch)
             # the sample cap: the largest hi with cum[hi] - cum[pos] <= max_batch_samples (at least one clip)
             hi = max(pos + 1, min(hi, int(np.searchsorted(cum, cum[pos] + max_batch_samples, side="right")) - 1))
             # the padding cap: (k - pos) * slots[k - 1] <= max_padding * (cum[k] - cum[pos]) holds at k = pos + 1; take the
@@ -359,7 +413,7 @@ class VerificationPipeline:
             feat_bytes = merged * max(1, longest // 160) * 40 * 4
             total = out[-2][1] + out[-1][1]
             padded = merged * ((longest + 7) // 8 * 8)
-            if (merged <= self.micro_batch and total <= max_batch_samples * 3 // 2 and feat_bytes <= max_feature_bytes
+            if (merged <= per_batch and total <= max_batch_samples * 3 // 2 and feat_bytes <= max_feature_bytes
                     and (padded <= max_padding * total or padded <= max_batch_samples)):
                 tail = out.pop()
                 out[-1] = (out[-1][0] + tail[0], out[-1][1] + tail[1])
@@ -389,7 +443,7 @@ class VerificationPipeline:
                 lo, first = hi, q + 1
         return groups, pieces
 
-    def _ragged_front(self, dev_buf, offs, lens, longest, rows, spans=None):
+    def _ragged_front(self, dev_buf, offs, lens, longest, rows, spans=None, crops=None, cubes_per_clip=1):
         """VAD -> front end -> CMVN statistics -> crop draw of one batch of clips addressed through offsets / lengths (device
         slices) into `dev_buf`; `longest`: the batch's longest clip in samples (host int); rows: the clips' global indices
         (they key the crop draw).  Returns (RAW features [n, T, 40], crop starts [n, 20], CMVN statistics or None): the VAD
@@ -397,7 +451,9 @@ class VerificationPipeline:
         normalisation (utils.py:382-397) is applied by the cube gather to the 20 x 80 rows the network reads, not to every row
         of a clip.  A three-channel model gets the same RAW static features and the statistics of its three channels
         ([n, 3, 2, 40], svk_delta_cmvn_stats): the gather forms the delta channels for the rows it copies, and no per-clip
-        plane is ever written.  Nothing here touches the host."""
+        plane is ever written.  Nothing here touches the host.  With K = cubes_per_clip cubes per clip the crop starts are
+        [n, 20 K] (clip-major: cube k of a clip is columns 20 k .. 20 k + 19); `crops`: the caller's starts in that shape (device)
+        instead of a draw."""
         timed = partial(_timed, spans)
         dev_lens, gather = lens, None
         if self.use_vad:
@@ -406,8 +462,8 @@ class VerificationPipeline:
                                                                          max_frames=self.spec.num_frames(int(longest)), gather=gather))
         cmvn_stats = self.eng.delta_cmvn_stats if self.channels == 3 else self.eng.cmvn_stats
         stats = timed("cmvn", lambda: cmvn_stats(feat, n_frames, variance=True)) if self.normalize else None
-        idx = timed("crops", lambda: self.eng.draw_crops(n_frames, c.CUBE_CROPS, c.CUBE_FRAMES, self.crop_seed, 0, self.bad_clips,
-                                                         utt_index=rows))
+        idx = crops if crops is not None else timed("crops", lambda: self.eng.draw_crops(
+            n_frames, cubes_per_clip * c.CUBE_CROPS, c.CUBE_FRAMES, self.crop_seed, 0, self.bad_clips, utt_index=rows))
         return feat, idx, stats
 
     class _CubeRing:
@@ -416,10 +472,15 @@ class VerificationPipeline:
         16-cube groups leaves most of the chip idle there (measured: 0.45 ms of fixed cost per such batch).  So every batch
         leaves only its gathered cubes (the 20 x 80 rows the network will read: 256 KB per clip, utils.py:351-379) in a RING
         of 2 x `step` cubes, and the network runs over `step` cubes as soon as that many have gathered; the first block reads
-        the ring as feature rows with crop starts 0, 80, 160 ...  Memory is O(step), whatever the number of clips."""
+        the ring as feature rows with crop starts 0, 80, 160 ...  Memory is O(step), whatever the number of clips.
+        With K cubes per clip a clip leaves K consecutive cubes (crop starts [n, 20 K]: the gather's [n, C, 20 K, 80, 40] is
+        [n K, 1, 20, 80, 40] as it lies for one channel, one permuting copy away for three); `step` is rounded up to a multiple
+        of K so that no clip straddles the ring's end, and `emb` / `order_dev` are per CUBE."""
 
-        def __init__(self, pipe, step, emb, order_dev, spans):
-            self.pipe, self.step, self.cap = pipe, int(step), 2 * int(step)
+        def __init__(self, pipe, step, emb, order_dev, spans, cubes_per_clip=1):
+            self.K = int(cubes_per_clip)
+            step = -(-int(step) // self.K) * self.K
+            self.pipe, self.step, self.cap = pipe, step, 2 * step
             self.emb, self.order, self.spans = emb, order_dev, spans
             self.channels = getattr(pipe, "channels", 1)       # 3: the ring holds three-channel cubes
             hit = getattr(pipe, "_ring_buf", None)
@@ -432,22 +493,27 @@ class VerificationPipeline:
             self.at = self.done = 0            # cubes gathered / handed to the network so far (absolute counts)
 
         def push(self, feat, idx, stats=None):
-            n = feat.shape[0]
-            assert n <= self.step, "a batch must not exceed the network step"
+            n, K = feat.shape[0], self.K
+            assert n * K <= self.step, "a batch must not exceed the network step"
             w = self.at % self.cap
-            first = min(n, self.cap - w)
+            first = min(n, (self.cap - w) // K)           # clips in front of the ring's end
 
             # three-channel model: the static rows become the three-channel cube on the way (svk_cube_gather_delta)
             cube_gather = self.pipe.eng.cube_gather_delta if self.channels == 3 else self.pipe.eng.cube_gather
+            if K > 1 and self.channels == 3:
+                def cube_gather(f, i, frames, out, stats):      # [m, 3, 20 K, 80, 40] -> the ring's [m K, 3, 20, 80, 40]
+                    wide = self.pipe.eng.cube_gather_delta(f, i, frames, stats=stats)
+                    out.view(f.shape[0], K, 3, c.CUBE_CROPS, frames, wide.shape[-1]).copy_(
+                        wide.view(f.shape[0], 3, K, c.CUBE_CROPS, frames, wide.shape[-1]).permute(0, 2, 1, 3, 4, 5))
 
             def gather():
-                cube_gather(feat[:first], idx[:first], c.CUBE_FRAMES, out=self.cubes[w:w + first],
+                cube_gather(feat[:first], idx[:first], c.CUBE_FRAMES, out=self.cubes[w:w + first * K],
                             stats=None if stats is None else stats[:first])
                 if first < n:                    # the batch wraps around the end of the ring
-                    cube_gather(feat[first:], idx[first:], c.CUBE_FRAMES, out=self.cubes[:n - first],
+                    cube_gather(feat[first:], idx[first:], c.CUBE_FRAMES, out=self.cubes[:(n - first) * K],
                                 stats=None if stats is None else stats[first:])
             _timed(self.spans, "gather", gather)
-            self.at += n
+            self.at += n * K
             while self.at - self.done >= self.step:
                 self._network(self.step)
 
@@ -480,11 +546,22 @@ class VerificationPipeline:
                                             torch.empty((numel,), dtype=torch.int16, device=self.eng.device) for _ in range(2)]
         return bufs
 
-    def _ragged_loop(self, emb, plan, offsets, lengths, step, first_utt, spans, fetch, release=None):
+    def _ragged_loop(self, emb, plan, offsets, lengths, step, first_utt, spans, fetch, release=None, crop_idx=None):
         """The body of both ragged forms.  plan: the clip indices of every batch, in the order they run; offsets / lengths:
         per clip, into the buffer fetch(k) returns for batch k once the current stream is ordered behind its upload;
-        release(k): batch k's buffer has been read.  Embeddings land in emb[clip index]."""
+        release(k): batch k's buffer has been read.  Embeddings land in emb[clip index].  crop_idx: the caller's crop starts,
+        [n, 20] or [n, K, 20] in clip order (host), instead of the draw.  K cubes per clip: the ring and the network work on
+        cubes, whose embeddings [n K, 128] are pooled to `emb` at the end."""
         dev = self.eng.device
+        K = self.cubes_per_clip
+        if crop_idx is not None:
+            crop_idx = np.asarray(crop_idx, dtype=np.int32)
+            if crop_idx.ndim not in (2, 3) or crop_idx.shape[0] != len(lengths) or crop_idx.shape[-1] != c.CUBE_CROPS:
+                raise ValueError("crop_idx must be [n, 20] or [n, K, 20] for the n = %d clips" % len(lengths))
+            K = crop_idx.shape[1] if crop_idx.ndim == 3 else 1
+            if K < 1:
+                raise ValueError("crop starts [n, K, 20] need K >= 1")
+        pooled = K > 1 or (crop_idx is not None and crop_idx.ndim == 3)
         # the whole schedule goes up ONCE, before the loop: a host array handed to a launch is a synchronous copy that waits
         # for everything queued before it
         order = np.concatenate(plan).astype(np.int64)
@@ -492,12 +569,19 @@ class VerificationPipeline:
         keys_dev = order_dev + int(first_utt)
         offs_dev = torch.from_numpy(offsets[order]).to(dev)
         lens_dev = torch.from_numpy(lengths[order].astype(np.int32)).to(dev)
-        ring = self._CubeRing(self, step, emb, order_dev, spans)
+        crops_dev = None if crop_idx is None else torch.from_numpy(crop_idx[order].reshape(len(order), -1)).to(dev)
+        if pooled:              # cube K u + k of clip u: its embedding lands in row K u + k
+            emb_cubes = torch.empty((len(lengths) * K, 128), dtype=torch.float32, device=dev)
+            order_cubes = (order_dev[:, None] * K + torch.arange(K, device=dev)[None, :]).reshape(-1)
+        else:
+            emb_cubes, order_cubes = emb, order_dev
+        ring = self._CubeRing(self, max(step, K), emb_cubes, order_cubes, spans, K)
         pos = 0
         for k, ids in enumerate(plan):
             sl = slice(pos, pos + len(ids))
             feat, idx, stats = self._ragged_front(fetch(k), offs_dev[sl], lens_dev[sl], int(lengths[ids].max()), keys_dev[sl],
-                                                  spans=spans)
+                                                  spans=spans, crops=None if crops_dev is None else crops_dev[sl],
+                                                  cubes_per_clip=K)
             if release is not None:
                 release(k)
             # the network runs as soon as a full step of cubes has gathered: its kernels then cover the host side of the
@@ -505,13 +589,16 @@ class VerificationPipeline:
             ring.push(feat, idx, stats)
             pos += len(ids)
         ring.finish()
+        if pooled:
+            emb.copy_(_timed(spans, "pool", lambda: self.eng.embedding_pool(emb_cubes, rows_per_seg=K, l2_rows=self._pool_flag())))
 
-    def embed_ragged(self, clips, max_batch_samples=64 * 1024 * 1024, first_utt=0, spans=None):
+    def embed_ragged(self, clips, max_batch_samples=64 * 1024 * 1024, first_utt=0, spans=None, crop_idx=None):
         """Clips of DIFFERENT lengths (VoxCeleb1 utterances run from 4 to 145 s): `clips` is a list of 1-D
         int16 arrays on the HOST.  They are sorted by length, packed back to back (16-byte aligned) into batches of
         at most `max_batch_samples` samples and `micro_batch` clips, uploaded, and addressed through the
         offsets / lengths form of the C-ABI.  Embeddings come back in the order of `clips`.  Needs crop_rng='device'.
-        `spans`: a list that receives ("vad" | "frontend" | "cmvn" | "crops" | "gather" | "network", start, end) HIP events (bench.py)."""
+        `spans`: a list that receives ("vad" | "frontend" | "cmvn" | "crops" | "gather" | "network", start, end) HIP events (bench.py).
+        `crop_idx`: [n, 20] or [n, K, 20] crop starts in the order of `clips` (host) instead of the device draw."""
         if self.crop_rng != "device":
             raise ValueError("embed_ragged needs crop_rng='device'")
         dev = self.eng.device
@@ -561,10 +648,11 @@ class VerificationPipeline:
             return staged[slot][:total]
 
         self._ragged_loop(emb, [ids for ids, _ in batches], offsets, lengths, self.micro_batch, first_utt, spans, fetch,
-                          release=lambda k: consumed[k & 1].record(main))
+                          release=lambda k: consumed[k & 1].record(main), crop_idx=crop_idx)
         return emb
 
-    def embed_ragged_resident(self, buf, offsets, lengths, max_batch_samples=64 * 1024 * 1024, first_utt=0, spans=None):
+    def embed_ragged_resident(self, buf, offsets, lengths, max_batch_samples=64 * 1024 * 1024, first_utt=0, spans=None,
+                              crop_idx=None):
         """`embed_ragged` for audio that is ALREADY in one buffer: `buf` is one 1-D int16 array holding every clip, clip k at
         samples [offsets[k], offsets[k] + lengths[k]) (offsets multiples of 8: 16-byte aligned; host arrays; clips may
         overlap, e.g. windows over one recording).
@@ -612,7 +700,7 @@ class VerificationPipeline:
         # otherwise over micro-batches as large as the main path's
         step = self.micro_batch if len(groups) > 1 else max(self.micro_batch, 4096)
         if not host:
-            self._ragged_loop(emb, plan, offsets, lengths, step, first_utt, spans, lambda k: buf)
+            self._ragged_loop(emb, plan, offsets, lengths, step, first_utt, spans, lambda k: buf, crop_idx=crop_idx)
             return emb
         src = torch.from_numpy(buf)
         buf = torch.empty((n_samples,), dtype=torch.int16, device=dev)
@@ -621,7 +709,7 @@ class VerificationPipeline:
                 if k == 0 or group_of[k] != group_of[k - 1]:
                     up.wait(group_of[k])
                 return buf
-            self._ragged_loop(emb, plan, offsets, lengths, step, first_utt, spans, fetch)
+            self._ragged_loop(emb, plan, offsets, lengths, step, first_utt, spans, fetch, crop_idx=crop_idx)
         return emb
 
     def embed_host(self, pcm_host, first_utt=0):
@@ -663,3 +751,15 @@ def enroll_last_utterance(embeddings, speaker_ids):
     uniq = np.unique(speaker_ids)
     last = np.array([np.nonzero(speaker_ids == s)[0][-1] for s in uniq], dtype=np.int64)
     return uniq, last
+
+
+def enroll_mean(embeddings, speaker_ids, l2=True):
+    """Speaker model = the mean of the speaker's utterance embeddings (each L2-normalised first with `l2`), what the d-vector
+    method describes; `enroll_last_utterance` is the reference's own behaviour.  One `svk_embedding_pool` launch over CSR
+    segments (`speaker_segments`).  Returns (sorted unique ids, models [S, 128] float32 on the device)."""
+    uniq, seg_start, row_index = speaker_segments(speaker_ids)
+    eng = get_engine()
+    emb = eng.to_device(embeddings, torch.float32)
+    if emb.dim() != 2 or emb.shape[0] != row_index.size:
+        raise ValueError("enroll_mean wants one embedding row per speaker id")
+    return uniq, eng.embedding_pool(emb, seg_start=seg_start, row_index=row_index, l2_rows=l2)
