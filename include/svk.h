@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only): + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
+#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
 
 typedef enum svk_status {
   SVK_OK = 0,
@@ -289,6 +289,24 @@ int svk_embedding_pool(svk_ctx* ctx, const float* d_emb, int64_t n_rows, int32_t
                        const int64_t* d_seg_start, const int64_t* d_row_index, int32_t flags, float* d_out,
                        int32_t* d_empty_count);
 
+/* One score per TRIAL of a list (the `label utterance_a utterance_b` lines of the VoxCeleb1 protocols) instead of the whole
+ * matrix of svk_cosine_scores or the row-i-against-row-i of svk_l2_dist; replaces the a[idx_a], b[idx_b] gathers and the
+ * reduction a framework would do:  d_out[p] = score(d_a[d_idx_a[p]], d_b[d_idx_b[p]]).
+ *   metric 0      cosine, x.y / (||x|| ||y||); a zero norm divides by 1 (svk_cosine_scores, sklearn's normalize)
+ *   metric 1      -||x - y||_2: siamese.py:29-30 negated, so that a larger score means the same speaker (what the ROC expects)
+ *   d_a, d_b      [n_a][dim], [n_b][dim] f32, 4-byte aligned; d_a == d_b is allowed.  16-byte loads when dim % 4 == 0 and both
+ *                 are 16-byte aligned, 4-byte loads otherwise: the same bits either way
+ *   d_idx_a/_b    int64 [n_pairs].  An index outside its matrix is the caller's error: the rows are not read, that trial's score
+ *                 is NaN and *d_bad_count (int32, may be NULL, the caller zeroes it) goes up by one
+ * The products, the sums, the square roots and the division are float64 and the result is rounded to float32 once: it lies
+ * within 1 float32 ulp of the correctly rounded exact score.  The order of additions of a trial depends on dim alone (a team of
+ * 16 lanes per trial, each lane its columns in order, then a butterfly), not on n_pairs, the launch geometry or the
+ * neighbouring trials: a trial scored alone gives the bits it gives inside a list.  1 <= dim <= 4096; n_pairs == 0 launches
+ * nothing.  SVK_ERR_BAD_ARG: NULL context or buffer, negative size, dim out of range, unknown metric, misalignment. */
+int svk_pair_scores(svk_ctx* ctx, const float* d_a, int64_t n_a, const float* d_b, int64_t n_b, int32_t dim,
+                    const int64_t* d_idx_a, const int64_t* d_idx_b, int64_t n_pairs, int32_t metric, float* d_out,
+                    int32_t* d_bad_count);
+
 /* ---- ROC / EER / AUC on the device ------------------------------------------------------------
  * evaluation.py:47-52 (sklearn roc_curve + roc_auc_score + brentq on interp1d) for pair sets too
  * large for the host: LSD radix sort of the scores (descending, 8-bit digits, the label riding along;
@@ -313,6 +331,30 @@ int svk_roc_eer(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, in
 size_t svk_roc_k_workspace_bytes(int64_t n, int32_t k);
 int svk_roc_k(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, int64_t n, int32_t k, void* d_workspace,
               size_t workspace_bytes, uint32_t* d_curve, double* h_out);
+
+/* svk_roc_eer plus the detection cost the VoxCeleb results are quoted with and the thresholds to decide with (the reference
+ * has neither; on the host this is NumPy over sklearn's roc_curve(drop_intermediate=False): evaluation.get_min_dcf).  One sort
+ * serves all of it.  h_ops (HOST) [n_op][3] = {p_target, c_miss, c_fa}, 0 <= n_op <= 8, 0 < p_target < 1, costs > 0.
+ * h_out (HOST) [5 + 4 n_op] = {eer, auc, positives, points, eer_threshold}, then per operating point {min_dcf, threshold, p_miss,
+ * p_fa}; the first four are svk_roc_eer's values for the same input, bit for bit (the same kernels in the same order).
+ * The candidates are roc_curve's origin (reject everything: p_miss = 1, p_fa = 0, threshold +inf) and one point per distinct
+ * score in descending order; the cost of a point is c_miss p (1 - tps / P) + c_fa (1 - p) fps / N in float64, min_dcf the
+ * smallest cost / min(c_miss p, c_fa (1 - p)); among equal costs the FIRST point wins (the highest threshold).  threshold is
+ * that point's score -- accept when score >= threshold -- and p_miss, p_fa the rates there.  eer_threshold is the score of the
+ * first point where 1 - fpr - tpr <= 0 (the upper end of the segment the EER is interpolated on).  Strict like svk_roc_k: a
+ * non-finite score or a single class is SVK_ERR_BAD_ARG, as are a bad operating point, n_op outside [0, 8], n < 2 or n >= 2^32
+ * and a workspace below svk_roc_dcf_workspace_bytes(n) (0 for n < 2).  Synchronises the stream. */
+size_t svk_roc_dcf_workspace_bytes(int64_t n);
+int svk_roc_dcf(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, int64_t n, const double* h_ops, int32_t n_op,
+                void* d_workspace, size_t workspace_bytes, double* h_out);
+
+/* Applies thresholds chosen on one set to another (actual DCF, false accepts / false rejects; replaces a comparison and a
+ * masked sum per threshold in a framework): one streaming pass over UNSORTED scores.  h_thresholds (HOST) [n_thr] f32,
+ * 1 <= n_thr <= 16, +-inf allowed, NaN not.  h_out (HOST) int64 [2 n_thr + 2]: [2 t] = targets (label != 0) with score >=
+ * thr[t], [2 t + 1] = non-targets with score >= thr[t], [2 n_thr] = targets, [2 n_thr + 1] = non-targets.  A NaN score is never
+ * accepted and counts only in its class total.  Integer counts, exact; n may exceed 2^32.  Synchronises the stream. */
+int svk_decision_counts(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, int64_t n, const float* h_thresholds,
+                        int32_t n_thr, int64_t* h_out);
 
 /* evaluation.py:112-134 (top-1 of each test utterance) in one streaming pass over d_scores [n_rows][n_cols]:
  * d_argmax[r] = np.argmax(row r) (the first maximum; a NaN is the maximum, the first NaN wins); d_true[r] = the

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsvk.so")
 
 SVK_OK = 0
-VERSION = 114                      # include/svk.h SVK_VERSION (0.1.12: + svk_c3d2_head; + the svk_delta_* entries, the *_multi first block and svk_embedding_pool, number unchanged)
+VERSION = 114                      # include/svk.h SVK_VERSION (0.1.12: + svk_pair_scores, svk_roc_dcf, svk_decision_counts, number unchanged; + svk_c3d2_head; + the svk_delta_* entries, the *_multi first block and svk_embedding_pool, number unchanged)
 SVK_ERR_BAD_ARG, SVK_ERR_UNSUPPORTED, SVK_ERR_HIP, SVK_ERR_NO_DEVICE, SVK_ERR_OOM, SVK_ERR_RCCL = -1, -2, -3, -4, -5, -6
 OUT_MFE, OUT_LMFE, OUT_MFCC = 0, 1, 2
 PCM_I16, PCM_F32 = 0, 1
@@ -80,8 +80,12 @@ SIGNATURES = {
     "svk_roc_eer": (C.c_int, [_vp, _vp, _vp, _i64, _vp, C.c_size_t, C.POINTER(C.c_double)]),
     "svk_roc_k_workspace_bytes": (C.c_size_t, [_i64, _i32]),
     "svk_roc_k": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, C.c_size_t, _vp, C.POINTER(C.c_double)]),
+    "svk_roc_dcf_workspace_bytes": (C.c_size_t, [_i64]),
+    "svk_roc_dcf": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(C.c_double), _i32, _vp, C.c_size_t, C.POINTER(C.c_double)]),
+    "svk_decision_counts": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(_f32), _i32, C.POINTER(_i64)]),
     "svk_top1": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, C.POINTER(_i64)]),
     "svk_l2_dist": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
+    "svk_pair_scores": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _vp]),
     "svk_embedding_pool": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _i32, _vp, _vp]),
     "svk_c3d2_stage1_lds_bytes": (C.c_size_t, []),
     "svk_c3d2_stage1": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),

@@ -17,8 +17,15 @@
 //      (fps, tps) at every boundary.
 //   4. roc_points_kernel: trapezoid area (AUC) and the segment where 1 - fpr - tpr changes sign,
 //      solved linearly (the root brentq finds on the linear interpolant).
+//      Each workgroup leaves its share of the area in the workspace; roc_finish_kernel, ONE workgroup, adds the shares in a
+//      fixed order (the AUC is the same bits on every run and from every entry point) and looks up the score at the upper end
+//      of the EER segment.
 //   5. svk_roc_k only: roc_curve's drop_intermediate (second differences of fps, tps) and its
 //      prepended origin, compacted by the same pattern into the caller's curve planes.
+//   6. svk_roc_dcf only: dcf_part_kernel, one pass over the origin + the distinct-score points that leaves every workgroup's
+//      (cost, index) minimum per operating point in the workspace; roc_finish_kernel reduces them (no float64 atomics, no
+//      workgroup waits on another).  The first point among equal costs wins: the highest threshold.
+// svk_decision_counts is a pass of its own over UNSORTED scores: accepted targets / non-targets at up to 16 thresholds.
 // Bit-level equality of eer / auc with sklearn is not expected (float64 accumulation order), |d| ~ 1e-15;
 // the curve counts are exact.  Element indices are u32 (n < 2^32), every address is 64-bit.
 #include "svk_internal.h"
@@ -33,6 +40,9 @@ constexpr int GROUPS = ITEMS * WAVES;    // (item, wave) groups of a tile, in st
 constexpr int SPAN_ITEMS = 4;            // elements per thread per step of the point / curve passes
 constexpr unsigned GMAX = 1024;          // workgroups of a span-parallel kernel (count matrix [256][GMAX])
 constexpr int SCAN_T = 1024;
+constexpr unsigned PMAX = 2048;          // workgroups of a pass over the ROC points (their partial results: [PMAX] rows)
+constexpr int DCF_MAX_OPS = 8;           // operating points of one svk_roc_dcf call
+constexpr int DC_MAX_THR = 16;           // thresholds of one svk_decision_counts call
 
 __device__ __forceinline__ unsigned desc_key(unsigned u) {
   if (u == 0x80000000u) u = 0u;                      // -0.0 -> +0.0
@@ -370,9 +380,10 @@ __global__ __launch_bounds__(RT) void emit_kernel(Op op, size_t span, const unsi
 }
 
 // ---- 4. AUC and EER over the points ---------------------------------------------------------------------------
-// out[0] = eer, out[1] = auc (accumulated; zeroed before)
+// out[0] = eer, *eer_point = the point at the upper end of its segment, area_parts[workgroup] = its share of the AUC
 __global__ __launch_bounds__(RT) void roc_points_kernel(const unsigned* __restrict__ pf, const unsigned* __restrict__ pt,
-                                                        size_t m, double P, double N, double* __restrict__ out) {
+                                                        size_t m, double P, double N, double* __restrict__ out,
+                                                        double* __restrict__ area_parts, unsigned* __restrict__ eer_point) {
   __shared__ double red[WAVES];
   double area = 0.0;
   for (size_t j = (size_t)blockIdx.x * RT + threadIdx.x; j < m; j += (size_t)gridDim.x * RT) {
@@ -385,7 +396,10 @@ __global__ __launch_bounds__(RT) void roc_points_kernel(const unsigned* __restri
     const double x0 = f0 / N, x1 = f1 / N, y0 = t0 / P, y1 = t1 / P;
     area += (x1 - x0) * (y0 + y1) * 0.5;
     const double g0 = 1.0 - x0 - y0, g1 = 1.0 - x1 - y1;
-    if (g0 > 0.0 && g1 <= 0.0) out[0] = x0 + (x1 - x0) * g0 / (g0 - g1);  // exactly one segment qualifies
+    if (g0 > 0.0 && g1 <= 0.0) {  // exactly one segment qualifies
+      out[0] = x0 + (x1 - x0) * g0 / (g0 - g1);
+      *eer_point = (unsigned)j;
+    }
   }
   area = wave_sum(area);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = area;
@@ -393,7 +407,203 @@ __global__ __launch_bounds__(RT) void roc_points_kernel(const unsigned* __restri
   if (threadIdx.x == 0) {
     double s = 0.0;
     for (int i = 0; i < WAVES; ++i) s += red[i];
-    atomicAdd(&out[1], s);
+    area_parts[blockIdx.x] = s;
+  }
+}
+
+// ---- 6. detection cost over the points --------------------------------------------------------------------------
+// Operating point o: a[o] = c_miss p_target, b[o] = c_fa (1 - p_target); the cost of a point is a (1 - tps / P) + b fps / N.
+struct DcfOps {
+  int n;
+  double a[DCF_MAX_OPS], b[DCF_MAX_OPS];
+};
+
+// (c, i) beats (bc, bi): the smaller cost, then the smaller index (the earlier point, the higher threshold)
+__device__ __forceinline__ void dcf_take(double& bc, unsigned& bi, double c, unsigned i) {
+  if (c < bc || (c == bc && i < bi)) {
+    bc = c;
+    bi = i;
+  }
+}
+__device__ __forceinline__ void dcf_wave_min(double& bc, unsigned& bi) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const double oc = __shfl_xor(bc, m, 64);
+    const unsigned oi = __shfl_xor(bi, m, 64);
+    dcf_take(bc, bi, oc, oi);
+  }
+}
+
+// Index 0 is roc_curve's origin (reject everything: tps = fps = 0), index j + 1 the distinct-score point j.
+// pcost / pidx [DCF_MAX_OPS][PMAX]: this workgroup's minimum per operating point.
+__global__ __launch_bounds__(RT) void dcf_part_kernel(const unsigned* __restrict__ pf, const unsigned* __restrict__ pt, size_t m,
+                                                      double P, double N, const DcfOps ops, double* __restrict__ pcost,
+                                                      unsigned* __restrict__ pidx) {
+  double bc[DCF_MAX_OPS];
+  unsigned bi[DCF_MAX_OPS];
+#pragma unroll
+  for (int o = 0; o < DCF_MAX_OPS; ++o) {
+    bc[o] = INFINITY;
+    bi[o] = 0xffffffffu;
+  }
+  for (size_t j = (size_t)blockIdx.x * RT + threadIdx.x; j <= m; j += (size_t)gridDim.x * RT) {
+    double t = 0.0, f = 0.0;
+    if (j > 0) {
+      t = (double)pt[j - 1];
+      f = (double)pf[j - 1];
+    }
+    const double miss = 1.0 - t / P, fa = f / N;
+#pragma unroll
+    for (int o = 0; o < DCF_MAX_OPS; ++o) {
+      if (o < ops.n) {
+#pragma clang fp contract(off)   // two products and a sum, each rounded: the host path's arithmetic
+        const double cost = ops.a[o] * miss + ops.b[o] * fa;
+        if (cost < bc[o]) {   // a thread's indices only grow: the first of equal costs stays
+          bc[o] = cost;
+          bi[o] = (unsigned)j;
+        }
+      }
+    }
+  }
+  __shared__ double rc[DCF_MAX_OPS][WAVES];
+  __shared__ unsigned ri[DCF_MAX_OPS][WAVES];
+#pragma unroll
+  for (int o = 0; o < DCF_MAX_OPS; ++o) {
+    if (o < ops.n) {
+      dcf_wave_min(bc[o], bi[o]);
+      if ((threadIdx.x & 63) == 0) {
+        rc[o][threadIdx.x >> 6] = bc[o];
+        ri[o][threadIdx.x >> 6] = bi[o];
+      }
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < ops.n) {
+    const int o = threadIdx.x;
+    double c = rc[o][0];
+    unsigned i = ri[o][0];
+    for (int w = 1; w < WAVES; ++w) dcf_take(c, i, rc[o][w], ri[o][w]);
+    pcost[(size_t)o * PMAX + blockIdx.x] = c;
+    pidx[(size_t)o * PMAX + blockIdx.x] = i;
+  }
+}
+
+// One workgroup: out[1] = the AUC, the pgrid shares added in a fixed order; fin[0] = the score of the EER point; per operating
+// point o, fin[1 + 4 o ..] = {the smallest cost, its index (0 = the origin), fps, tps} and thr[o] = that point's score.  A
+// point's score is the sorted key of the last pair at or above it, element fps + tps - 1.
+__global__ __launch_bounds__(RT) void roc_finish_kernel(const double* __restrict__ area_parts, unsigned pgrid,
+                                                        const unsigned* __restrict__ eer_point, const unsigned* __restrict__ pf,
+                                                        const unsigned* __restrict__ pt, const unsigned* __restrict__ keys,
+                                                        int n_op, const double* __restrict__ pcost,
+                                                        const unsigned* __restrict__ pidx, unsigned dgrid,
+                                                        double* __restrict__ out, double* __restrict__ fin,
+                                                        float* __restrict__ thr) {
+  __shared__ double red[WAVES];
+  __shared__ unsigned redi[WAVES];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  double area = 0.0;
+  for (unsigned i = threadIdx.x; i < pgrid; i += RT) area += area_parts[i];
+  area = wave_sum(area);
+  if (lane == 0) red[w] = area;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int i = 0; i < WAVES; ++i) s += red[i];
+    out[1] = s;
+    const unsigned j = *eer_point;
+    fin[0] = (double)key_value(keys[(size_t)pf[j] + pt[j] - 1]);
+  }
+  for (int o = 0; o < n_op; ++o) {
+    double bc = INFINITY;
+    unsigned bi = 0xffffffffu;
+    for (unsigned i = threadIdx.x; i < dgrid; i += RT) dcf_take(bc, bi, pcost[(size_t)o * PMAX + i], pidx[(size_t)o * PMAX + i]);
+    dcf_wave_min(bc, bi);
+    __syncthreads();
+    if (lane == 0) {
+      red[w] = bc;
+      redi[w] = bi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int i = 1; i < WAVES; ++i) dcf_take(bc, bi, red[i], redi[i]);
+      double f = 0.0, t = 0.0;
+      float score = INFINITY;   // the origin accepts nothing
+      if (bi > 0) {
+        const unsigned fi = pf[bi - 1], ti = pt[bi - 1];
+        f = (double)fi;
+        t = (double)ti;
+        score = key_value(keys[(size_t)fi + ti - 1]);
+      }
+      fin[1 + 4 * o] = bc;
+      fin[2 + 4 * o] = (double)bi;
+      fin[3 + 4 * o] = f;
+      fin[4 + 4 * o] = t;
+      thr[o] = score;
+    }
+  }
+}
+
+// ---- decision counts ----------------------------------------------------------------------------------------------
+struct DcThr {
+  float v[DC_MAX_THR];
+};
+
+// One streaming pass, four consecutive pairs per thread and step (VEC: one 16-byte and one 4-byte load).  counts[2 t] =
+// targets with score >= v[t], counts[2 t + 1] = non-targets with score >= v[t], counts[2 MAXT] = targets; a NaN score (and a
+// NaN threshold: the unused slots up to MAXT) accepts nothing.  Per-thread counts are 32-bit: n < 2^32 x the threads launched.
+template <int MAXT, bool VEC>
+__global__ __launch_bounds__(RT) void decision_counts_kernel(const float* __restrict__ sc, const uint8_t* __restrict__ lab, size_t n,
+                                                             const DcThr thr, unsigned long long* __restrict__ counts) {
+  unsigned acc[MAXT], tgt[MAXT], pos = 0;
+#pragma unroll
+  for (int t = 0; t < MAXT; ++t) acc[t] = tgt[t] = 0;
+  const size_t quads = (n + 3) / 4;
+  for (size_t q = (size_t)blockIdx.x * RT + threadIdx.x; q < quads; q += (size_t)gridDim.x * RT) {
+    const size_t i0 = 4 * q;
+    float s[4];
+    unsigned l[4];
+    if (VEC && i0 + 4 <= n) {
+      const float4 v = *reinterpret_cast<const float4*>(sc + i0);
+      const uchar4 u = *reinterpret_cast<const uchar4*>(lab + i0);
+      s[0] = v.x, s[1] = v.y, s[2] = v.z, s[3] = v.w;
+      l[0] = u.x != 0, l[1] = u.y != 0, l[2] = u.z != 0, l[3] = u.w != 0;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const bool ok = i0 + e < n;
+        s[e] = ok ? sc[i0 + e] : __builtin_nanf("");
+        l[e] = ok ? lab[i0 + e] != 0 : 0u;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      pos += l[e];
+#pragma unroll
+      for (int t = 0; t < MAXT; ++t) {
+        const unsigned hit = s[e] >= thr.v[t];
+        acc[t] += hit;
+        tgt[t] += hit & l[e];
+      }
+    }
+  }
+  constexpr int NC = 2 * MAXT + 1;
+  __shared__ long long red[WAVES][NC];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int t = 0; t < MAXT; ++t) {
+    const long long a = wave_sum((long long)tgt[t]), b = wave_sum((long long)(acc[t] - tgt[t]));
+    if (lane == 0) {
+      red[w][2 * t] = a;
+      red[w][2 * t + 1] = b;
+    }
+  }
+  const long long p = wave_sum((long long)pos);
+  if (lane == 0) red[w][2 * MAXT] = p;
+  __syncthreads();
+  if ((int)threadIdx.x < NC) {
+    long long h = 0;
+    for (int i = 0; i < WAVES; ++i) h += red[i][threadIdx.x];
+    if (h) atomicAdd(&counts[threadIdx.x], (unsigned long long)h);
   }
 }
 
@@ -467,13 +677,28 @@ RocLayout roc_layout(size_t m) {
   }
   l.pf = o;     o += up(m * 4);
   l.pt = o;     o += up(m * 4);
-  l.counts = o; o += up((size_t)256 * GMAX * 4);
+  l.counts = o; o += up((size_t)256 * GMAX * 4);   // after the sort: the point passes' per-workgroup results (POST_* below)
   l.parts = o;  o += up((size_t)4 * GMAX * 4);   // four [GMAX] partial-sum rows: (a, b) of the points, of the curve
   l.hist = o;   o += up(1026 * 4);
   l.misc = o;   o += 256;                       // [0..1] doubles eer, auc; then u32 totals at +64
   l.total = o;
   return l;
 }
+
+// The count matrix's bytes once the sort is done, by byte offset: what the passes over the ROC points leave per workgroup.
+constexpr size_t POST_AREA = 0;                                               // double [PMAX]
+constexpr size_t POST_COST = POST_AREA + PMAX * 8;                            // double [DCF_MAX_OPS][PMAX]
+constexpr size_t POST_IDX = POST_COST + (size_t)DCF_MAX_OPS * PMAX * 8;       // u32 [DCF_MAX_OPS][PMAX]
+constexpr size_t POST_FIN = POST_IDX + (size_t)DCF_MAX_OPS * PMAX * 4;        // double [1 + 4 DCF_MAX_OPS]
+constexpr size_t POST_THR = POST_FIN + (1 + 4 * DCF_MAX_OPS) * 8;             // float [DCF_MAX_OPS]
+static_assert(POST_THR + DCF_MAX_OPS * 4 <= (size_t)256 * GMAX * 4, "the point passes' results outgrow the count matrix");
+
+// What svk_roc_dcf asks of a split beyond {eer, auc, positives, points}: fin / thr as roc_finish_kernel writes them.
+struct DcfRequest {
+  DcfOps ops;
+  double fin[1 + 4 * DCF_MAX_OPS];
+  float thr[DCF_MAX_OPS];
+};
 
 // span (a multiple of `unit`) and grid so that at most GMAX workgroups cover n elements
 void spans(size_t n, size_t unit, size_t* span, unsigned* grid) {
@@ -503,9 +728,10 @@ int span_pass(svk_ctx* ctx, const Op& op, unsigned* pa, unsigned* pb, unsigned* 
 
 // One split of m pairs.  strict (svk_roc_k): non-finite scores and a single class are errors found before the
 // sort, named by `split`.  cf / ct: the split's curve planes, or NULL.  h4 = {eer, auc, positives, points}: points =
-// distinct scores (curve == false) or the length of roc_curve's output (curve == true).
+// distinct scores (curve == false) or the length of roc_curve's output (curve == true).  dcf: NULL, or the operating points
+// whose detection-cost minima this split's points are searched for; it also takes the EER point's score.
 int roc_split(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, size_t m, char* w, const RocLayout& l,
-              bool strict, int split, bool curve, unsigned* cf, unsigned* ct, double* h4) {
+              bool strict, int split, bool curve, unsigned* cf, unsigned* ct, double* h4, DcfRequest* dcf = nullptr) {
   hipStream_t st = ctx->stream;
   unsigned* keys[2] = {reinterpret_cast<unsigned*>(w + l.keys[0]), reinterpret_cast<unsigned*>(w + l.keys[1])};
   uint8_t* vals[2] = {reinterpret_cast<uint8_t*>(w + l.vals[0]), reinterpret_cast<uint8_t*>(w + l.vals[1])};
@@ -515,7 +741,13 @@ int roc_split(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, size
   unsigned* parts = reinterpret_cast<unsigned*>(w + l.parts);
   unsigned* hist = reinterpret_cast<unsigned*>(w + l.hist);
   double* out = reinterpret_cast<double*>(w + l.misc);
-  unsigned* totals = reinterpret_cast<unsigned*>(w + l.misc + 64);   // [0] pos, [1] points, [2] -, [3] curve points
+  unsigned* totals = reinterpret_cast<unsigned*>(w + l.misc + 64);   // [0] pos, [1] points, [2] -, [3] curve points, [4] EER point
+  char* post = w + l.counts;
+  double* area_parts = reinterpret_cast<double*>(post + POST_AREA);
+  double* pcost = reinterpret_cast<double*>(post + POST_COST);
+  unsigned* pidx = reinterpret_cast<unsigned*>(post + POST_IDX);
+  double* fin = reinterpret_cast<double*>(post + POST_FIN);
+  float* thr = reinterpret_cast<float*>(post + POST_THR);
   const unsigned* bits = reinterpret_cast<const unsigned*>(d_scores);
 
   SVK_HIP(ctx, hipMemsetAsync(hist, 0, 1026 * 4, st));
@@ -565,8 +797,19 @@ int roc_split(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, size
   unsigned M = 0;
   SVK_HIP(ctx, hipMemcpyAsync(&M, totals + 1, 4, hipMemcpyDeviceToHost, st));
   SVK_HIP(ctx, hipStreamSynchronize(st));
-  const unsigned pgrid = (unsigned)std::max<size_t>(1, std::min<size_t>((M + RT - 1) / RT, (size_t)ctx->num_cu * 8));
-  hipLaunchKernelGGL(roc_points_kernel, dim3(pgrid), dim3(RT), 0, st, pf, pt, (size_t)M, (double)P, (double)m - (double)P, out);
+  const size_t pcap = std::min<size_t>((size_t)ctx->num_cu * 8, PMAX);
+  const unsigned pgrid = (unsigned)std::max<size_t>(1, std::min<size_t>((M + RT - 1) / RT, pcap));
+  const double Pd = (double)P, Nd = (double)m - (double)P;
+  hipLaunchKernelGGL(roc_points_kernel, dim3(pgrid), dim3(RT), 0, st, pf, pt, (size_t)M, Pd, Nd, out, area_parts, totals + 4);
+  SVK_LAUNCH_CHECK(ctx);
+  const int n_op = dcf ? dcf->ops.n : 0;
+  const unsigned dgrid = (unsigned)std::min<size_t>(((size_t)M + 1 + RT - 1) / RT, pcap);
+  if (n_op) {
+    hipLaunchKernelGGL(dcf_part_kernel, dim3(dgrid), dim3(RT), 0, st, pf, pt, (size_t)M, Pd, Nd, dcf->ops, pcost, pidx);
+    SVK_LAUNCH_CHECK(ctx);
+  }
+  hipLaunchKernelGGL(roc_finish_kernel, dim3(1), dim3(RT), 0, st, area_parts, pgrid, totals + 4, pf, pt, src, n_op, pcost, pidx,
+                     dgrid, out, fin, thr);
   SVK_LAUNCH_CHECK(ctx);
   unsigned C = M;
   if (curve) {
@@ -579,6 +822,10 @@ int roc_split(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, size
     SVK_HIP(ctx, hipMemcpyAsync(&C, totals + 3, 4, hipMemcpyDeviceToHost, st));
   }
   SVK_HIP(ctx, hipMemcpyAsync(h4, out, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (dcf) {
+    SVK_HIP(ctx, hipMemcpyAsync(dcf->fin, fin, sizeof(double) * (1 + 4 * (size_t)n_op), hipMemcpyDeviceToHost, st));
+    if (n_op) SVK_HIP(ctx, hipMemcpyAsync(dcf->thr, thr, sizeof(float) * (size_t)n_op, hipMemcpyDeviceToHost, st));
+  }
   SVK_HIP(ctx, hipStreamSynchronize(st));
   h4[2] = (double)P;
   h4[3] = curve ? (double)C + 1.0 : (double)M;
@@ -647,6 +894,80 @@ int svk_top1(svk_ctx* ctx, const float* d_scores, int64_t n_rows, int32_t n_cols
   SVK_HIP(ctx, hipMemcpyAsync(&h, hits, 8, hipMemcpyDeviceToHost, st));
   SVK_HIP(ctx, hipStreamSynchronize(st));
   *h_correct = (int64_t)h;
+  return SVK_OK;
+}
+
+size_t svk_roc_dcf_workspace_bytes(int64_t n) { return n >= 2 ? roc_layout((size_t)n).total : 0; }
+
+int svk_roc_dcf(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, int64_t n, const double* h_ops, int32_t n_op,
+                void* d_workspace, size_t workspace_bytes, double* h_out) {
+  if (!ctx || !h_out) return SVK_ERR_BAD_ARG;
+  SVK_REQUIRE(ctx, n >= 2, "need at least two (label, score) pairs");
+  SVK_REQUIRE(ctx, n < ((int64_t)1 << 32), "at most 2^32 - 1 pairs");
+  SVK_REQUIRE(ctx, n_op >= 0 && n_op <= DCF_MAX_OPS, "0 to 8 operating points");
+  SVK_REQUIRE(ctx, d_scores && d_labels && d_workspace && (h_ops || n_op == 0), "NULL buffer");
+  DcfRequest req;
+  req.ops.n = n_op;
+  for (int o = 0; o < DCF_MAX_OPS; ++o) req.ops.a[o] = req.ops.b[o] = 0.0;
+  for (int o = 0; o < n_op; ++o) {
+    const double p = h_ops[3 * o], c_miss = h_ops[3 * o + 1], c_fa = h_ops[3 * o + 2];
+    if (!(p > 0.0 && p < 1.0 && c_miss > 0.0 && c_miss < INFINITY && c_fa > 0.0 && c_fa < INFINITY))
+      return svk_fail(ctx, SVK_ERR_BAD_ARG, "bad argument: operating point %d = (%g, %g, %g): need 0 < p_target < 1 and finite "
+                      "c_miss, c_fa > 0", o, p, c_miss, c_fa);
+    req.ops.a[o] = c_miss * p;
+    req.ops.b[o] = c_fa * (1.0 - p);
+  }
+  const RocLayout l = roc_layout((size_t)n);
+  SVK_REQUIRE(ctx, workspace_bytes >= l.total, "workspace smaller than svk_roc_dcf_workspace_bytes(n)");
+  double h4[4];
+  if (int rc = roc_split(ctx, d_scores, d_labels, (size_t)n, reinterpret_cast<char*>(d_workspace), l, true, 0, false, nullptr,
+                         nullptr, h4, &req))
+    return rc;
+  const double P = h4[2], N = (double)n - P;
+  for (int i = 0; i < 4; ++i) h_out[i] = h4[i];
+  h_out[4] = req.fin[0];
+  for (int o = 0; o < n_op; ++o) {
+    const double* f = req.fin + 1 + 4 * o;
+    double* r = h_out + 5 + 4 * o;
+    r[0] = f[0] / std::min(req.ops.a[o], req.ops.b[o]);
+    r[1] = (double)req.thr[o];
+    r[2] = 1.0 - f[3] / P;
+    r[3] = f[2] / N;
+  }
+  return SVK_OK;
+}
+
+int svk_decision_counts(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, int64_t n, const float* h_thresholds,
+                        int32_t n_thr, int64_t* h_out) {
+  if (!ctx || !h_out) return SVK_ERR_BAD_ARG;
+  SVK_REQUIRE(ctx, n >= 0, "negative size");
+  SVK_REQUIRE(ctx, n_thr >= 1 && n_thr <= DC_MAX_THR, "1 to 16 thresholds");
+  SVK_REQUIRE(ctx, h_thresholds && ((d_scores && d_labels) || n == 0), "NULL buffer");
+  SVK_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(d_scores) & 3) == 0, "scores must be 4-byte aligned");
+  DcThr thr;
+  for (int t = 0; t < DC_MAX_THR; ++t) thr.v[t] = t < n_thr ? h_thresholds[t] : __builtin_nanf("");
+  for (int t = 0; t < n_thr; ++t) SVK_REQUIRE(ctx, thr.v[t] == thr.v[t], "NaN threshold");
+  const int maxt = n_thr == 1 ? 1 : n_thr <= 4 ? 4 : DC_MAX_THR;
+  unsigned long long h[2 * DC_MAX_THR + 1] = {};
+  if (n > 0) {
+    if (int rc = svk_ensure_work(ctx, sizeof(h))) return rc;
+    auto* counts = static_cast<unsigned long long*>(ctx->work);
+    hipStream_t st = ctx->stream;
+    SVK_HIP(ctx, hipMemsetAsync(counts, 0, sizeof(h), st));
+    const bool vec = (reinterpret_cast<uintptr_t>(d_scores) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_labels) & 3) == 0;
+    const size_t quads = ((size_t)n + 3) / 4;
+    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((quads + RT - 1) / RT, (size_t)ctx->num_cu * 8));
+    auto kern = maxt == 1 ? (vec ? decision_counts_kernel<1, true> : decision_counts_kernel<1, false>)
+              : maxt == 4 ? (vec ? decision_counts_kernel<4, true> : decision_counts_kernel<4, false>)
+                          : (vec ? decision_counts_kernel<DC_MAX_THR, true> : decision_counts_kernel<DC_MAX_THR, false>);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(RT), 0, st, d_scores, d_labels, (size_t)n, thr, counts);
+    SVK_LAUNCH_CHECK(ctx);
+    SVK_HIP(ctx, hipMemcpyAsync(h, counts, sizeof(unsigned long long) * (2 * (size_t)maxt + 1), hipMemcpyDeviceToHost, st));
+    SVK_HIP(ctx, hipStreamSynchronize(st));
+  }
+  for (int t = 0; t < 2 * n_thr; ++t) h_out[t] = (int64_t)h[t];
+  h_out[2 * n_thr] = (int64_t)h[2 * maxt];
+  h_out[2 * n_thr + 1] = n - (int64_t)h[2 * maxt];
   return SVK_OK;
 }
 

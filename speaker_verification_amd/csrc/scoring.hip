@@ -4,6 +4,9 @@
 //       float32 rows (Q18); here the whole [n_test x n_enroll] matrix is one launch on
 //       v_mfma_f32_16x16x4_f32 (exact f32 products, f32 accumulation).
 //   svk_l2_dist       <- /root/reference/siamese.py:29-30.
+//   svk_pair_scores   <- the trial lists of the VoxCeleb protocols (`label utterance_a utterance_b`): one score per index
+//       pair instead of the matrix (VoxCeleb1-E: 6e5 trials over 1.5e5 utterances, 2e10 matrix entries) -- a gather of two
+//       rows per trial, float64 arithmetic.
 #include <algorithm>
 #include <cstdlib>
 
@@ -341,6 +344,81 @@ __global__ __launch_bounds__(256) void l2_dist_kernel(const float* __restrict__ 
   }
 }
 
+// ---- svk_pair_scores ---------------------------------------------------------------------------------------------
+// A TEAM of 16 lanes owns one trial (four trials per wave, sixteen per workgroup); lane t of it owns the columns
+// 4 (t + 16 k) .. + 3 of both rows, k = 0, 1, ...: dim = 128 is two 16-byte loads per row and lane, none idle.  Each lane
+// adds its columns in order in float64 (a product of two floats is exact there, so the fused multiply-adds below round once per
+// addition), the team's partial sums meet in a four-step butterfly (every lane ends with the same bits): the order of additions
+// depends on dim alone.  VEC4 (dim % 4 == 0, both matrices 16-byte aligned) and the scalar loads fill the same registers.
+constexpr int PAIR_TEAM = 16, PAIR_THREADS = 256, PAIR_PER_WG = PAIR_THREADS / PAIR_TEAM;
+
+template <bool VEC4, int METRIC>
+__global__ __launch_bounds__(PAIR_THREADS) void pair_scores_kernel(const float* __restrict__ a, int64_t n_a,
+                                                                   const float* __restrict__ b, int64_t n_b, int dim,
+                                                                   const int64_t* __restrict__ idx_a,
+                                                                   const int64_t* __restrict__ idx_b, int64_t n_pairs,
+                                                                   float* __restrict__ out, int32_t* __restrict__ bad_count) {
+  const int t = threadIdx.x & (PAIR_TEAM - 1);
+  for (int64_t p = (int64_t)blockIdx.x * PAIR_PER_WG + (threadIdx.x / PAIR_TEAM); p < n_pairs;
+       p += (int64_t)gridDim.x * PAIR_PER_WG) {   // (whole teams leave: the butterfly stays inside a team)
+    const int64_t ia = idx_a[p], ib = idx_b[p];
+    if ((uint64_t)ia >= (uint64_t)n_a || (uint64_t)ib >= (uint64_t)n_b) {   // the caller's error: not followed
+      if (t == 0) {
+        out[p] = __builtin_nanf("");
+        if (bad_count) atomicAdd(bad_count, 1);
+      }
+      continue;
+    }
+    const float* ra = a + ia * dim;
+    const float* rb = b + ib * dim;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;   // cosine: x.y, x.x, y.y;  L2: s0 = sum of (x - y)^2
+    for (int col = 4 * t; col < dim; col += 4 * PAIR_TEAM) {
+      float x[4], y[4];
+      if constexpr (VEC4) {
+        const f32x4 vx = *reinterpret_cast<const f32x4*>(ra + col), vy = *reinterpret_cast<const f32x4*>(rb + col);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] = vx[e], y[e] = vy[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          x[e] = col + e < dim ? ra[col + e] : 0.f;
+          y[e] = col + e < dim ? rb[col + e] : 0.f;
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const double dx = (double)x[e], dy = (double)y[e];
+        if constexpr (METRIC == 0) {
+          s0 = fma(dx, dy, s0);
+          s1 = fma(dx, dx, s1);
+          s2 = fma(dy, dy, s2);
+        } else {
+          const double d = dx - dy;
+          s0 = fma(d, d, s0);
+        }
+      }
+    }
+#pragma unroll
+    for (int m = PAIR_TEAM / 2; m >= 1; m >>= 1) {
+      s0 += __shfl_xor(s0, m, 64);
+      if constexpr (METRIC == 0) {
+        s1 += __shfl_xor(s1, m, 64);
+        s2 += __shfl_xor(s2, m, 64);
+      }
+    }
+    if (t == 0) {
+      if constexpr (METRIC == 0) {
+        double na = sqrt(s1), nb = sqrt(s2);
+        na = na == 0.0 ? 1.0 : na;   // sklearn normalize(): a zero norm divides by 1
+        nb = nb == 0.0 ? 1.0 : nb;
+        out[p] = (float)(s0 / (na * nb));
+      } else {
+        out[p] = (float)(-sqrt(s0));
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -391,6 +469,27 @@ int svk_l2_dist(svk_ctx* ctx, const float* d_a, const float* d_b, int32_t n, int
   SVK_REQUIRE(ctx, d_a && d_b && d_out, "NULL buffer");
   const unsigned grid = (unsigned)std::max(1, std::min((n + 3) / 4, ctx->num_cu * 8));
   hipLaunchKernelGGL(l2_dist_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_a, d_b, n, dim, d_out);
+  SVK_LAUNCH_CHECK(ctx);
+  return SVK_OK;
+}
+
+int svk_pair_scores(svk_ctx* ctx, const float* d_a, int64_t n_a, const float* d_b, int64_t n_b, int32_t dim,
+                    const int64_t* d_idx_a, const int64_t* d_idx_b, int64_t n_pairs, int32_t metric, float* d_out,
+                    int32_t* d_bad_count) {
+  if (!ctx) return SVK_ERR_BAD_ARG;
+  SVK_REQUIRE(ctx, n_a >= 0 && n_b >= 0 && n_pairs >= 0, "negative shape");
+  SVK_REQUIRE(ctx, dim >= 1 && dim <= 4096, "dim must be in [1, 4096]");
+  SVK_REQUIRE(ctx, metric == 0 || metric == 1, "metric must be 0 (cosine) or 1 (negated L2 distance)");
+  if (n_pairs == 0) return SVK_OK;
+  SVK_REQUIRE(ctx, d_a && d_b && d_idx_a && d_idx_b && d_out, "NULL buffer");
+  const uintptr_t both = reinterpret_cast<uintptr_t>(d_a) | reinterpret_cast<uintptr_t>(d_b);
+  SVK_REQUIRE(ctx, (both & 3) == 0, "rows must be 4-byte aligned");
+  const bool vec4 = dim % 4 == 0 && (both & 15) == 0;
+  const unsigned grid = (unsigned)std::min<int64_t>((n_pairs + PAIR_PER_WG - 1) / PAIR_PER_WG, (int64_t)ctx->num_cu * 8);
+  auto kern = metric == 0 ? (vec4 ? pair_scores_kernel<true, 0> : pair_scores_kernel<false, 0>)
+                          : (vec4 ? pair_scores_kernel<true, 1> : pair_scores_kernel<false, 1>);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(PAIR_THREADS), 0, ctx->stream, d_a, n_a, d_b, n_b, (int)dim, d_idx_a, d_idx_b,
+                     n_pairs, d_out, d_bad_count);
   SVK_LAUNCH_CHECK(ctx);
   return SVK_OK;
 }

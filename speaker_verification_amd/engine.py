@@ -700,6 +700,51 @@ class Engine:
               self.ctx)
         return float(out[0]), float(out[1])
 
+    def _scores_labels(self, scores, labels):
+        torch = _torch()
+        sc = self.to_device(scores, torch.float32).reshape(-1)
+        lb = self.to_device(labels).reshape(-1)
+        lb = (lb != 0).to(torch.uint8) if lb.dtype != torch.uint8 else lb
+        if lb.numel() != sc.numel():
+            raise ValueError("scores and labels differ in length")
+        return sc, lb
+
+    def roc_dcf(self, scores, labels, operating_points=()):
+        """svk_roc_dcf: EER, AUC, minDCF and the thresholds of flat scores / 0-1 labels from one sort on the device.
+        operating_points: up to 8 (p_target, c_miss, c_fa).  Returns a dict: eer, auc, positives, points, eer_threshold, and one
+        entry per operating point in the lists min_dcf, threshold, p_miss, p_fa (accept when score >= threshold; the origin of
+        the ROC, "reject everything", has threshold +inf).  eer and auc are roc_eer's values, bit for bit.  Raises for a
+        non-finite score or a single class."""
+        torch = _torch()
+        sc, lb = self._scores_labels(scores, labels)
+        n = sc.numel()
+        ops = np.ascontiguousarray(np.asarray(operating_points, dtype=np.float64).reshape(-1, 3))
+        n_op = int(ops.shape[0])
+        work = torch.empty((max(1, int(self.lib.svk_roc_dcf_workspace_bytes(n))),), dtype=torch.uint8, device=self.device)
+        out = (C.c_double * (5 + 4 * max(n_op, 0)))()
+        self._stream()
+        check(self.lib.svk_roc_dcf(self.ctx, self._ptr(sc), self._ptr(lb), n, ops.ctypes.data_as(C.POINTER(C.c_double)), n_op,
+                                   self._ptr(work), work.numel(), out), self.ctx)
+        res = {"eer": float(out[0]), "auc": float(out[1]), "positives": int(out[2]), "points": int(out[3]),
+               "eer_threshold": float(out[4])}
+        for j, name in enumerate(("min_dcf", "threshold", "p_miss", "p_fa")):
+            res[name] = [float(out[5 + 4 * o + j]) for o in range(n_op)]
+        return res
+
+    def decision_counts(self, scores, labels, thresholds):
+        """svk_decision_counts: one pass over unsorted scores / 0-1 labels.  thresholds: 1 to 16 floats (+-inf allowed).  Returns
+        (accepted int64 [n_thr, 2], totals): accepted[t] = (targets, non-targets) with score >= thresholds[t], totals = (targets,
+        non-targets) of the set.  A NaN score is never accepted."""
+        sc, lb = self._scores_labels(scores, labels)
+        thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))
+        n_thr = int(thr.size)
+        out = (C.c_int64 * (2 * max(n_thr, 1) + 2))()
+        self._stream()
+        check(self.lib.svk_decision_counts(self.ctx, self._ptr(sc), self._ptr(lb), sc.numel(),
+                                           thr.ctypes.data_as(C.POINTER(C.c_float)), n_thr, out), self.ctx)
+        flat = np.array(out[:2 * n_thr + 2], dtype=np.int64)
+        return flat[:2 * n_thr].reshape(n_thr, 2), (int(flat[2 * n_thr]), int(flat[2 * n_thr + 1]))
+
     def roc_k(self, scores, labels, k=1, curve=False):
         """svk_roc_k: per split of `split_step(n, k)` consecutive pairs (evaluation.py:11-33), (eer, auc), or with
         curve=True (eer, auc, fpr, tpr): sklearn's roc_curve(drop_intermediate=True) as float64 NumPy arrays, fps / fps[-1]
@@ -784,6 +829,33 @@ class Engine:
         check(self.lib.svk_embedding_pool(self.ctx, self._ptr(x), n_rows, dim, n_seg, K, self._ptr(start), self._ptr(index),
                                           int(bool(l2_rows)) | 2 * int(bool(l2_mean)), self._ptr(out), self._ptr(empty_count)),
               self.ctx)
+        return out
+
+    PAIR_METRICS = {"cosine": 0, "l2": 1}
+
+    def pair_scores(self, a, b, idx_a, idx_b, metric="cosine", bad_count=None):
+        """svk_pair_scores: out[p] = score of a[idx_a[p]] against b[idx_b[p]] for a trial list -> float32 [n_pairs] on the
+        device.  metric: "cosine", or "l2" = -||x - y|| (larger = same speaker); b may be a itself.  An index outside its matrix
+        gives NaN at that trial and counts in bad_count (an int32 [1] device tensor the caller zeroes), if given."""
+        torch = _torch()
+        if metric not in self.PAIR_METRICS:
+            raise ValueError("metric must be 'cosine' or 'l2', got %r" % (metric,))
+        x = self.to_device(a, torch.float32)
+        y = x if b is a else self.to_device(b, torch.float32)
+        if x.dim() != 2 or y.dim() != 2 or x.shape[1] != y.shape[1]:
+            raise ValueError("pair_scores wants (Na, D) and (Nb, D)")
+        ia = self.to_device(idx_a, torch.int64).reshape(-1)
+        ib = self.to_device(idx_b, torch.int64).reshape(-1)
+        if ia.numel() != ib.numel():
+            raise ValueError("idx_a and idx_b differ in length")
+        if bad_count is not None and not (isinstance(bad_count, torch.Tensor) and bad_count.is_cuda
+                                          and bad_count.dtype == torch.int32 and bad_count.numel() >= 1):
+            raise ValueError("bad_count must be an int32 device tensor")
+        out = torch.empty((ia.numel(),), dtype=torch.float32, device=self.device)
+        self._stream()
+        check(self.lib.svk_pair_scores(self.ctx, self._ptr(x), x.shape[0], self._ptr(y), y.shape[0], x.shape[1], self._ptr(ia),
+                                       self._ptr(ib), ia.numel(), self.PAIR_METRICS[metric], self._ptr(out),
+                                       self._ptr(bad_count)), self.ctx)
         return out
 
     def l2_dist(self, a, b):

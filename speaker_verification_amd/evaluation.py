@@ -12,6 +12,10 @@ computes them (sklearn + scipy, evaluation.py:47-52, 112-134).  `device=True`
 (`get_and_plot_k_eer_auc`, `evaluate`) keeps the score matrix on the GPU:
 `svk_top1` for the argmax, hits and one-hot labels, ONE `svk_roc_k` call for the
 k splits and their ROC curves; `get_eer_auc_device` is the single-split form.
+
+Trial lists (the `label utterance_a utterance_b` protocols of VoxCeleb1, which the reference does not read): `read_trials` /
+`make_trials` build the index pairs, `evaluate_trials` scores them with `svk_pair_scores` and reports EER, AUC, minDCF and the
+thresholds (`svk_roc_dcf`; `get_min_dcf` is the host form of the same definition).
 """
 import os
 
@@ -41,6 +45,149 @@ def get_eer_auc_device(label, distance, curve=False):
     if curve:
         return get_engine().roc_k(distance, label, k=1, curve=True)[0]
     return get_engine().roc_eer(distance, label)
+
+
+DEFAULT_OPERATING_POINTS = ((0.01, 1, 1), (0.05, 1, 1))      # (p_target, c_miss, c_fa): the two VoxCeleb results quote
+
+
+def get_min_dcf(label, distance, p_target, c_miss=1, c_fa=1):
+    """(min_dcf, threshold, p_miss, p_fa) on the host, float64 NumPy over sklearn's roc_curve(drop_intermediate=False): the
+    candidates are the curve's origin (reject everything, threshold +inf) and one point per distinct score in descending
+    order; cost = c_miss p_target (1 - tpr) + c_fa (1 - p_target) fpr; min_dcf = the smallest cost / min(c_miss p_target,
+    c_fa (1 - p_target)); among equal costs the first point (the highest threshold) wins.  Accept when score >= threshold."""
+    from sklearn.metrics import roc_curve
+    if not (0.0 < p_target < 1.0 and c_miss > 0 and c_fa > 0):
+        raise ValueError("need 0 < p_target < 1 and c_miss, c_fa > 0")
+    fpr, tpr, thresholds = roc_curve(np.asarray(label).reshape(-1), np.asarray(distance).reshape(-1), pos_label=1,
+                                     drop_intermediate=False)
+    a, b = float(c_miss) * float(p_target), float(c_fa) * (1.0 - float(p_target))
+    cost = a * (1.0 - tpr) + b * fpr
+    j = int(np.argmin(cost))                         # the first of equal minima
+    threshold = float("inf") if j == 0 else float(thresholds[j])
+    return float(cost[j] / min(a, b)), threshold, float(1.0 - tpr[j]), float(fpr[j])
+
+
+def read_trials(path_or_lines):
+    """A trial list -- lines of `label name_a name_b`, label 1 = same speaker, 0 = different; blank lines and lines starting
+    with `#` are skipped -- from a path or an iterable of lines.  Returns (labels uint8 [n], idx_a int64 [n], idx_b int64 [n],
+    names): the indices point into `names`, every distinct name once, in order of first appearance (the row order the
+    embeddings are wanted in).  ValueError names the line for a malformed line or a label other than 0 or 1."""
+    if isinstance(path_or_lines, (str, os.PathLike)):
+        with open(path_or_lines) as fh:
+            return read_trials(fh.readlines())
+    index, names, labels, ia, ib = {}, [], [], [], []
+    for number, line in enumerate(path_or_lines, 1):
+        text = line.strip()
+        if not text or text.startswith("#"):
+            continue
+        parts = text.split()
+        if len(parts) != 3:
+            raise ValueError("trial list line %d: want `label name_a name_b`, got %r" % (number, text))
+        if parts[0] not in ("0", "1"):
+            raise ValueError("trial list line %d: label must be 0 or 1, got %r" % (number, parts[0]))
+        labels.append(int(parts[0]))
+        for name, dst in ((parts[1], ia), (parts[2], ib)):
+            if name not in index:
+                index[name] = len(names)
+                names.append(name)
+            dst.append(index[name])
+    return np.array(labels, dtype=np.uint8), np.array(ia, dtype=np.int64), np.array(ib, dtype=np.int64), names
+
+
+def make_trials(speaker_ids, n_target, n_nontarget, seed):
+    """A seeded trial list for a corpus without an official one: n_target pairs (i, j) of the same speaker and n_nontarget
+    of different speakers, i != j, no unordered pair twice.  Returns (labels uint8, idx_a int64, idx_b int64), targets
+    first.  ValueError when the corpus holds fewer such pairs than asked for."""
+    ids = np.asarray(speaker_ids)
+    n = int(ids.size)
+    _, inv = np.unique(ids, return_inverse=True)
+    sizes = np.bincount(inv) if n else np.zeros(0, dtype=np.int64)
+    have_t = int(np.sum(sizes * (sizes - 1) // 2))
+    have_n = n * (n - 1) // 2 - have_t
+    if n_target < 0 or n_nontarget < 0 or n_target > have_t or n_nontarget > have_n:
+        raise ValueError("make_trials: %d target / %d non-target pairs asked for, the %d utterances hold %d / %d"
+                         % (n_target, n_nontarget, n, have_t, have_n))
+    rng = np.random.default_rng(seed)
+    members = [np.nonzero(inv == s)[0] for s in range(sizes.size) if sizes[s] >= 2]
+    small = 1 << 22                                   # up to here every candidate pair is listed and the draw is a choice
+
+    def sample(pairs, count):
+        return pairs[rng.choice(pairs.shape[0], size=count, replace=False)]
+
+    def reject(count, propose):
+        seen, out = set(), []
+        while len(out) < count:
+            i, j = propose()
+            key = (min(i, j), max(i, j))
+            if key not in seen:
+                seen.add(key)
+                out.append((i, j))
+        return np.array(out, dtype=np.int64).reshape(-1, 2)
+
+    def same():
+        m = members[int(rng.choice(len(members), p=weights))]
+        i, j = rng.choice(m.size, size=2, replace=False)
+        return int(m[i]), int(m[j])
+
+    def differ():
+        while True:
+            i, j = (int(v) for v in rng.integers(0, n, size=2))
+            if inv[i] != inv[j]:
+                return i, j
+
+    if n_target == 0:
+        tgt = np.zeros((0, 2), dtype=np.int64)
+    elif have_t <= small:
+        tgt = sample(np.concatenate([np.stack([m[a] for a in np.triu_indices(m.size, 1)], axis=1) for m in members]), int(n_target))
+    else:
+        weights = np.array([m.size * (m.size - 1) / 2.0 for m in members])
+        weights /= weights.sum()
+        tgt = reject(int(n_target), same)
+    if n_nontarget == 0:
+        non = np.zeros((0, 2), dtype=np.int64)
+    elif n * (n - 1) // 2 <= small:
+        i, j = np.triu_indices(n, 1)
+        keep = inv[i] != inv[j]
+        non = sample(np.stack([i[keep], j[keep]], axis=1), int(n_nontarget))
+    else:
+        non = reject(int(n_nontarget), differ)
+    idx = np.concatenate([tgt, non]).astype(np.int64)
+    labels = np.r_[np.ones(int(n_target), dtype=np.uint8), np.zeros(int(n_nontarget), dtype=np.uint8)]
+    return labels, np.ascontiguousarray(idx[:, 0]), np.ascontiguousarray(idx[:, 1])
+
+
+def evaluate_trials(embeddings, labels, idx_a, idx_b, metric="cosine", operating_points=DEFAULT_OPERATING_POINTS, device=True):
+    """Verification over a trial list: trial p compares embeddings[idx_a[p]] with embeddings[idx_b[p]] (`svk_pair_scores`,
+    metric "cosine" or "l2"), labels[p] = 1 for the same speaker.  Returns a dict: eer, auc, eer_threshold, and per operating
+    point (p_target, c_miss, c_fa) the lists min_dcf, threshold, p_miss, p_fa; scores = the float32 trial scores on the device.
+    device=True: one `svk_roc_dcf` call; device=False: the same device scores, metrics on the host (`get_eer_auc`,
+    `get_min_dcf`; eer_threshold by the same rule, the first point of the curve where 1 - fpr - tpr <= 0).  An index outside
+    the embeddings raises ValueError."""
+    eng = get_engine()
+    bad = torch.zeros((1,), dtype=torch.int32, device=eng.device)
+    emb = eng.to_device(embeddings, torch.float32)
+    scores = eng.pair_scores(emb, emb, idx_a, idx_b, metric=metric, bad_count=bad)
+    if int(bad.item()):
+        raise ValueError("evaluate_trials: %d trials index outside the %d embeddings" % (int(bad.item()), emb.shape[0]))
+    labels = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1)
+    if labels.size != scores.numel():
+        raise ValueError("one label per trial")
+    ops = [tuple(float(v) for v in op) for op in operating_points]
+    if device:
+        res = eng.roc_dcf(scores, labels, ops)
+        out = {k: res[k] for k in ("eer", "auc", "eer_threshold", "min_dcf", "threshold", "p_miss", "p_fa")}
+    else:
+        from sklearn.metrics import roc_curve
+        sc = scores.cpu().numpy()
+        eer, auc, _, _ = get_eer_auc(labels, sc)
+        fpr, tpr, thr = roc_curve(labels, sc, pos_label=1, drop_intermediate=False)
+        at = int(np.nonzero(1.0 - fpr - tpr <= 0)[0][0])
+        rows = [get_min_dcf(labels, sc, *op) for op in ops]
+        out = {"eer": float(eer), "auc": float(auc), "eer_threshold": float(thr[at]),
+               "min_dcf": [r[0] for r in rows], "threshold": [r[1] for r in rows], "p_miss": [r[2] for r in rows],
+               "p_fa": [r[3] for r in rows]}
+    out["scores"] = scores
+    return out
 
 
 def get_and_plot_k_eer_auc(label, scores, k=1, plot_path='eer_auc.png', device=False):

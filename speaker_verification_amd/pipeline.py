@@ -742,6 +742,13 @@ class VerificationPipeline:
     def score(self, test_emb, enroll_emb):
         return self.eng.cosine_scores(test_emb, enroll_emb)
 
+    def score_trials(self, emb_a, idx_a, idx_b, emb_b=None, metric="cosine"):
+        """One score per trial (emb_a[idx_a[p]] against emb_b[idx_b[p]], emb_b = emb_a when not given) through
+        `svk_pair_scores` -> float32 [n_trials] on the device: a VoxCeleb-style trial list instead of the whole matrix of
+        `score`.  On several GPUs call it on the all-gathered embeddings (`distributed.all_gather_embeddings`); every rank
+        then holds the whole list's scores (the trial list itself is not sharded)."""
+        return self.eng.pair_scores(emb_a, emb_a if emb_b is None else emb_b, idx_a, idx_b, metric=metric)
+
 
 def enroll_last_utterance(embeddings, speaker_ids):
     """Speaker model = embedding of that speaker's LAST listed utterance: the reference
