@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
+#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
 
 typedef enum svk_status {
   SVK_OK = 0,
@@ -306,6 +306,43 @@ int svk_embedding_pool(svk_ctx* ctx, const float* d_emb, int64_t n_rows, int32_t
 int svk_pair_scores(svk_ctx* ctx, const float* d_a, int64_t n_a, const float* d_b, int64_t n_b, int32_t dim,
                     const int64_t* d_idx_a, const int64_t* d_idx_b, int64_t n_pairs, int32_t metric, float* d_out,
                     int32_t* d_bad_count);
+
+/* Speaker SEARCH: the k best rows of a gallery for every query row by cosine score, without the [n_query][n_gallery] matrix
+ * that svk_cosine_scores writes and svk_top1 / a framework's top-k reads back (148 642 x 1 211: 720 MB each way; a corpus
+ * against itself or against 10^6 enrolled speakers: more than the card holds).  The product runs as in svk_cosine_scores'
+ * tiled kernel; each wave keeps a sorted list of k entries per query row on chip, and a second kernel merges the lists of
+ * the gallery spans.
+ *   d_query, d_gallery   [n_query][dim], [n_gallery][dim] f32, 4-byte aligned.  16-byte loads when dim % 4 == 0 and both are
+ *                 16-byte aligned, 4-byte loads otherwise: the same bits either way
+ *   d_top_score   f32 [n_query][k], d_top_index int64 [n_query][k]: the k best gallery rows of query q, best first.  An index is
+ *                 index_base + j for row j of THIS call's d_gallery (index_base >= 0); slots beyond the number of candidates
+ *                 hold index -1 and score -inf
+ *   order         ONE strict total order, in the selection, in the merge and in accumulation: the higher score first; a NaN
+ *                 score above every number (as svk_top1 and svk_c3d2_head put it); among equal scores (-0 == +0, all NaNs
+ *                 equal) the lower index first.  The order being total, the result does not depend on how the work was split
+ *   flags         bit 0 (1), accumulate: on entry the outputs hold lists of that form from earlier calls (sorted, -1 / -inf in
+ *                 the empty slots); the result is the k best of that list and this call's gallery together.  With index_base
+ *                 this searches a gallery that is streamed in chunks or larger than device memory with one set of lists: the
+ *                 result equals ONE call over the concatenated gallery bit for bit, for any chunking with disjoint index
+ *                 ranges, presented in any order.  Every other bit must be 0
+ *   d_exclude     NULL, or int64 [n_query]: the gallery row whose global index (index_base + j) equals d_exclude[q] is not a
+ *                 candidate for query q -- a self-search, where query q is row q of the gallery.  A value outside this call's
+ *                 range excludes nothing
+ *   d_workspace   svk_cosine_topk_workspace_bytes(n_query, n_gallery, dim, k) bytes, 16-byte aligned (the 1 / norms of both
+ *                 matrices and the partial lists, 8 k bytes per query and gallery span); the size depends on the shape alone
+ *                 and is 0 for arguments the call rejects (and for n_query == 0 or n_gallery == 0, which need none)
+ * The score is what svk_cosine_scores' tiled path computes: f32 products and f32 accumulation on v_mfma_f32_16x16x4_f32 in
+ * a K order fixed by dim, times 1 / ||q|| and 1 / ||g||, each formed in f32 by a pre-pass over its matrix; a zero norm divides
+ * by 1, so a zero row scores 0.  There is ONE arithmetic for every shape: the bits of a score depend on the two rows and dim
+ * alone, not on n_query, n_gallery, the row's position, the launch geometry, the chunking or k; runs are bit-identical.
+ * 1 <= dim <= 4096, 1 <= k <= 32.  n_query == 0 launches nothing; n_gallery == 0 leaves the lists as they are with the
+ * accumulate flag and fills them with -1 / -inf without it.  SVK_ERR_BAD_ARG: NULL context or buffer, negative size, dim or k
+ * out of range, undefined flag bits, a negative index_base, misalignment, a workspace below the size above.  Asynchronous on
+ * the context's stream: no host round trip. */
+size_t svk_cosine_topk_workspace_bytes(int32_t n_query, int32_t n_gallery, int32_t dim, int32_t k);
+int svk_cosine_topk(svk_ctx* ctx, const float* d_query, int32_t n_query, const float* d_gallery, int32_t n_gallery,
+                    int32_t dim, int32_t k, int64_t index_base, const int64_t* d_exclude, int32_t flags,
+                    void* d_workspace, size_t workspace_bytes, float* d_top_score, int64_t* d_top_index);
 
 /* ---- ROC / EER / AUC on the device ------------------------------------------------------------
  * evaluation.py:47-52 (sklearn roc_curve + roc_auc_score + brentq on interp1d) for pair sets too

@@ -858,6 +858,41 @@ class Engine:
                                        self._ptr(bad_count)), self.ctx)
         return out
 
+    def cosine_topk(self, query, gallery, k, exclude=None, index_base=0, into=None):
+        """svk_cosine_topk: the k best gallery rows of every query row by cosine score, without the score matrix ->
+        (scores float32 [n, k], indices int64 [n, k]) on the device, best first; an index is index_base + the gallery row,
+        empty slots hold -1 / -inf.  Higher score first, NaN above every number, the lower index among equal scores.
+        exclude: int64 [n], the global index that is no candidate for each query (a self-search).  into=(scores, indices):
+        accumulate into those tensors (lists of earlier calls over other chunks of the gallery, disjoint index ranges); the
+        result equals one call over the whole gallery bit for bit.  The workspace is a torch allocation sized by the library."""
+        torch = _torch()
+        q = self.to_device(query, torch.float32)
+        g = self.to_device(gallery, torch.float32)
+        if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
+            raise ValueError("cosine_topk wants (Nq, D) and (Ng, D)")
+        n, ng, dim, k = int(q.shape[0]), int(g.shape[0]), int(q.shape[1]), int(k)
+        ex = None
+        if exclude is not None:
+            ex = self.to_device(exclude, torch.int64).reshape(-1)
+            if ex.numel() != n:
+                raise ValueError("exclude holds one index per query row")
+        if into is None:
+            scores = torch.empty((n, max(k, 0)), dtype=torch.float32, device=self.device)
+            indices = torch.empty((n, max(k, 0)), dtype=torch.int64, device=self.device)
+        else:
+            scores, indices = into
+            for t, dt in ((scores, torch.float32), (indices, torch.int64)):
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()
+                        and tuple(t.shape) == (n, k)):
+                    raise ValueError("into wants contiguous device tensors (float32 [n, k], int64 [n, k])")
+        work = torch.empty((max(16, int(self.lib.svk_cosine_topk_workspace_bytes(n, ng, dim, k))),), dtype=torch.uint8,
+                           device=self.device)
+        self._stream()
+        check(self.lib.svk_cosine_topk(self.ctx, self._ptr(q), n, self._ptr(g), ng, dim, k, int(index_base), self._ptr(ex),
+                                       0 if into is None else 1, self._ptr(work), work.numel(), self._ptr(scores),
+                                       self._ptr(indices)), self.ctx)
+        return scores, indices
+
     def l2_dist(self, a, b):
         torch = _torch()
         a = self.to_device(a, torch.float32)

@@ -527,3 +527,32 @@ def identification_accuracy(model, data, labels=None, topk=(1, 5), batch=4096):
     out["predicted"] = np.concatenate(predicted) if predicted else np.zeros(0, dtype=np.int32)
     out["n"] = n
     return out
+
+
+def rank_speakers(test_embeddings, enroll_embeddings, speaker_ids, k=5, threshold=None):
+    """The k nearest enrolled speakers of every test utterance (`svk_cosine_topk`: no score matrix) -> {"ids": [n][k] lists of
+    speaker ids, best first, "scores": float32 [n, k], "indices": int64 [n, k]} (NumPy).  speaker_ids[j] names row j of
+    enroll_embeddings.  threshold: open-set rejection -- an entry whose score is below it (or a slot past the enrolled rows,
+    index -1) is reported as None; a NaN score is never below a threshold."""
+    speaker_ids = list(speaker_ids)
+    if len(speaker_ids) != int(enroll_embeddings.shape[0]):
+        raise ValueError("one speaker id per enrolled row")
+    scores, indices = get_engine().cosine_topk(test_embeddings, enroll_embeddings, k)
+    scores, indices = scores.cpu().numpy(), indices.cpu().numpy()
+    keep = indices >= 0
+    if threshold is not None:
+        keep &= ~(scores < np.float32(threshold))
+    ids = [[speaker_ids[j] if ok else None for j, ok in zip(row, row_ok)] for row, row_ok in zip(indices, keep)]
+    return {"ids": ids, "scores": scores, "indices": indices}
+
+
+def topk_hits(indices, true_columns):
+    """hits int64 [k] from top-k lists indices [n, k] (best first, -1 = empty slot) and the true column of every row [n]
+    (-1 = not enrolled): hits[r] = the rows whose true column is among their first r + 1 entries -- the meaning of
+    svk_c3d2_head's h_hits; -1 never counts.  Pure NumPy; 100 hits[r] / n is the rank-(r + 1) accuracy."""
+    indices = np.asarray(indices)
+    true_columns = np.asarray(true_columns).reshape(-1)
+    if indices.ndim != 2 or indices.shape[0] != true_columns.size:
+        raise ValueError("topk_hits wants indices (n, k) and one true column per row")
+    match = (indices == true_columns[:, None]) & (indices >= 0)
+    return np.cumsum(match, axis=1).astype(bool).sum(axis=0).astype(np.int64)

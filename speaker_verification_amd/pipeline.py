@@ -742,6 +742,36 @@ class VerificationPipeline:
     def score(self, test_emb, enroll_emb):
         return self.eng.cosine_scores(test_emb, enroll_emb)
 
+    SEARCH_UPLOAD_BYTES = 1 << 30       # a host gallery above this is uploaded and searched in chunks of about this size
+
+    def search(self, test_emb, enroll_emb, k=1, exclude_self=False, chunk_rows=None):
+        """The k best enrolled rows of every test row by cosine score (`svk_cosine_topk`: the score matrix of `score` is
+        never written) -> (scores float32 [n, k], indices int64 [n, k]) on the device, best first, -1 / -inf past the
+        enrolled rows.  enroll_emb: a device tensor or a host array.  With chunk_rows, or for a host array above
+        SEARCH_UPLOAD_BYTES, the gallery is uploaded and searched chunk by chunk into one set of lists (the accumulate flag):
+        the same bits as one call.  exclude_self: the two sides are the same rows and row q is no candidate for query q."""
+        eng = self.eng
+        n_gallery, dim = int(enroll_emb.shape[0]), int(enroll_emb.shape[1])
+        query = eng.to_device(test_emb, torch.float32)
+        exclude = None
+        if exclude_self:
+            if int(query.shape[0]) != n_gallery:
+                raise ValueError("exclude_self wants the same rows on both sides (%d against %d)" % (query.shape[0], n_gallery))
+            exclude = torch.arange(n_gallery, dtype=torch.int64, device=eng.device)
+        on_host = not (isinstance(enroll_emb, torch.Tensor) and enroll_emb.is_cuda)
+        if chunk_rows is None and on_host and 4 * n_gallery * dim > self.SEARCH_UPLOAD_BYTES:
+            chunk_rows = max(1, self.SEARCH_UPLOAD_BYTES // (4 * dim))
+        if chunk_rows is None or n_gallery == 0:
+            return eng.cosine_topk(query, enroll_emb, k, exclude=exclude)
+        chunk_rows = int(chunk_rows)
+        if chunk_rows < 1:
+            raise ValueError("chunk_rows must be at least 1")
+        into = None
+        for lo in range(0, n_gallery, chunk_rows):
+            out = eng.cosine_topk(query, enroll_emb[lo:lo + chunk_rows], k, exclude=exclude, index_base=lo, into=into)
+            into = out
+        return into
+
     def score_trials(self, emb_a, idx_a, idx_b, emb_b=None, metric="cosine"):
         """One score per trial (emb_a[idx_a[p]] against emb_b[idx_b[p]], emb_b = emb_a when not given) through
         `svk_pair_scores` -> float32 [n_trials] on the device: a VoxCeleb-style trial list instead of the whole matrix of
