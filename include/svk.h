@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
+#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_class_scatter, svk_class_scatter_workspace_bytes, svk_embedding_project (the embedding back end: class statistics in float64 and centre / project / length-normalise in one pass); earlier additions under the same number: + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
 
 typedef enum svk_status {
   SVK_OK = 0,
@@ -288,6 +288,54 @@ int svk_l2_dist(svk_ctx* ctx, const float* d_a, const float* d_b, int32_t n, int
 int svk_embedding_pool(svk_ctx* ctx, const float* d_emb, int64_t n_rows, int32_t dim, int64_t n_seg, int32_t rows_per_seg,
                        const int64_t* d_seg_start, const int64_t* d_row_index, int32_t flags, float* d_out,
                        int32_t* d_empty_count);
+
+/* ---- embedding back end (csrc/backend.hip) ---------------------------------
+ * The statistics a back end (centring, LDA, WCCN, whitening: backend.py) is fitted on: the float64 mean of every class and the
+ * within-class scatter  S_w = sum_c sum_{i in c} (x_i - m_c)(x_i - m_c)^T  of labelled embedding rows.
+ *   d_emb         [n_rows][dim] f32, 4-byte aligned
+ *   segments      d_seg_start int64 [n_class + 1] and d_row_index (NULL or int64 [n_rows]) mean what they mean in
+ *                 svk_embedding_pool: class c is rows d_row_index[start[c] : start[c + 1]]; offsets are clamped, never followed;
+ *                 a row index outside [0, n_rows) is not read and makes its class NaN (its mean, and through it d_sw, unless
+ *                 the class has fewer than two rows); rows outside every class are ignored
+ *   flags         bit 0 (1): every row enters as x / ||x|| with a float64 norm, a zero row as zeros; every other bit must be 0
+ *   d_class_mean  float64 [n_class][dim]: the mean of the class, rows added in order inside blocks of 64 rows and the blocks'
+ *                 sums in order; an empty class gives zeros.  A class's mean has the bits it has when it is the only class
+ *   d_sw          float64 [dim][dim], computed from the CENTRED rows (two-pass, not sum x x^T - n m m^T) on
+ *                 v_mfma_f64_16x16x4_f64 with the rows as K.  A class of one row contributes exactly zero: classes of fewer
+ *                 than two rows are left out, and their presence changes no bit of d_sw
+ *   d_workspace   svk_class_scatter_workspace_bytes(n_rows, dim, n_class) bytes, 16-byte aligned (the row norms, the prefix sums
+ *                 of the class sizes and the partial matrices); 0 for arguments the call rejects and for n_class == 0
+ * Determinism: no floating-point atomics.  The rows of the classes with two or more rows, in class order, are cut into chunks
+ * whose length depends on dim alone; each chunk's partial matrix is an MFMA chain in row order and the partial matrices are
+ * added in chunk order.  The bits depend on the rows, the segments, dim and flags alone -- not on the launch geometry, a
+ * counter or timing: runs are bit-identical, and d_sw[a][b] == d_sw[b][a] bit for bit (only the upper triangle is computed).
+ * NaN: a NaN at column a of one row makes that class's mean NaN at column a, and row a and column a of d_sw (flag bit 0 set:
+ * the row's norm is NaN and so is the whole row).  1 <= dim <= 512; n_class == 0 writes a zero d_sw and launches nothing else.
+ * The global mean, S_b and S_t = S_w + S_b are n_class x dim numbers: the host forms them (backend.solve).  Asynchronous on the
+ * context's stream.  SVK_ERR_BAD_ARG: NULL context or buffer, negative size, dim outside [1, 512], undefined flag bits,
+ * misalignment (f32: 4 bytes; int64 / float64: 8; workspace: 16), a short workspace. */
+size_t svk_class_scatter_workspace_bytes(int64_t n_rows, int32_t dim, int64_t n_class);
+int svk_class_scatter(svk_ctx* ctx, const float* d_emb, int64_t n_rows, int32_t dim, const int64_t* d_seg_start,
+                      const int64_t* d_row_index, int64_t n_class, int32_t flags, void* d_workspace, size_t workspace_bytes,
+                      double* d_class_mean, double* d_sw);
+
+/* The per-embedding half of the back end, one trip through HBM:  y = l2( (l2(x) - mu) W ).  ONE arithmetic for every shape:
+ *   flags bit 0 (1)   x' = (float)(x / ||x||): the sum of squares, the square root and the division in float64, rounded once; a
+ *                     zero row gives zeros.  Clear: x' = x
+ *   c = x' - mu       in f32; d_mean NULL (mu = 0) or f32 [dim]
+ *   y_j = sum_k c_k W_kj   f32 products, f32 accumulation on v_mfma_f32_16x16x4_f32; d_w f32 [dim][out_dim] row-major.  The order
+ *                     of k is fixed by dim: super-steps of 16, inside one the k = 16 S + 4 g + e in the order (e, g)
+ *   flags bit 1 (2)   y / ||y||: the sum of squares of the f32 y, the square root and the division in float64, rounded once; a
+ *                     zero y stays zero.  The y that is normalised has the bits the call gives with the bit clear
+ *   d_w NULL          the identity: out_dim must equal dim, y = c exactly, no matrix pipe
+ *   d_out             f32 [n_rows][out_dim]; must not be d_emb
+ * A wave owns 16 rows and all their output tiles; W is staged through LDS sixteen k at a time.  Loads of x and mu are 16-byte
+ * when dim % 4 == 0 and both are 16-byte aligned, 4-byte otherwise: the same bits either way.  The bits of a row's output
+ * depend on that row, mu, W, dim, out_dim and flags alone -- not on n_rows, the row's position or the geometry; NaN stays in
+ * its own row.  1 <= out_dim <= dim <= 512; n_rows == 0 launches nothing.  SVK_ERR_BAD_ARG: NULL context or buffer, negative
+ * size, dims out of range, NULL d_w with out_dim != dim, undefined flag bits, misalignment, d_out == d_emb. */
+int svk_embedding_project(svk_ctx* ctx, const float* d_emb, int64_t n_rows, int32_t dim, const float* d_mean, const float* d_w,
+                          int32_t out_dim, int32_t flags, float* d_out);
 
 /* One score per TRIAL of a list (the `label utterance_a utterance_b` lines of the VoxCeleb1 protocols) instead of the whole
  * matrix of svk_cosine_scores or the row-i-against-row-i of svk_l2_dist; replaces the a[idx_a], b[idx_b] gathers and the

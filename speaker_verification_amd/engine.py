@@ -831,6 +831,61 @@ class Engine:
               self.ctx)
         return out
 
+    def class_scatter(self, emb, seg_start, row_index=None, l2_rows=False):
+        """svk_class_scatter: the float64 class means [n_class, dim] and the within-class scatter S_w [dim, dim] (two-pass, on
+        the centred rows) of emb [n_rows, dim] f32 -> two float64 device tensors.  Class c is rows
+        row_index[seg_start[c] : seg_start[c + 1]] (`pipeline.speaker_segments`); l2_rows: every row enters L2-normalised.
+        Bit-identical from run to run, S_w symmetric bit for bit.  The workspace is a torch allocation sized by the library."""
+        torch = _torch()
+        x = self.to_device(emb, torch.float32)
+        if x.dim() != 2:
+            raise ValueError("class_scatter wants rows (n_rows, dim)")
+        n_rows, dim = int(x.shape[0]), int(x.shape[1])
+        start = self.to_device(seg_start, torch.int64).reshape(-1)
+        if start.numel() < 1:
+            raise ValueError("seg_start holds n_class + 1 offsets")
+        n_class = start.numel() - 1
+        index = None
+        if row_index is not None:
+            index = self.to_device(row_index, torch.int64).reshape(-1)
+            if index.numel() != n_rows:
+                raise ValueError("row_index holds one entry per row of emb")
+        work = torch.empty((max(16, int(self.lib.svk_class_scatter_workspace_bytes(n_rows, dim, n_class))),), dtype=torch.uint8,
+                           device=self.device)
+        mean = torch.empty((n_class, dim), dtype=torch.float64, device=self.device)
+        sw = torch.empty((dim, dim), dtype=torch.float64, device=self.device)
+        self._stream()
+        check(self.lib.svk_class_scatter(self.ctx, self._ptr(x), n_rows, dim, self._ptr(start), self._ptr(index), n_class,
+                                         int(bool(l2_rows)), self._ptr(work), work.numel(), self._ptr(mean), self._ptr(sw)),
+              self.ctx)
+        return mean, sw
+
+    def embedding_project(self, emb, mean=None, w=None, l2_in=False, l2_out=False):
+        """svk_embedding_project: y = l2_out((l2_in(x) - mean) @ w) for every row of emb [n, dim] -> float32 [n, out_dim] on the
+        device in one pass.  mean: None or [dim]; w: None (the identity) or [dim, out_dim], out_dim <= dim <= 512.  The norms
+        are float64, the product is f32 on the matrix pipe; a row's bits depend on that row alone."""
+        torch = _torch()
+        x = self.to_device(emb, torch.float32)
+        if x.dim() != 2:
+            raise ValueError("embedding_project wants rows (n, dim)")
+        n, dim = int(x.shape[0]), int(x.shape[1])
+        mu = None
+        if mean is not None:
+            mu = self.to_device(mean, torch.float32).reshape(-1)
+            if mu.numel() != dim:
+                raise ValueError("mean holds one entry per column of emb")
+        out_dim, wt = dim, None
+        if w is not None:
+            wt = self.to_device(w, torch.float32)
+            if wt.dim() != 2 or int(wt.shape[0]) != dim:
+                raise ValueError("w wants (dim, out_dim)")
+            out_dim = int(wt.shape[1])
+        out = torch.empty((n, out_dim), dtype=torch.float32, device=self.device)
+        self._stream()
+        check(self.lib.svk_embedding_project(self.ctx, self._ptr(x), n, dim, self._ptr(mu), self._ptr(wt), out_dim,
+                                             int(bool(l2_in)) | 2 * int(bool(l2_out)), self._ptr(out)), self.ctx)
+        return out
+
     PAIR_METRICS = {"cosine": 0, "l2": 1}
 
     def pair_scores(self, a, b, idx_a, idx_b, metric="cosine", bad_count=None):

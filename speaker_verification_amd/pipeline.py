@@ -114,7 +114,7 @@ def speaker_segments(speaker_ids):
 class VerificationPipeline:
     def __init__(self, model, use_vad=True, vad_threshold=c.VAD_ENERGY_THRESHOLD, normalize=c.NORMALIZE,
                  crop_seed=12345, micro_batch=1024, preemph_cof=None, crop_rng="reference", overlap_front=False,
-                 pcm_scale=1.0 / 32768.0, cubes_per_clip=1, pool="mean"):
+                 pcm_scale=1.0 / 32768.0, cubes_per_clip=1, pool="mean", backend=None):
         """model: a `model.C3D2` with one channel, or with three (static, delta, delta-delta features: utils.py:325-348,
         :382-397; every method then carries [n, 3, T, 40] feature rows and [n, 3, 20, 80, 40] cubes): its inference form is
         `model.fused_inference()`, seven libsvk kernels.  Any other channel count raises ValueError.
@@ -135,7 +135,10 @@ class VerificationPipeline:
         (pool="mean_l2"), svk_embedding_pool.  The clip's feature rows are read K times by the first block, never copied.
         `micro_batch` keeps counting cubes: a chunk holds `clips_per_chunk(micro_batch, K)` clips.  crop_rng="device" draws
         20 K starts per clip (the first 20 are the one-cube draw), "reference" calls randint(T - 80, size=20) K times per clip,
-        in clip order.  K = 1 (the default) is today's path: no pooling, the same kernels, the same results."""
+        in clip order.  K = 1 (the default) is today's path: no pooling, the same kernels, the same results.
+        backend: a fitted `backend.EmbeddingBackend`, or None.  With one, `score`, `search` and `score_trials` project both
+        sides (`project`: centre, LDA / WCCN / whitening, length norm -- svk_embedding_project) before they compare them; the
+        embed methods keep returning raw embeddings.  None (the default) changes no code path."""
         self.channels = int(getattr(model, "num_channels", 0))
         if self.channels not in (1, 3):
             raise ValueError("VerificationPipeline runs C3D2 models with 1 or 3 input channels, got num_channels = %r"
@@ -152,6 +155,7 @@ class VerificationPipeline:
         if self.cubes_per_clip < 1 or pool not in ("mean", "mean_l2"):
             raise ValueError("cubes_per_clip must be at least 1 and pool 'mean' or 'mean_l2', got %r, %r" % (cubes_per_clip, pool))
         self.pool = pool
+        self.backend = backend
         # model front end: lmfe(signal, 16000, 0.025, 0.01, 40, 1024)  (load_data.py:64-70, Q14)
         self.spec = spec_from_seconds(c.SAMPLE_RATE, c.FRAME_LEN, c.FRAME_STEP, c.NUM_FFT, c.NUM_COEF, c.NUM_COEF,
                                       _lib.OUT_LMFE, preemph=preemph_cof is not None,
@@ -739,7 +743,13 @@ class VerificationPipeline:
                 up.release(k)
         return emb
 
+    def project(self, emb):
+        """The rows as the scorers see them: through the back end, or unchanged without one."""
+        return emb if self.backend is None else self.backend.transform(emb, engine=self.eng)
+
     def score(self, test_emb, enroll_emb):
+        if self.backend is not None:
+            test_emb, enroll_emb = self.project(test_emb), self.project(enroll_emb)
         return self.eng.cosine_scores(test_emb, enroll_emb)
 
     SEARCH_UPLOAD_BYTES = 1 << 30       # a host gallery above this is uploaded and searched in chunks of about this size
@@ -749,10 +759,11 @@ class VerificationPipeline:
         never written) -> (scores float32 [n, k], indices int64 [n, k]) on the device, best first, -1 / -inf past the
         enrolled rows.  enroll_emb: a device tensor or a host array.  With chunk_rows, or for a host array above
         SEARCH_UPLOAD_BYTES, the gallery is uploaded and searched chunk by chunk into one set of lists (the accumulate flag):
-        the same bits as one call.  exclude_self: the two sides are the same rows and row q is no candidate for query q."""
+        the same bits as one call.  exclude_self: the two sides are the same rows and row q is no candidate for query q.  With a
+        back end both sides are projected first, a chunked gallery chunk by chunk (a row's projection depends on that row alone)."""
         eng = self.eng
         n_gallery, dim = int(enroll_emb.shape[0]), int(enroll_emb.shape[1])
-        query = eng.to_device(test_emb, torch.float32)
+        query = self.project(eng.to_device(test_emb, torch.float32))
         exclude = None
         if exclude_self:
             if int(query.shape[0]) != n_gallery:
@@ -762,13 +773,13 @@ class VerificationPipeline:
         if chunk_rows is None and on_host and 4 * n_gallery * dim > self.SEARCH_UPLOAD_BYTES:
             chunk_rows = max(1, self.SEARCH_UPLOAD_BYTES // (4 * dim))
         if chunk_rows is None or n_gallery == 0:
-            return eng.cosine_topk(query, enroll_emb, k, exclude=exclude)
+            return eng.cosine_topk(query, self.project(enroll_emb), k, exclude=exclude)
         chunk_rows = int(chunk_rows)
         if chunk_rows < 1:
             raise ValueError("chunk_rows must be at least 1")
         into = None
         for lo in range(0, n_gallery, chunk_rows):
-            out = eng.cosine_topk(query, enroll_emb[lo:lo + chunk_rows], k, exclude=exclude, index_base=lo, into=into)
+            out = eng.cosine_topk(query, self.project(enroll_emb[lo:lo + chunk_rows]), k, exclude=exclude, index_base=lo, into=into)
             into = out
         return into
 
@@ -777,6 +788,8 @@ class VerificationPipeline:
         `svk_pair_scores` -> float32 [n_trials] on the device: a VoxCeleb-style trial list instead of the whole matrix of
         `score`.  On several GPUs call it on the all-gathered embeddings (`distributed.all_gather_embeddings`); every rank
         then holds the whole list's scores (the trial list itself is not sharded)."""
+        if self.backend is not None:
+            emb_a, emb_b = self.project(emb_a), None if emb_b is None else self.project(emb_b)
         return self.eng.pair_scores(emb_a, emb_a if emb_b is None else emb_b, idx_a, idx_b, metric=metric)
 
 
