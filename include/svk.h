@@ -258,10 +258,25 @@ int svk_ingest_resample(svk_ctx* ctx, const int16_t* d_pcm, int32_t n_ch, int64_
 
 /* ---- scoring ---------------------------------------------------------------
  * evaluation.py:67-84: cosine of every test row against every enrolled row,
- * float32, out [n_test][n_enroll]  (f32 MFMA).  dim <= 4096.                 */
+ * float32, out [n_test][n_enroll]  (f32 MFMA).  dim <= 4096.
+ * Accuracy: f32 products and f32 accumulation in a K order fixed by dim; every score lies within 1e-5 of the float64
+ * cosine of the same float32 rows, on every kernel the call may pick (one wave per 16 test rows below 2^22 pairs or 64
+ * enrolled rows, the tiled kernel above, either register budget), with 16-byte or -- dim % 4 != 0, or a matrix that is only
+ * 4-byte aligned -- 4-byte loads (tests/test_scoring_float64.py; DESIGN.md 3.4 has the measured errors).  A zero norm
+ * divides by 1 (sklearn's normalize): a zero row scores exactly 0 against everything, never NaN.  A NaN or Inf in a row
+ * makes that row's scores NaN -- an infinite norm too: inf / inf and x * (1 / inf) with x = +-inf are NaN -- and stays
+ * there: every other score has the bits it has without it.  Within one shape the bits of a score depend on its two rows
+ * alone, not on their positions, and runs are bit-identical.
+ * 1 <= dim <= 4096: dim > 4096 is SVK_ERR_UNSUPPORTED, dim < 1 or a negative count SVK_ERR_BAD_ARG; n_test == 0 or
+ * n_enroll == 0 writes nothing, launches nothing and looks at no pointer.                                      */
 int svk_cosine_scores(svk_ctx* ctx, const float* d_test, const float* d_enroll, int32_t n_test,
                       int32_t n_enroll, int32_t dim, float* d_out);
-/* siamese.py:29-30: out[i] = || a[i] - b[i] ||_2 */
+/* siamese.py:29-30: out[i] = || a[i] - b[i] ||_2, one wave per row, f32.
+ * Accuracy: |out[i] - d| <= (dim / 2 + 3) 2^-24 d against the float64 distance d of the same float32 rows (one rounding in
+ * a - b, a sum of dim non-negative squares in any order, a square root); equal rows give exactly 0.
+ * dim == 0 is allowed: the rows are empty, out[i] = 0 for all n rows, and d_a, d_b are not looked at (they may be NULL, as
+ * the pointer of an empty matrix is); d_out must not be NULL.  n == 0 launches nothing.  Negative n or dim:
+ * SVK_ERR_BAD_ARG.                                                                                             */
 int svk_l2_dist(svk_ctx* ctx, const float* d_a, const float* d_b, int32_t n, int32_t dim, float* d_out);
 
 /* The mean over groups of embedding rows (csrc/pool.hip): the K cubes of a clip -> the clip's embedding, and the utterances of

@@ -466,7 +466,8 @@ int svk_l2_dist(svk_ctx* ctx, const float* d_a, const float* d_b, int32_t n, int
   if (!ctx) return SVK_ERR_BAD_ARG;
   SVK_REQUIRE(ctx, n >= 0 && dim >= 0, "negative shape");
   if (n == 0) return SVK_OK;
-  SVK_REQUIRE(ctx, d_a && d_b && d_out, "NULL buffer");
+  // dim == 0: the rows are empty (an empty matrix has no storage, its pointer may be NULL), every distance is 0
+  SVK_REQUIRE(ctx, d_out && (dim == 0 || (d_a && d_b)), "NULL buffer");
   const unsigned grid = (unsigned)std::max(1, std::min((n + 3) / 4, ctx->num_cu * 8));
   hipLaunchKernelGGL(l2_dist_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_a, d_b, n, dim, d_out);
   SVK_LAUNCH_CHECK(ctx);

@@ -4,7 +4,9 @@ drop-in Python surface, against the CPU oracle and the committed golden vectors.
 Tolerances (north-star): MFCC / log-mel allclose(rtol=1e-4, atol=1e-4) against the float64
 reference (the kernels compute in f32; element-wise RELATIVE error alone is not meaningful
 for cepstra that cross zero -- SURVEY.md section 7); cosine |d| <= 1e-5; VAD masks bit-exact;
-EER equal.
+EER equal.  The cosine tests here compare with the oracle's float32 product (the reference's own
+numbers and the goldens); the score matrix is held to float64, on every kernel and branch of
+svk_cosine_scores, in tests/test_scoring_float64.py (svk_l2_dist too).
 """
 import os
 
