@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_class_scatter, svk_class_scatter_workspace_bytes, svk_embedding_project (the embedding back end: class statistics in float64 and centre / project / length-normalise in one pass); earlier additions under the same number: + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
+#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): svk_c3d2_stage2 runs as one kernel and no longer touches d_act2, which may be NULL (same results, bit for bit); earlier under the same number: + svk_class_scatter, svk_class_scatter_workspace_bytes, svk_embedding_project (the embedding back end: class statistics in float64 and centre / project / length-normalise in one pass); earlier additions under the same number: + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
 
 typedef enum svk_status {
   SVK_OK = 0,
@@ -538,16 +538,20 @@ int svk_c3d2_stage1_c3_multi(svk_ctx* ctx, const float* d_feat, int32_t n_clips,
                              const float* d_slope2, int32_t flags, float* d_out, int32_t cubes_per_clip);
 
 /* The second block, model.py:119-124 + :151-158: conv2_1 (16 -> 32, kernel (3,1,4)) -> BN -> PReLU -> conv2_2
- * (32 -> 32, kernel (3,8,1), stride (1,2,1)) -> BN -> PReLU -> MaxPool3d((1,1,2)), two kernels on v_mfma_f32_16x16x32_f16
- * through two-piece products like svk_c3d2_stage1 (direct form; the input region of a work item is split into (h, l) halves
- * while it is staged into LDS, the weights of all taps sit in registers); epilogues carry bias, PReLU and the pool.
+ * (32 -> 32, kernel (3,8,1), stride (1,2,1)) -> BN -> PReLU -> MaxPool3d((1,1,2)), ONE kernel on v_mfma_f32_16x16x32_f16
+ * through two-piece products like svk_c3d2_stage1 (direct form; the weights of all taps sit in registers): conv2_1 is handed
+ * to conv2_2 depth pair by depth pair through LDS, already split into (h, l) halves, so its activation never reaches memory;
+ * epilogues carry bias, PReLU and the pool.
  *   d_in     [n_utt][16][36][18][16]  = svk_c3d2_stage1's output
  *   d_w21blk [2 nt][6 pairs][2][64][8 halves]: conv2_1, lane l = (co = 16 nt + (l & 15), kk = l >> 4), element e =
  *            W[co][ci = 8 (kk & 1) + e][kd][kw + (kk >= 2)] of the tap pair 2 kd + kw / 2 (kw = 0, 2); block 0 = H, 1 = L
  *   d_w22blk [2 nt][24 taps][2][64][8 halves]: conv2_2, element e = W[co][ci = 8 kk + e][kd][kh], tap = 8 kd + kh; H | L
  *   d_bias / d_slope [32] per layer (BN folded; PReLU slope per channel)
- *   d_act2   [n_utt][14][36][14][32]  conv2_1's activation (scratch, f32): 14 of the layer's 15 columns -- conv2_2 is one column
- *            wide and pool2 drops its 15th, so conv2_1's 15th is never read and (since 0.1.9) never computed;
+ *   d_act2   may be NULL: it is never read or written.  Only with SVK_C3D2_STAGE2_TWO_KERNELS in the environment (read at every
+ *            call: the two kernels this one replaced, kept as the reference its tests and A/B measurements run against, not as
+ *            a second path to ship on) is it conv2_1's activation [n_utt][14][36][14][32] (scratch, f32; 14 of the layer's
+ *            15 columns -- conv2_2 is one column wide and pool2 drops its 15th, so conv2_1's 15th is never computed), and NULL
+ *            is SVK_ERR_BAD_ARG;
  *   d_out    [n_utt][12][15][7][32] (channels last)
  * flags as for svk_c3d2_stage1. */
 int svk_c3d2_stage2(svk_ctx* ctx, const float* d_in, int32_t n_utt, const void* d_w21blk, const float* d_bias21,

@@ -892,6 +892,265 @@ __global__ __launch_bounds__(256, 2) void c3d2_conv22h_kernel(const ConvParams p
   }
 }
 
+// ---- The second block as ONE kernel: conv2_1 streamed into conv2_2 by depth through LDS.  conv2_1 is (3, 1, 4) -- no extent along
+// rows -- and conv2_2 (3, 8, 1) -- none along columns -- so one pooled output column j needs conv2_1's two columns 2 j, 2 j + 1 and
+// nothing else, and conv2_2's depth chain consumes them in the order a conv2_1 that walks depth too produces them: the activation
+// [14][36][14][32] (2.06 of the pair's 2.9 MB of HBM traffic per cube) only ever exists as two depth pairs in LDS.
+// Item = (cube, pooled column j), 7 per cube; one workgroup of eight waves per CU; a STEP is one depth pair of conv2_1's output:
+//   * waves 0 - 3 (producers; wave = (N tile, tiles 0 - 4 | 5 - 8)) compute the pair's 2 d x 36 rows x 2 columns = 144 positions = 9
+//     full tiles of conv2_1 from four input depths, PReLU, split into (h, l) and park them in the activation ring in conv2_2's
+//     plane order (pieces are made where a value is produced: conv2_2's re-split of staged scratch is gone).  They also fetch the
+//     input depth pair two steps ahead (columns 2 j .. 2 j + 4 of d_in, 23 KB) at the top of the step and split + park it behind
+//     their tiles; at an item's last step, the first two pairs of the next item;
+//   * waves 4 - 7 (consumers; wave = (N tile, plane tile), c3d2_conv22h_kernel's wave) multiply the pair of the step BEFORE into
+//     their depth chain: two accumulators are carried from step to step (outputs 2 t - 2 with 16 taps, 2 t - 1 with 8), two start.
+// One workgroup barrier per step, outside the role branches; 7 steps per item, the steps run on across items (the consumers drain
+// an item's last pair while the producers fill the next item's first).  Every output receives its blocks in the order of the two
+// kernels above, from the bias, with the same operands: bit-identical to them, per entry point.
+//   input ring    [4 planes: h c0-7, h c8-15, l c0-7, l c8-15][8 depth slots: depth & 7][36 rows][5 columns + 1]: pitch 6 makes the
+//                 16 slots of a tile (8 rows x 2 columns) distinct mod 16; 110 592 bytes
+//   activation    [8 planes: four channel quarters x {h, l}][2 pairs x 2 depths][row parity][18 x 2]; 36 864 bytes
+constexpr int S2S_IN_DSLOT = S2_H * 6;                    // 216 slots per input depth
+constexpr int S2S_IN_PLANE = 8 * S2S_IN_DSLOT;            // 1 728 slots
+constexpr int S2S_IN_WORDS = 4 * 4 * S2S_IN_PLANE;        // 27 648 words
+constexpr int S2S_ACT_DSLOT = 2 * S2_H;                   // 72 slots per activation depth
+constexpr int S2S_ACT_PLANE = 4 * S2S_ACT_DSLOT;          // 288 slots
+constexpr int S2S_ACT_WORDS = 4 * 8 * S2S_ACT_PLANE;      // 9 216 words
+constexpr int S2S_LDS_WORDS = S2S_IN_WORDS + S2S_ACT_WORDS;   // 147 456 bytes
+constexpr int S2S_STATIC_LDS = 272;                       // q_next (padded to 16) + bs22: the kernel's static LDS, beside the dynamic rings
+constexpr int S2S_PIECES = 2 * S2_H * 5 * 4;              // 1 440 sixteen-byte pieces of an input depth pair: [2 d][36 rows][5 w][4]
+static_assert(S2S_IN_PLANE % 16 == 0 && S2S_ACT_PLANE % 16 == 0, "the lanes of an LDS lane group sit in different planes");
+
+struct Stage2Params {
+  const float* in;      // [n][16][36][18][16]
+  const u32x4* w21;     // conv2_1's blocks, as c3d2_conv21h_kernel takes them
+  const float *bias21, *slope21;
+  const u32x4* w22;     // conv2_2's blocks, as c3d2_conv22h_kernel takes them
+  const float *bias22, *slope22;
+  float* out;           // [n][12][15][7][32]
+  int32_t n_utt;
+  unsigned* queue;
+};
+
+// piece e = tp + 256 m of producer thread tp: channels 4 (e & 3) .. + 3 of pixel (d = D0 + q / 36, row q % 36, column (e % 20) / 4), q = e / 20
+__device__ __forceinline__ void s2s_fetch(const float* col0, int D0, int tp, f32x4 (&sv)[6]) {
+#pragma unroll
+  for (int m = 0; m < 6; ++m) {
+    // (threads past the last piece load it again and park nothing: a load under a condition of its own made the compiler wait
+    // for every load of the pair right behind their issue)
+    const int e = min(tp + 256 * m, S2S_PIECES - 1), q = (e * 3277) >> 16, r = e - 20 * q;   // e / 20 for e < 1 536
+    sv[m] = *reinterpret_cast<const f32x4*>(col0 + (D0 * S2_H + q) * (S2_W * 16) + 4 * r);
+  }
+}
+__device__ __forceinline__ void s2s_park(unsigned* in_lds, int D0, int tp, const f32x4 (&sv)[6]) {
+#pragma unroll
+  for (int m = 0; m < 6; ++m) {
+    const int e = tp + 256 * m, q = (e * 3277) >> 16, r = e - 20 * q;
+    const int dd = q >= S2_H ? 1 : 0, row = q - S2_H * dd, col = r >> 2, piece = r & 3;
+    const int slot = ((D0 + dd) & 7) * S2S_IN_DSLOT + row * 6 + col;
+    park_pieces(in_lds + 4 * ((piece >> 1) * S2S_IN_PLANE + slot) + 2 * (piece & 1), 4 * 2 * S2S_IN_PLANE, sv[m], e < S2S_PIECES);
+  }
+}
+
+// conv2_1's output depths 2 t, 2 t + 1 of the item's two columns: tiles t0 .. t0 + nt_tiles - 1 of N tile nt -> activation depth slots
+// act_d0, act_d0 + 1.  Position P = 16 tile + i -> (dd = P / 72, row = (P % 72) / 2, column P % 2)
+template <bool SLOPE01>
+__device__ __forceinline__ void s2s_conv21_step(const unsigned* in_lds, unsigned* act_lds, int t, int act_d0, int nt, int t0, int nt_tiles,
+                                                int lane, const u32x4 (&W)[6][2], f32x4 b4, f32x4 sl4) {
+  const int i = lane & 15, kk = lane >> 4;
+  // (fragments fetched across tiles -- pairs 4 and 5 of a tile reading pairs 0 and 1 of the next -- measured 3 - 4 % SLOWER)
+#pragma unroll 1
+  for (int tile = t0; tile < t0 + nt_tiles; ++tile) {
+    const int P = 16 * tile + i, dd = P >= 2 * S2_H ? 1 : 0, rem = P - 2 * S2_H * dd, row = rem >> 1, col = rem & 1;
+    // input pixel (2 t + dd + kd, row, col + kw): depth slot (2 t + dd + kd) & 7 of plane (kk & 1) [l: + 2]; tap b = + 1 slot
+    const char* const a0 = reinterpret_cast<const char*>(in_lds) + 16 * ((kk & 1) * S2S_IN_PLANE + row * 6 + col + (kk >= 2 ? 1 : 0));
+    const char* a2[3];
+#pragma unroll
+    for (int kd = 0; kd < 3; ++kd) a2[kd] = a0 + 16 * S2S_IN_DSLOT * ((2 * t + dd + kd) & 7);
+    auto rd = [&](int pr, int piece) -> u32x4 {
+      return *reinterpret_cast<const u32x4*>(a2[pr >> 1] + 16 * 2 * (pr & 1) + 16 * 2 * S2S_IN_PLANE * piece);
+    };
+    f32x4 acc = b4;
+    u32x4 bh[3], bl[3];
+    bh[0] = rd(0, 0);
+    bl[0] = rd(0, 1);
+    bh[1] = rd(1, 0);
+    bl[1] = rd(1, 1);
+#pragma unroll
+    for (int pr = 0; pr < 6; ++pr) {
+      if (pr + 2 < 6) {
+        bh[(pr + 2) % 3] = rd(pr + 2, 0);
+        bl[(pr + 2) % 3] = rd(pr + 2, 1);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      acc = mfma_pieces(W[pr][0], W[pr][1], bh[pr % 3], bl[pr % 3], acc);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // channels 16 nt + 4 kk .. + 3 of the position: plane 2 nt + kk / 2 [l: + 4], bytes 8 (kk & 1) .. + 7 of its slot
+    const int slot = (act_d0 + dd) * S2S_ACT_DSLOT + (row & 1) * S2_H + (row >> 1) * 2 + col;
+    park_pieces(act_lds + 4 * ((2 * nt + (kk >> 1)) * S2S_ACT_PLANE + slot) + 2 * (kk & 1), 4 * 4 * S2S_ACT_PLANE, prelu4<SLOPE01>(acc, sl4), true);
+  }
+}
+
+// conv2_2's chain over the activation depths s = 2 tc, 2 tc + 1 at a2 (the lane's slot of depth 2 tc, h plane): accumulators P (output
+// 2 tc - 2, taps 0 - 15 done) and Q (2 tc - 1, taps 0 - 7 done) come in and go out one pair on.  KIND 0: tc = 0 (no outputs - 2, - 1),
+// 2: tc = 6 (no outputs 12, 13), 1: the rest.  `o2` = the lane's output address at depth 2 tc; bs[0], bs[4] = the lane's bias and slope in
+// LDS, read where they are used: beside the 192 weight registers, eight more held across the steps were sixteen spilled
+template <bool SLOPE01, int KIND>
+__device__ __forceinline__ void s2s_conv22_step(const char* a2, const u32x4 (&W)[24][2], const f32x4* bs, f32x4& P, f32x4& Q, float* o2,
+                                                bool store) {
+  auto rd = [&](int n, int piece) -> u32x4 {
+    const int dd = n >> 3, kh = n & 7;
+    return *reinterpret_cast<const u32x4*>(a2 + 16 * (dd * S2S_ACT_DSLOT + (kh & 1) * S2_H + (kh >> 1) * 2) + 16 * 4 * S2S_ACT_PLANE * piece);
+  };
+  constexpr int OD_STRIDE = O2_H * O2_W * 32;
+  f32x4 A = P, B = Q, C = bs[0], D = C, sl4;
+  u32x4 bh[3], bl[3];   // fragments two units ahead (three rotating sets), as in c3d2_conv22h_kernel
+  bh[0] = rd(0, 0);
+  bl[0] = rd(0, 1);
+  bh[1] = rd(1, 0);
+  bl[1] = rd(1, 1);
+#pragma unroll
+  for (int n = 0; n < 16; ++n) {
+    if (n + 2 < 16) {
+      bh[(n + 2) % 3] = rd(n + 2, 0);
+      bl[(n + 2) % 3] = rd(n + 2, 1);
+    }
+    if (KIND != 2 && n == 6) D = bs[0];
+    if (KIND != 0 && n == 5) sl4 = bs[4];
+    __builtin_amdgcn_sched_barrier(0);
+    const int dd = n >> 3, kh = n & 7;
+    if (dd == 0) {
+      if (KIND != 2) C = mfma_pieces(W[kh][0], W[kh][1], bh[n % 3], bl[n % 3], C);
+      if (KIND != 0) B = mfma_pieces(W[8 + kh][0], W[8 + kh][1], bh[n % 3], bl[n % 3], B);
+      if (KIND != 0) A = mfma_pieces(W[16 + kh][0], W[16 + kh][1], bh[n % 3], bl[n % 3], A);
+      if (KIND != 0 && kh == 7) prelu_pool_store<SLOPE01>(A, sl4, o2 - 2 * OD_STRIDE, store);
+    } else {
+      if (KIND != 2) D = mfma_pieces(W[kh][0], W[kh][1], bh[n % 3], bl[n % 3], D);
+      if (KIND != 2) C = mfma_pieces(W[8 + kh][0], W[8 + kh][1], bh[n % 3], bl[n % 3], C);
+      if (KIND != 0) B = mfma_pieces(W[16 + kh][0], W[16 + kh][1], bh[n % 3], bl[n % 3], B);
+      if (KIND != 0 && kh == 7) prelu_pool_store<SLOPE01>(B, sl4, o2 - OD_STRIDE, store);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  P = C;
+  Q = D;
+}
+
+// COMPILER-DEPENDENT (ROCm 7.2's hipcc), this barrier and the two __builtin_amdgcn_s_waitcnt(0x0F70) below: they buy about 10 % of the
+// kernel through where the compiler places its waits, not through anything the hardware needs.  After a compiler upgrade rerun
+// -Rpass-analysis=kernel-resource-usage (256 VGPRs, no spill, no scratch in both instances), look for `s_waitcnt vmcnt` between the
+// producers' global_load_dwordx4 and their first v_mfma in the assembly (there must be none), and time
+// `tools/time_network.py 16384 stage2` against SVK_C3D2_STAGE2_TWO_KERNELS=1 (9.20 against 10.21 ms when this was written).
+// The step barrier: the LDS traffic of the wave is waited for, its global traffic is not -- __syncthreads() waits for vmcnt(0) as well,
+// which here is the consumers' output stores of the step just ended (nothing in the kernel reads them) once per step.
+__device__ __forceinline__ void s2s_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// One role's walk over the workgroup's items and steps.  The two roles run the SAME skeleton -- the items in the same order from
+// q_next, seven steps per item, one barrier per step and one drain step -- as two instances, so every wave executes the same number
+// of barriers; one loop with the roles as branches inside it kept conv2_2's 192 weight registers live on the producers' path as well
+// (200 registers spilled).
+template <bool SLOPE01, bool PRODUCER>
+__device__ __forceinline__ void s2s_run(const Stage2Params& p, unsigned* in_lds, unsigned* act_lds, int* q_next, f32x4* bs22, int lane, int wave) {
+  const int i = lane & 15, kk = lane >> 4;
+  const int nt = wave & 1, half = (wave >> 1) & 1;
+  constexpr int NW = PRODUCER ? 6 : 24;
+  u32x4 W[NW][2];
+  load_wblk(PRODUCER ? p.w21 : p.w22, nt * NW, lane, W);
+  const f32x4* const bs = bs22 + 8 * nt + kk;   // the consumers' bias and slope: [2 nt][bias | slope][4 kk] in LDS
+  f32x4 b4, sl4;   // channels 16 nt + 4 kk .. + 3 of ONE position, of the role's layer
+  {
+    f32x4 b, sl;
+    load_bias_slope(PRODUCER ? p.bias21 : p.bias22, PRODUCER ? p.slope21 : p.slope22, nt, kk, b, sl);
+    if constexpr (PRODUCER) {
+      b4 = b;
+      sl4 = sl;
+    } else if (i == 0) {   // (both waves of an N tile write the same values)
+      bs22[8 * nt + kk] = b;
+      bs22[8 * nt + 4 + kk] = sl;
+    }
+  }
+  const int n_items = p.n_utt * O2_W;
+  auto col0_of = [&](int it) -> const float* {
+    const int u = it / O2_W, j = it - u * O2_W;
+    return p.in + (int64_t)u * (S2_D * S2_H * S2_W * 16) + 2 * j * 16;
+  };
+  int item = blockIdx.x, prev = n_items, nxt = n_items;   // the producers' item, the one before it, the one after it
+  const int tp = threadIdx.x & 255;
+  if (PRODUCER) {   // the first item's first two input depth pairs
+    f32x4 sa[6], sb[6];
+    s2s_fetch(col0_of(item), 0, tp, sa);
+    s2s_fetch(col0_of(item), 2, tp, sb);
+    s2s_park(in_lds, 0, tp, sa);
+    s2s_park(in_lds, 2, tp, sb);
+  }
+  __syncthreads();
+  // every load of the prologue has landed, and the compiler is told so (vmcnt(0) as an instruction it tracks): it keeps no count of
+  // loads across the loop's back edge, and with the weights' loads still open in its books it drained the step's input fetch in front
+  // of the step's first MFMA
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+  const int r30 = min(16 * half + i, 2 * O2_H - 1), lane_out = (r30 >> 1) * (O2_W * 32) + 16 * nt + 4 * kk;
+  const bool store = (i & 1) == 0 && 16 * half + i < 2 * O2_H;
+  f32x4 accP = {0.f, 0.f, 0.f, 0.f}, accQ = accP;   // (the consumers' first step is of KIND 0: it reads neither)
+  unsigned q_ticket = 0;
+  int gp = 0;   // the activation pair slot the producers fill in this step; the consumers read the other one
+  for (;;) {
+#pragma unroll 1
+    for (int t = 0; t < 7; ++t) {
+      const bool live = item < n_items;
+      if constexpr (PRODUCER) {
+        // (nothing is in flight at a step's top -- every fetch was parked -- but the compiler's books carry the previous step's loads
+        // across the back edge and it waits for them again in the middle of this step's fetch: vmcnt(0) here, a no-op, clears them)
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        // (the ticket is drawn a step before it is needed: its round trip hides behind that step's tiles)
+        if (t == 4 && threadIdx.x == 0 && p.queue) q_ticket = atomicAdd(p.queue, 1u);
+        if (live) {
+          // input depth pair t + 2 of the item; at its last step pairs 0 and 1 of the next item (their depth slots 0 .. 3 were last read
+          // in step 5)
+          const int fitem = t < 6 ? item : nxt, fD = t < 6 ? 2 * t + 4 : 0;
+          const bool fa = fitem < n_items, fb = fa && t == 6;
+          f32x4 sa[6], sb[6];
+          if (fa) s2s_fetch(col0_of(fitem), fD, tp, sa);
+          if (fb) s2s_fetch(col0_of(fitem), 2, tp, sb);
+          s2s_conv21_step<SLOPE01>(in_lds, act_lds, t, 2 * gp, nt, half ? 5 : 0, half ? 4 : 5, lane, W, b4, sl4);
+          if (fa) s2s_park(in_lds, fD, tp, sa);
+          if (fb) s2s_park(in_lds, 2, tp, sb);
+        }
+        if (t == 5 && threadIdx.x == 0) *q_next = p.queue ? (int)q_ticket + (int)gridDim.x : item + (int)gridDim.x;
+      } else {
+        const int ci = t == 0 ? prev : item, tc = t == 0 ? 6 : t - 1;   // the pair of the step before
+        if (ci < n_items) {
+          const int u = ci / O2_W, j = ci - u * O2_W;
+          const char* const a2 = reinterpret_cast<const char*>(act_lds) + 16 * (kk * S2S_ACT_PLANE + 2 * (gp ^ 1) * S2S_ACT_DSLOT + r30);
+          float* const o2 = p.out + (((int64_t)u * O2_D + 2 * tc) * (O2_H * O2_W) + j) * 32 + lane_out;   // (a scalar base + one register)
+          if (tc == 0) s2s_conv22_step<SLOPE01, 0>(a2, W, bs, accP, accQ, o2, store);
+          else if (tc == 6) s2s_conv22_step<SLOPE01, 2>(a2, W, bs, accP, accQ, o2, store);
+          else s2s_conv22_step<SLOPE01, 1>(a2, W, bs, accP, accQ, o2, store);
+        }
+      }
+      s2s_barrier();
+      gp ^= 1;
+      if (t == 0 && !live) return;   // the last item's last pair is consumed
+      if (t == 5) nxt = __builtin_amdgcn_readfirstlane(*q_next);
+    }
+    prev = item;
+    item = nxt;
+  }
+}
+
+template <bool SLOPE01>
+__global__ __launch_bounds__(512) void c3d2_stage2h_kernel(const Stage2Params p) {
+  extern __shared__ __attribute__((aligned(16))) float smem_s2s[];
+  unsigned* const in_lds = reinterpret_cast<unsigned*>(smem_s2s);
+  unsigned* const act_lds = in_lds + S2S_IN_WORDS;
+  __shared__ int q_next;
+  __shared__ f32x4 bs22[16];
+  static_assert(sizeof(bs22) + 16 == S2S_STATIC_LDS, "S2S_STATIC_LDS states this kernel's static LDS");
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (wave < 4) s2s_run<SLOPE01, true>(p, in_lds, act_lds, &q_next, bs22, lane, wave);
+  else s2s_run<SLOPE01, false>(p, in_lds, act_lds, &q_next, bs22, lane, wave);
+}
+
 // ---- conv3_1 (32 -> 64, kernel (3,1,3)) + BN + PReLU (model.py:126-128, :159-161) through two-piece f16 products: direct
 // form, K = 32 = the 32 input channels of ONE tap, three MFMAs per tap, 9 taps.  No taps along h, so item = (cube, block of 3
 // rows): region 12 depths x 3 rows x 7 columns of 32 channels, split into (h, l) while staged: eight planes (four channel quarters
@@ -1268,10 +1527,32 @@ extern "C" int svk_c3d2_stage2(svk_ctx* ctx, const float* d_in, int32_t n_utt, c
   bool launch;
   const uintptr_t addr_bits = reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_act2) | reinterpret_cast<uintptr_t>(d_w21blk) |
                               reinterpret_cast<uintptr_t>(d_w22blk) | reinterpret_cast<uintptr_t>(d_out);
-  if (int rc = conv_checks(ctx, n_utt, flags, d_in && d_w21blk && d_bias21 && d_slope21 && d_w22blk && d_bias22 && d_slope22 && d_act2 && d_out,
+  // SVK_C3D2_STAGE2_TWO_KERNELS (read at every call) selects c3d2_conv21h_kernel + c3d2_conv22h_kernel through d_act2: the reference
+  // the streamed kernel is tested and measured against, not a second shipped path.  The streamed kernel never touches d_act2.
+  const bool two_kernels = getenv("SVK_C3D2_STAGE2_TWO_KERNELS") != nullptr;
+  if (int rc = conv_checks(ctx, n_utt, flags,
+                           d_in && d_w21blk && d_bias21 && d_slope21 && d_w22blk && d_bias22 && d_slope22 && (d_act2 || !two_kernels) && d_out,
                            addr_bits, 21, 0, &launch))
     return rc;
   if (!launch) return SVK_OK;
+  if (!two_kernels) {
+    using Stage2Kernel = void (*)(const Stage2Params);
+    const Stage2Kernel kern = (flags & 2) ? c3d2_stage2h_kernel<true> : c3d2_stage2h_kernel<false>;
+    Stage2Params p{d_in, reinterpret_cast<const u32x4*>(d_w21blk), d_bias21, d_slope21, reinterpret_cast<const u32x4*>(d_w22blk), d_bias22,
+                   d_slope22, d_out, n_utt, nullptr};
+    if (int rc = svk_work_queue(ctx, SVK_SLOT_STAGE2, 1, &p.queue)) return rc;
+    // (svk_persistent_grid allows 64 bytes of static LDS beside the dynamic region; this kernel has S2S_STATIC_LDS: checked here)
+    static_assert(sizeof(unsigned) * (size_t)S2S_LDS_WORDS + S2S_STATIC_LDS <= 160 * 1024, "one workgroup must fit a CU's LDS");
+    if (sizeof(unsigned) * (size_t)S2S_LDS_WORDS + S2S_STATIC_LDS > (size_t)ctx->lds_per_cu)
+      return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "svk_c3d2_stage2 needs %zu bytes of LDS per workgroup (device: %d)",
+                      sizeof(unsigned) * (size_t)S2S_LDS_WORDS + S2S_STATIC_LDS, ctx->lds_per_cu);
+    unsigned grid;
+    if (int rc = svk_persistent_grid(ctx, "svk_c3d2_stage2", kern, sizeof(unsigned) * (size_t)S2S_LDS_WORDS, 512, 1, (int64_t)n_utt * O2_W, &grid))
+      return rc;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), sizeof(unsigned) * (size_t)S2S_LDS_WORDS, ctx->stream, p);
+    SVK_LAUNCH_CHECK(ctx);
+    return SVK_OK;
+  }
   // conv2_1 and conv2_2 share a CU between workgroups: as many as the occupancy calculator allows
   unsigned* queues;
   if (int rc = svk_work_queue(ctx, SVK_SLOT_STAGE2, 2, &queues)) return rc;

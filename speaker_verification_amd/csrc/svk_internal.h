@@ -28,7 +28,7 @@ struct svk_ctx {
 // one as long as they run on the handle's stream (svk_c3d2_stage1 and svk_c3d2_stage1_c3 do).
 constexpr size_t SVK_SCRATCH_BYTES = 256;
 constexpr size_t SVK_SLOT_LOG_POWER = 0;       // svk_log_power: the running maximum (1 word)
-constexpr size_t SVK_SLOT_STAGE2 = 64;         // svk_c3d2_stage2: the work-item counters of conv2_1, conv2_2 (2 words)
+constexpr size_t SVK_SLOT_STAGE2 = 64;         // svk_c3d2_stage2: its work-item counter (1 word; 2 on the two-kernel reference path)
 constexpr size_t SVK_SLOT_CONV31 = 80;         // svk_c3d2_conv31 (1 word)
 constexpr size_t SVK_SLOT_CONV32 = 96;         // svk_c3d2_conv32t (1 word)
 constexpr size_t SVK_SLOT_CONV41 = 100;        // svk_c3d2_conv41 (1 word)

@@ -9,6 +9,7 @@ reference's NumPy return types.
 """
 import ctypes as C
 import math
+import os
 
 import numpy as np
 
@@ -578,15 +579,15 @@ class Engine:
         args.append(2 if len(tables) > k and tables[k] else 0)      # bit 1: every slope in [0, 1], the two-instruction PReLU
         return args
 
-    def _c3d2_block(self, fn, act, tables, out_shape, w_shapes, co, w_dtype=None, scratch_shape=None):
+    def _c3d2_block(self, fn, act, tables, out_shape, w_shapes, co, w_dtype=None, scratch_shape=None, scratch_used=True):
         """fn(ctx, act, n, (weight blocks, bias, slope) per layer, flags[, scratch], out) -> out [n, *out_shape] f32
         (weight blocks of f16 unless `w_dtype`)."""
         torch = _torch()
         n = act.shape[0]
         args = self._c3d2_layers(tables, w_shapes, w_dtype or torch.float16, co)
         if scratch_shape is not None:      # held until the launch is enqueued: `out` must not reuse its memory
-            scratch = torch.empty((n,) + scratch_shape, dtype=torch.float32, device=self.device)
-            args.append(self._ptr(scratch))
+            scratch = torch.empty((n,) + scratch_shape, dtype=torch.float32, device=self.device) if scratch_used else None
+            args.append(self._ptr(scratch) if scratch_used else None)       # (None: a NULL scratch the entry point never touches)
         out = torch.empty((n,) + out_shape, dtype=torch.float32, device=self.device)
         self._stream()
         check(fn(self.ctx, self._ptr(act), n, *args, self._ptr(out)), self.ctx)
@@ -597,9 +598,10 @@ class Engine:
         BN + PReLU -> [n, 12, 15, 7, 32] f32 (channels last), both convolutions through two-piece f16 products."""
         if tuple(act1.shape[1:]) != (16, 36, 18, 16) or not act1.is_contiguous():
             raise ValueError("c3d2_stage2 wants the activation [n, 16, 36, 18, 16]")
-        # scratch: the 14 columns of conv2_1 that pool2 leaves alive
+        # conv2_1's activation stays in LDS; only the two-kernel reference path (SVK_C3D2_STAGE2_TWO_KERNELS, read by the library at
+        # every call) goes through the scratch: the 14 columns of conv2_1 that pool2 leaves alive, 903 KB per cube
         return self._c3d2_block(self.lib.svk_c3d2_stage2, act1, tables, (12, 15, 7, 32), ((2, 6, 2, 64, 8), (2, 24, 2, 64, 8)), 32,
-                                scratch_shape=(14, 36, 14, 32))
+                                scratch_shape=(14, 36, 14, 32), scratch_used="SVK_C3D2_STAGE2_TWO_KERNELS" in os.environ)
 
     def c3d2_conv31(self, act, tables):
         """svk_c3d2_conv31: [n, 12, 15, 7, 32] (svk_c3d2_stage2's output) -> conv3_1 + BN + PReLU -> chunked, column-major
