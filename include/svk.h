@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): svk_c3d2_stage2 runs as one kernel and no longer touches d_act2, which may be NULL (same results, bit for bit); earlier under the same number: + svk_class_scatter, svk_class_scatter_workspace_bytes, svk_embedding_project (the embedding back end: class statistics in float64 and centre / project / length-normalise in one pass); earlier additions under the same number: + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
+#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_plda_scores, svk_plda_scores_workspace_bytes, svk_plda_pair_scores (PLDA log-likelihood ratios: the score matrix on the f32 matrix pipe, trial lists in float64); earlier under the same number: svk_c3d2_stage2 runs as one kernel and no longer touches d_act2, which may be NULL (same results, bit for bit); earlier under the same number: + svk_class_scatter, svk_class_scatter_workspace_bytes, svk_embedding_project (the embedding back end: class statistics in float64 and centre / project / length-normalise in one pass); earlier additions under the same number: + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
 
 typedef enum svk_status {
   SVK_OK = 0,
@@ -369,6 +369,63 @@ int svk_embedding_project(svk_ctx* ctx, const float* d_emb, int64_t n_rows, int3
 int svk_pair_scores(svk_ctx* ctx, const float* d_a, int64_t n_a, const float* d_b, int64_t n_b, int32_t dim,
                     const int64_t* d_idx_a, const int64_t* d_idx_b, int64_t n_pairs, int32_t metric, float* d_out,
                     int32_t* d_bad_count);
+
+/* ---- PLDA scoring (csrc/plda.hip) ------------------------------------------------------------
+ * Log-likelihood ratios under the two-covariance PLDA model in the basis that diagonalises both covariances (plda.py fits it
+ * from svk_class_scatter's statistics): a projected utterance is u = y + e with y ~ N(0, diag psi) for the speaker and
+ * e ~ N(0, I) for the session.  An enrolled model is the mean u of n >= 1 projected utterances, a test utterance is v:
+ *   llr(u, n, v) = sum_k [ alpha_k(n) u_k v_k - 1/2 beta_k(n) v_k^2 - 1/2 gamma_k(n) u_k^2 ] + c(n)
+ *   alpha_k(n) = n psi_k / d1,  beta_k(n) = n psi_k^2 / (d1 d3),  gamma_k(n) = n^2 psi_k^2 / (d1 d2)
+ *   d1 = (n + 1) psi_k + 1,  d2 = n psi_k + 1,  d3 = psi_k + 1
+ *   c(n) = -1/2 sum_k log(d1 / (d2 d3)), each logarithm formed as log1p(-n psi_k^2 / (d2 d3))
+ * A direction with psi_k = 0 contributes exactly 0.  d_psi: float64 [dim], finite and >= 0 (the caller's duty: anything else
+ * gives NaN or nonsense in the scores, never a fault).  Both entries take PROJECTED rows [.][dim] f32, 1 <= dim <= 512 (the
+ * back end's limit), and are asynchronous on the context's stream.
+ *
+ * svk_plda_scores: d_out[i][j] = llr(d_enroll[j], n_j, d_test[i]), f32 [n_test][n_enroll]; n_j = d_enroll_count[j] (int32), or 1
+ * for every j when d_enroll_count is NULL.  A float64 pre-pass, then ONE product kernel on v_mfma_f32_16x16x4_f32:
+ *   pre-pass      enrolled row j:  b_jk = f32(alpha_k(n_j) u_jk),  t_j = -1/2 sum_k gamma_k(n_j) u_jk^2 + c(n_j) kept as float64
+ *                 counts NULL:   test row i:  s_i = -1/2 sum_k beta_k(1) v_ik^2 kept as float64;  a_ik = v_ik;  K = dim
+ *                 counts given:  a_i,dim+k = f32(v_ik^2),  b_j,dim+k = f32(-1/2 beta_k(n_j)),  s_i = 0;  K = 2 dim
+ *                 (float64 products, divisions and sums; lane l of a wave adds the columns l, l + 64, ... in order, then a butterfly)
+ *   product       dot_ij = sum_k a_ik b_jk: f32 products, f32 accumulation, the order of k fixed by dim and the form (128-column
+ *                 blocks in order, the second half after the first; inside a block super-steps of 16, inside one the
+ *                 k = 16 S + 4 g + e in the order (e, g)).  The enrolled operand is staged through LDS 32 rows at a time; the
+ *                 split is over output rows and columns, never over K
+ *   epilogue      d_out[i][j] = f32(((double) dot_ij + s_i) + t_j), rounded once
+ *   accuracy      with a, b the float64 values of the operands before their rounding and ref the float64 score,
+ *                 |d_out - ref| <= (K + 4) 2^-24 sum_k |a_k b_k| + 2^-24 |ref|  (tests/test_plda_scores.py derives it)
+ * Within a form (counts NULL / given) the bits of a score depend on its two rows, psi, the row's count and dim alone -- not on
+ * n_test, n_enroll, the rows' positions or the launch geometry; runs are bit-identical.  The same bits with 16-byte loads
+ * (dim % 4 == 0 and a 16-byte aligned d_test) and 4-byte loads.  A NaN or Inf in a test row stays in that row of d_out, one in
+ * an enrolled row in that column; a count < 1 makes its column NaN.
+ *   d_workspace   svk_plda_scores_workspace_bytes(n_test, n_enroll, dim, with_counts) bytes, 16-byte aligned (t, s, the enrolled
+ *                 operand and, with counts, both second halves); with_counts: non-zero when d_enroll_count is given.  0 for
+ *                 arguments the call rejects and for n_test == 0 or n_enroll == 0, which need none
+ * n_test == 0 or n_enroll == 0 writes nothing, launches nothing and looks at no pointer.  SVK_ERR_BAD_ARG: NULL context or
+ * buffer, negative size, dim outside [1, 512], misalignment (f32 / int32: 4 bytes; float64: 8; workspace: 16), a short workspace. */
+size_t svk_plda_scores_workspace_bytes(int32_t n_test, int32_t n_enroll, int32_t dim, int32_t with_counts);
+int svk_plda_scores(svk_ctx* ctx, const float* d_test, int32_t n_test, const float* d_enroll, int32_t n_enroll, int32_t dim,
+                    const double* d_psi, const int32_t* d_enroll_count, void* d_workspace, size_t workspace_bytes,
+                    float* d_out);
+
+/* One LLR per TRIAL of a list, as svk_pair_scores gives one cosine:  d_out[p] = llr(d_b[d_idx_b[p]], n, d_a[d_idx_a[p]]) with
+ * n = d_count_b[d_idx_b[p]] (int32 [n_b]), or 1 when d_count_b is NULL.  d_a is the TEST side, d_b the ENROLLED side; d_a == d_b
+ * is allowed.
+ *   d_a, d_b      [n_a][dim], [n_b][dim] f32 projected rows, 4-byte aligned.  16-byte loads when dim % 4 == 0 and both are
+ *                 16-byte aligned, 4-byte loads otherwise: the same bits either way
+ *   d_idx_a/_b    int64 [n_pairs].  An index outside its matrix is the caller's error: the rows are not read, that trial's score
+ *                 is NaN and *d_bad_count (int32, may be NULL, the caller zeroes it) goes up by one.  A count < 1 gives NaN too
+ *                 (and is not counted)
+ * Every coefficient, product, division, logarithm and sum is float64 and the result is rounded to float32 once:
+ * |d_out - ref| <= 2^-24 |ref| + (dim + 8) 2^-52 sum |terms| against a float64 evaluation of the formula above, the terms being
+ * its 6 dim summands (tests/test_plda_pair_scores.py).  The order of additions of a trial depends on dim alone (a team of 16
+ * lanes per trial, each lane its columns in order, then a butterfly), not on n_pairs, the launch geometry or the neighbouring
+ * trials: a trial scored alone gives the bits it gives inside a list.  n_pairs == 0 launches nothing.  SVK_ERR_BAD_ARG: NULL
+ * context or buffer, negative size, dim outside [1, 512], misalignment. */
+int svk_plda_pair_scores(svk_ctx* ctx, const float* d_a, int64_t n_a, const float* d_b, int64_t n_b, int32_t dim,
+                         const double* d_psi, const int32_t* d_count_b, const int64_t* d_idx_a, const int64_t* d_idx_b,
+                         int64_t n_pairs, float* d_out, int32_t* d_bad_count);
 
 /* Speaker SEARCH: the k best rows of a gallery for every query row by cosine score, without the [n_query][n_gallery] matrix
  * that svk_cosine_scores writes and svk_top1 / a framework's top-k reads back (148 642 x 1 211: 720 MB each way; a corpus

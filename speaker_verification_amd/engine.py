@@ -915,6 +915,65 @@ class Engine:
                                        self._ptr(bad_count)), self.ctx)
         return out
 
+    def _plda_operands(self, psi, counts, dim, n_enroll):
+        """psi as float64 [dim] and the counts as int32 [n_enroll] (or None) on the device, shapes checked (not the values:
+        `plda.Plda` validates those on the host)."""
+        torch = _torch()
+        p = self.to_device(psi, torch.float64).reshape(-1)
+        if p.numel() != dim:
+            raise ValueError("psi holds one entry per column of the projected rows (%d), got %d" % (dim, p.numel()))
+        cnt = None
+        if counts is not None:
+            cnt = self.to_device(counts, torch.int32).reshape(-1)
+            if cnt.numel() != n_enroll:
+                raise ValueError("counts holds one entry per enrolled row (%d), got %d" % (n_enroll, cnt.numel()))
+        return p, cnt
+
+    def plda_scores(self, test, enroll, psi, counts=None):
+        """svk_plda_scores: the PLDA log-likelihood ratio of every PROJECTED test row [Nt, D] against every enrolled model
+        [Ns, D] (the mean of counts[j] >= 1 projected utterances; None: 1 each) -> float32 [Nt, Ns] on the device.  psi:
+        float64 [D], the between-speaker variances (`plda.Plda`).  A float64 pre-pass and one f32 MFMA product; the workspace
+        is a torch allocation sized by the library."""
+        torch = _torch()
+        t = self.to_device(test, torch.float32)
+        e = self.to_device(enroll, torch.float32)
+        if t.dim() != 2 or e.dim() != 2 or t.shape[1] != e.shape[1]:
+            raise ValueError("plda_scores wants (Nt, D) and (Ns, D)")
+        nt, ns, dim = int(t.shape[0]), int(e.shape[0]), int(t.shape[1])
+        p, cnt = self._plda_operands(psi, counts, dim, ns)
+        work = torch.empty((max(16, int(self.lib.svk_plda_scores_workspace_bytes(nt, ns, dim, int(cnt is not None)))),),
+                           dtype=torch.uint8, device=self.device)
+        out = torch.empty((nt, ns), dtype=torch.float32, device=self.device)
+        self._stream()
+        check(self.lib.svk_plda_scores(self.ctx, self._ptr(t), nt, self._ptr(e), ns, dim, self._ptr(p), self._ptr(cnt),
+                                       self._ptr(work), work.numel(), self._ptr(out)), self.ctx)
+        return out
+
+    def plda_pair_scores(self, a, b, idx_a, idx_b, psi, counts_b=None, bad_count=None):
+        """svk_plda_pair_scores: out[p] = the PLDA log-likelihood ratio of the test row a[idx_a[p]] against the enrolled model
+        b[idx_b[p]] (of counts_b[idx_b[p]] utterances; None: 1) -> float32 [n_pairs] on the device, float64 arithmetic.  b may
+        be a itself.  An index outside its matrix gives NaN at that trial and counts in bad_count (an int32 [1] device tensor
+        the caller zeroes), if given."""
+        torch = _torch()
+        x = self.to_device(a, torch.float32)
+        y = x if b is a else self.to_device(b, torch.float32)
+        if x.dim() != 2 or y.dim() != 2 or x.shape[1] != y.shape[1]:
+            raise ValueError("plda_pair_scores wants (Na, D) and (Nb, D)")
+        ia = self.to_device(idx_a, torch.int64).reshape(-1)
+        ib = self.to_device(idx_b, torch.int64).reshape(-1)
+        if ia.numel() != ib.numel():
+            raise ValueError("idx_a and idx_b differ in length")
+        if bad_count is not None and not (isinstance(bad_count, torch.Tensor) and bad_count.is_cuda
+                                          and bad_count.dtype == torch.int32 and bad_count.numel() >= 1):
+            raise ValueError("bad_count must be an int32 device tensor")
+        p, cnt = self._plda_operands(psi, counts_b, int(x.shape[1]), int(y.shape[0]))
+        out = torch.empty((ia.numel(),), dtype=torch.float32, device=self.device)
+        self._stream()
+        check(self.lib.svk_plda_pair_scores(self.ctx, self._ptr(x), x.shape[0], self._ptr(y), y.shape[0], x.shape[1],
+                                            self._ptr(p), self._ptr(cnt), self._ptr(ia), self._ptr(ib), ia.numel(),
+                                            self._ptr(out), self._ptr(bad_count)), self.ctx)
+        return out
+
     def cosine_topk(self, query, gallery, k, exclude=None, index_base=0, into=None):
         """svk_cosine_topk: the k best gallery rows of every query row by cosine score, without the score matrix ->
         (scores float32 [n, k], indices int64 [n, k]) on the device, best first; an index is index_base + the gallery row,

@@ -157,19 +157,27 @@ def make_trials(speaker_ids, n_target, n_nontarget, seed):
 
 
 def evaluate_trials(embeddings, labels, idx_a, idx_b, metric="cosine", operating_points=DEFAULT_OPERATING_POINTS, device=True,
-                    backend=None):
+                    backend=None, plda=None):
     """Verification over a trial list: trial p compares embeddings[idx_a[p]] with embeddings[idx_b[p]] (`svk_pair_scores`,
     metric "cosine" or "l2"), labels[p] = 1 for the same speaker.  Returns a dict: eer, auc, eer_threshold, and per operating
     point (p_target, c_miss, c_fa) the lists min_dcf, threshold, p_miss, p_fa; scores = the float32 trial scores on the device.
     device=True: one `svk_roc_dcf` call; device=False: the same device scores, metrics on the host (`get_eer_auc`,
     `get_min_dcf`; eer_threshold by the same rule, the first point of the curve where 1 - fpr - tpr <= 0).  An index outside
-    the embeddings raises ValueError.  backend: a fitted `backend.EmbeddingBackend`; the embeddings go through it first."""
+    the embeddings raises ValueError.  backend: a fitted `backend.EmbeddingBackend`; the embeddings go through it first.
+    plda: a fitted `plda.Plda` (fitted behind the back end, if any): the rows are projected and the scores are PLDA
+    log-likelihood ratios (`svk_plda_pair_scores`, idx_a the test side); metric must then be left at its default."""
     eng = get_engine()
     bad = torch.zeros((1,), dtype=torch.int32, device=eng.device)
     emb = eng.to_device(embeddings, torch.float32)
     if backend is not None:
         emb = backend.transform(emb, engine=eng)
-    scores = eng.pair_scores(emb, emb, idx_a, idx_b, metric=metric, bad_count=bad)
+    if plda is not None:
+        if metric != "cosine":
+            raise ValueError("PLDA scores are log-likelihood ratios: metric does not apply")
+        emb = plda.project(emb, engine=eng)
+        scores = plda.score_trials(emb, idx_a, idx_b, bad_count=bad, engine=eng)
+    else:
+        scores = eng.pair_scores(emb, emb, idx_a, idx_b, metric=metric, bad_count=bad)
     if int(bad.item()):
         raise ValueError("evaluate_trials: %d trials index outside the %d embeddings" % (int(bad.item()), emb.shape[0]))
     labels = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1)

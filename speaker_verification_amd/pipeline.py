@@ -114,7 +114,7 @@ def speaker_segments(speaker_ids):
 class VerificationPipeline:
     def __init__(self, model, use_vad=True, vad_threshold=c.VAD_ENERGY_THRESHOLD, normalize=c.NORMALIZE,
                  crop_seed=12345, micro_batch=1024, preemph_cof=None, crop_rng="reference", overlap_front=False,
-                 pcm_scale=1.0 / 32768.0, cubes_per_clip=1, pool="mean", backend=None):
+                 pcm_scale=1.0 / 32768.0, cubes_per_clip=1, pool="mean", backend=None, plda=None):
         """model: a `model.C3D2` with one channel, or with three (static, delta, delta-delta features: utils.py:325-348,
         :382-397; every method then carries [n, 3, T, 40] feature rows and [n, 3, 20, 80, 40] cubes): its inference form is
         `model.fused_inference()`, seven libsvk kernels.  Any other channel count raises ValueError.
@@ -138,7 +138,11 @@ class VerificationPipeline:
         in clip order.  K = 1 (the default) is today's path: no pooling, the same kernels, the same results.
         backend: a fitted `backend.EmbeddingBackend`, or None.  With one, `score`, `search` and `score_trials` project both
         sides (`project`: centre, LDA / WCCN / whitening, length norm -- svk_embedding_project) before they compare them; the
-        embed methods keep returning raw embeddings.  None (the default) changes no code path."""
+        embed methods keep returning raw embeddings.  None (the default) changes no code path.
+        plda: a fitted `plda.Plda` (fitted on what the back end returns, if there is one), or None.  With one, `project` applies
+        the back end and then the PLDA projection, and `score` / `score_trials` return PLDA log-likelihood ratios
+        (svk_plda_scores / svk_plda_pair_scores) instead of cosines; `search` raises ValueError (top-k by LLR is not built).
+        None (the default) changes no code path."""
         self.channels = int(getattr(model, "num_channels", 0))
         if self.channels not in (1, 3):
             raise ValueError("VerificationPipeline runs C3D2 models with 1 or 3 input channels, got num_channels = %r"
@@ -156,6 +160,7 @@ class VerificationPipeline:
             raise ValueError("cubes_per_clip must be at least 1 and pool 'mean' or 'mean_l2', got %r, %r" % (cubes_per_clip, pool))
         self.pool = pool
         self.backend = backend
+        self.plda = plda
         # model front end: lmfe(signal, 16000, 0.025, 0.01, 40, 1024)  (load_data.py:64-70, Q14)
         self.spec = spec_from_seconds(c.SAMPLE_RATE, c.FRAME_LEN, c.FRAME_STEP, c.NUM_FFT, c.NUM_COEF, c.NUM_COEF,
                                       _lib.OUT_LMFE, preemph=preemph_cof is not None,
@@ -744,10 +749,20 @@ class VerificationPipeline:
         return emb
 
     def project(self, emb):
-        """The rows as the scorers see them: through the back end, or unchanged without one."""
-        return emb if self.backend is None else self.backend.transform(emb, engine=self.eng)
+        """The rows as the scorers see them: through the back end and the PLDA projection, or unchanged without either."""
+        if self.backend is not None:
+            emb = self.backend.transform(emb, engine=self.eng)
+        return emb if self.plda is None else self.plda.project(emb, engine=self.eng)
 
-    def score(self, test_emb, enroll_emb):
+    def score(self, test_emb, enroll_emb, counts=None):
+        """Every test row against every enrolled row: cosines, or with `plda` log-likelihood ratios.  counts (PLDA only): the
+        utterances behind each enrolled row when those are mean models (`enroll_mean(..., l2=False)` with a model fitted
+        with l2_in=False, whose projection is the mean of the projections; otherwise build the models with `Plda.enroll` and
+        score them with `Plda.score`)."""
+        if self.plda is not None:
+            return self.plda.score(self.project(test_emb), self.project(enroll_emb), counts=counts, engine=self.eng)
+        if counts is not None:
+            raise ValueError("counts belong to PLDA scoring: the cosine does not use them")
         if self.backend is not None:
             test_emb, enroll_emb = self.project(test_emb), self.project(enroll_emb)
         return self.eng.cosine_scores(test_emb, enroll_emb)
@@ -761,6 +776,8 @@ class VerificationPipeline:
         SEARCH_UPLOAD_BYTES, the gallery is uploaded and searched chunk by chunk into one set of lists (the accumulate flag):
         the same bits as one call.  exclude_self: the two sides are the same rows and row q is no candidate for query q.  With a
         back end both sides are projected first, a chunked gallery chunk by chunk (a row's projection depends on that row alone)."""
+        if self.plda is not None:
+            raise ValueError("search ranks by cosine score: top-k by PLDA log-likelihood ratio is not built (use score)")
         eng = self.eng
         n_gallery, dim = int(enroll_emb.shape[0]), int(enroll_emb.shape[1])
         query = self.project(eng.to_device(test_emb, torch.float32))
@@ -787,7 +804,13 @@ class VerificationPipeline:
         """One score per trial (emb_a[idx_a[p]] against emb_b[idx_b[p]], emb_b = emb_a when not given) through
         `svk_pair_scores` -> float32 [n_trials] on the device: a VoxCeleb-style trial list instead of the whole matrix of
         `score`.  On several GPUs call it on the all-gathered embeddings (`distributed.all_gather_embeddings`); every rank
-        then holds the whole list's scores (the trial list itself is not sharded)."""
+        then holds the whole list's scores (the trial list itself is not sharded).  With `plda`: log-likelihood ratios through
+        `svk_plda_pair_scores`, emb_a the test side and emb_b the enrolled side (one utterance each); `metric` must be left alone."""
+        if self.plda is not None:
+            if metric != "cosine":
+                raise ValueError("PLDA scores are log-likelihood ratios: metric does not apply")
+            u_a = self.project(emb_a)
+            return self.plda.score_trials(u_a, idx_a, idx_b, u_b=None if emb_b is None else self.project(emb_b), engine=self.eng)
         if self.backend is not None:
             emb_a, emb_b = self.project(emb_a), None if emb_b is None else self.project(emb_b)
         return self.eng.pair_scores(emb_a, emb_a if emb_b is None else emb_b, idx_a, idx_b, metric=metric)
