@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_plda_scores, svk_plda_scores_workspace_bytes, svk_plda_pair_scores (PLDA log-likelihood ratios: the score matrix on the f32 matrix pipe, trial lists in float64); earlier under the same number: svk_c3d2_stage2 runs as one kernel and no longer touches d_act2, which may be NULL (same results, bit for bit); earlier under the same number: + svk_class_scatter, svk_class_scatter_workspace_bytes, svk_embedding_project (the embedding back end: class statistics in float64 and centre / project / length-normalise in one pass); earlier additions under the same number: + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
+#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_calibration_stats, svk_calibration_stats_workspace_bytes, svk_calibration_apply (score calibration and fusion: the statistics of a prior-weighted logistic regression in one pass, and the affine map); earlier under the same number: + svk_plda_scores, svk_plda_scores_workspace_bytes, svk_plda_pair_scores (PLDA log-likelihood ratios: the score matrix on the f32 matrix pipe, trial lists in float64); earlier under the same number: svk_c3d2_stage2 runs as one kernel and no longer touches d_act2, which may be NULL (same results, bit for bit); earlier under the same number: + svk_class_scatter, svk_class_scatter_workspace_bytes, svk_embedding_project (the embedding back end: class statistics in float64 and centre / project / length-normalise in one pass); earlier additions under the same number: + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
 
 typedef enum svk_status {
   SVK_OK = 0,
@@ -519,6 +519,62 @@ int svk_decision_counts(svk_ctx* ctx, const float* d_scores, const uint8_t* d_la
  * rows of d_true (all zeros for -1).  *h_correct (HOST) = rows with argmax == d_true.  Synchronises the stream. */
 int svk_top1(svk_ctx* ctx, const float* d_scores, int64_t n_rows, int32_t n_cols, const int32_t* d_true,
              int32_t* d_argmax, uint8_t* d_labels, int64_t* h_correct);
+
+/* ---- score calibration and fusion (csrc/calibration.hip) ---------------------------------------
+ * An affine map from the scores of n_sys systems to a calibrated log-likelihood ratio, llr = sum_d w_d s_d + b, fitted by
+ * prior-weighted logistic regression on a development trial list (calibration.py runs the Newton iteration on the host; the
+ * reference has no calibration).  svk_calibration_stats is the one pass over the trials an iteration needs, svk_calibration_apply
+ * the map itself.  Both take the scores as planes: system d's score of trial p is d_scores[d * plane_stride + p], f32,
+ * 0 <= d < n_sys, 0 <= p < n, with 1 <= n_sys <= 8, plane_stride >= n, d_scores 4-byte aligned.  16-byte loads when d_scores is
+ * 16-byte aligned and (n_sys == 1 or plane_stride % 4 == 0) (and, for the statistics, d_labels is 4-byte aligned; for apply,
+ * d_out 16-byte aligned), 4-byte loads otherwise: the same bits either way.  h_weights (HOST) float64 [n_sys + 1], the offset b
+ * last; all finite.  Element indices and addresses are 64-bit; n may exceed 2^32 (not tested at that size).
+ *
+ * svk_calibration_stats: objective, gradient and Hessian of the regression at h_weights.  d_labels: uint8, non-zero = target.
+ * With x_p = (s_0p, .., s_(n_sys-1)p, 1), c_p = h_class_weight[0] for a target and [1] for a non-target (HOST, float64, finite),
+ * all in float64:
+ *   z_p   = ((w_0 s_0p + w_1 s_1p) + ..) + b) + tau      each product and each sum rounded on its own, in that order
+ *   e     = exp(-|z|),  lp = log1p(e),  q = 1 / (1 + e)      one exp, one log1p, one division per trial
+ *   softplus(z) = max(z, 0) + lp;  sigma(z) = z >= 0 ? q : e q;  sigma(z) sigma(-z) = (e q) q
+ *   L_tar = sum over targets of softplus(-z_p),  L_non = sum over non-targets of softplus(z_p)        (unweighted, nats)
+ *   G     = sum_p c_p r_p x_p,  r_p = -sigma(-z_p) for a target, +sigma(z_p) for a non-target          (n_sys + 1 values)
+ *   H     = sum_p c_p sigma(z_p) sigma(-z_p) x_p x_p^T, the upper triangle packed row by row   ((n_sys + 1)(n_sys + 2) / 2)
+ * |z| of 745 and more gives e = 0 and the exact limits (softplus = max(z, 0), sigma = 0 or 1, H term 0), never NaN or Inf for
+ * finite z.  h_out (HOST) float64 [2 + (n_sys + 1) + (n_sys + 1)(n_sys + 2) / 2] = {L_tar, L_non, G.., H..}; h_count (HOST)
+ * int64 [3] = {targets, non-targets, skipped}.  A trial with a NaN or an infinite score in ANY system adds to no sum and to
+ * neither class: it is counted in h_count[2].  With c = (p / N_tar, (1 - p) / N_non) and tau = log(p / (1 - p)),
+ * c_0 L_tar + c_1 L_non is the prior-weighted objective and G, H its gradient and Hessian; with w = (1, 0), tau = 0,
+ * Cllr = (L_tar / N_tar + L_non / N_non) / (2 ln 2).
+ *   flags         bit 0 (1), value only: G and H are neither computed nor written (h_out holds 2 values), L_tar and L_non are
+ *                 those of the full call bit for bit.  Every other bit must be 0
+ *   order of additions   a function of n alone, the same for every output.  With Q = ceil(n / 4) quads of four consecutive
+ *                 trials, S = ceil(ceil(Q / 256) / 2048) and W = ceil(Q / (256 S)) workgroups: workgroup g owns the quads
+ *                 [256 S g, 256 S (g + 1)); thread t adds, from 0.0, the trials of its quads 256 S g + t + 256 k, k = 0, 1, ..,
+ *                 in index order (at most 4 S additions); a 64-lane xor butterfly (32, 16, .., 1: 6 additions); the 4 wave
+ *                 sums from 0.0 in wave order (4); then ONE workgroup adds the W rows: 16 groups of ceil(W / 16) consecutive
+ *                 rows, each from 0.0 in index order, then the 16 group sums from 0.0 in order.  No floating-point atomics, no
+ *                 workgroup waits on another: runs are bit-identical, on any device
+ *   accuracy      every output is within (A + 8) 2^-52 sum_p |term_p| of the exact sum of its terms at the z_p above, A = 4 S +
+ *                 6 + 4 + ceil(W / 16) + 16 the additions on the longest path and 8 covering exp, log1p, the division and the
+ *                 products (tests/test_calibration_stats.py)
+ *   d_workspace   svk_calibration_stats_workspace_bytes(n, n_sys) bytes, 16-byte aligned (the W rows of partial sums); 0 for
+ *                 arguments the call rejects and for n == 0
+ * n == 0 launches nothing, looks at no device pointer and returns zeros.  The call synchronises the stream (its results are
+ * host scalars).  SVK_ERR_BAD_ARG: NULL context or buffer, negative n, n_sys outside [1, 8], plane_stride < n, misalignment
+ * (scores: 4 bytes; workspace: 16), a non-finite weight, tau or class weight, undefined flag bits, a short workspace. */
+size_t svk_calibration_stats_workspace_bytes(int64_t n, int32_t n_sys);
+int svk_calibration_stats(svk_ctx* ctx, const float* d_scores, int32_t n_sys, int64_t plane_stride, const uint8_t* d_labels,
+                          int64_t n, const double* h_weights, double tau, const double* h_class_weight, int32_t flags,
+                          void* d_workspace, size_t workspace_bytes, double* h_out, int64_t* h_count);
+
+/* d_out[p] = f32(((w_0 (double) s_0p + w_1 (double) s_1p) + ..) + b): float64 products and sums, each rounded on its own, in
+ * the order d = 0, 1, .., then the offset; rounded to f32 once:  |d_out - ref| <= 2^-24 |ref| + (n_sys + 1) 2^-52 sum |terms|.
+ * d_out: f32 [n], 4-byte aligned; it may be d_scores itself when n_sys == 1 (in place).  A non-finite score gives what IEEE
+ * arithmetic gives; nothing is counted.  Asynchronous on the context's stream, no workspace; n == 0 launches nothing.
+ * SVK_ERR_BAD_ARG: NULL context or buffer, negative n, n_sys outside [1, 8], plane_stride < n, misalignment, a non-finite
+ * weight. */
+int svk_calibration_apply(svk_ctx* ctx, const float* d_scores, int32_t n_sys, int64_t plane_stride, int64_t n,
+                          const double* h_weights, float* d_out);
 
 /* ---- the first block of the embedding network ----------------------------------------------------
  * model.py:110-117 + :141-150 (C3D2): cube (utils.py:351-379) -> conv1_1 (1 -> 16, kernel (3,1,5)) -> BN -> PReLU

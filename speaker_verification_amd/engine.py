@@ -747,6 +747,83 @@ class Engine:
         flat = np.array(out[:2 * n_thr + 2], dtype=np.int64)
         return flat[:2 * n_thr].reshape(n_thr, 2), (int(flat[2 * n_thr]), int(flat[2 * n_thr + 1]))
 
+    def _score_planes(self, scores):
+        """Scores as the calibration entries read them -> (f32 tensor [n_sys, n] with unit stride along n, plane_stride).
+        scores: a tensor / array [n] or [n_sys, n], or a sequence of [n] tensors, stacked once (planes a multiple of four floats
+        apart: the 16-byte loads).  A device f32 view whose rows are plane_stride >= n apart is taken as it is (no copy)."""
+        torch = _torch()
+        if isinstance(scores, (list, tuple)):
+            rows = [self.to_device(s, torch.float32).reshape(-1) for s in scores]
+            if not rows or any(r.numel() != rows[0].numel() for r in rows):
+                raise ValueError("a sequence of systems wants one score per trial in each")
+            n = rows[0].numel()
+            scores = torch.empty((len(rows), (n + 3) // 4 * 4), dtype=torch.float32, device=self.device)[:, :n]
+            for d, r in enumerate(rows):
+                scores[d].copy_(r)
+        if not (isinstance(scores, torch.Tensor) and scores.device == self.device and scores.dtype == torch.float32
+                and scores.dim() == 2 and scores.stride(1) == 1 and scores.stride(0) >= scores.shape[1]):
+            scores = self.to_device(scores, torch.float32)
+            if scores.dim() == 1:
+                scores = scores.reshape(1, -1)
+        if scores.dim() != 2:
+            raise ValueError("calibration scores want [n] or [n_sys, n], got %s" % (tuple(scores.shape),))
+        n_sys, n = int(scores.shape[0]), int(scores.shape[1])
+        return scores, (int(scores.stride(0)) if n_sys > 1 else n)
+
+    def calibration_stats(self, scores, labels, weights, tau, class_weight, value_only=False):
+        """svk_calibration_stats: one pass over the trials -> (l_tar, l_non, grad, hess, counts) at `weights` (float64
+        [n_sys + 1], the offset last): the softplus sums of the two classes in nats (unweighted), the class-weighted gradient
+        float64 [n_sys + 1] and Hessian float64 [n_sys + 1, n_sys + 1] (symmetric, filled from the packed triangle) of
+        z = w . (s, 1) + tau, and counts = (targets, non-targets, skipped): a trial with a non-finite score is left out and
+        counted as skipped.  class_weight = (target, non-target).  value_only: grad and hess are None (not computed)."""
+        torch = _torch()
+        sc, stride = self._score_planes(scores)
+        n_sys, n = int(sc.shape[0]), int(sc.shape[1])
+        lb = self.to_device(labels).reshape(-1)
+        lb = (lb != 0).to(torch.uint8) if lb.dtype != torch.uint8 else lb
+        if lb.numel() != n:
+            raise ValueError("scores and labels differ in length")
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        cw = np.ascontiguousarray(np.asarray(class_weight, dtype=np.float64).reshape(-1))
+        if w.size != n_sys + 1 or cw.size != 2:
+            raise ValueError("calibration_stats wants n_sys + 1 = %d weights and 2 class weights" % (n_sys + 1))
+        dim = n_sys + 1
+        work = torch.empty((max(16, int(self.lib.svk_calibration_stats_workspace_bytes(n, n_sys))),), dtype=torch.uint8,
+                           device=self.device)
+        out = (C.c_double * (2 + dim + dim * (dim + 1) // 2))()
+        count = (C.c_int64 * 3)()
+        dp = C.POINTER(C.c_double)
+        self._stream()
+        check(self.lib.svk_calibration_stats(self.ctx, self._ptr(sc), n_sys, stride, self._ptr(lb), n, w.ctypes.data_as(dp),
+                                             float(tau), cw.ctypes.data_as(dp), 1 if value_only else 0, self._ptr(work),
+                                             work.numel(), out, count), self.ctx)
+        counts = (int(count[0]), int(count[1]), int(count[2]))
+        if value_only:
+            return float(out[0]), float(out[1]), None, None, counts
+        flat = np.array(out[:], dtype=np.float64)
+        hess = np.zeros((dim, dim), dtype=np.float64)
+        hess[np.triu_indices(dim)] = flat[2 + dim:]
+        hess = hess + np.triu(hess, 1).T
+        return float(flat[0]), float(flat[1]), flat[2:2 + dim].copy(), hess, counts
+
+    def calibration_apply(self, scores, weights, out=None):
+        """svk_calibration_apply: f32 [n] on the device, out[p] = f32(sum_d weights[d] * scores[d, p] + weights[n_sys]) in
+        float64.  out: the tensor to write; for one system it may be the scores themselves (in place)."""
+        torch = _torch()
+        sc, stride = self._score_planes(scores)
+        n_sys, n = int(sc.shape[0]), int(sc.shape[1])
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        if w.size != n_sys + 1:
+            raise ValueError("calibration_apply wants n_sys + 1 = %d weights, got %d" % (n_sys + 1, w.size))
+        if out is None:
+            out = torch.empty((n,), dtype=torch.float32, device=self.device)
+        elif not (out.device == self.device and out.dtype == torch.float32 and out.numel() == n and out.is_contiguous()):
+            raise ValueError("out wants a contiguous float32 device tensor of %d elements" % n)
+        self._stream()
+        check(self.lib.svk_calibration_apply(self.ctx, self._ptr(sc), n_sys, stride, n, w.ctypes.data_as(C.POINTER(C.c_double)),
+                                             self._ptr(out)), self.ctx)
+        return out.reshape(-1)
+
     def roc_k(self, scores, labels, k=1, curve=False):
         """svk_roc_k: per split of `split_step(n, k)` consecutive pairs (evaluation.py:11-33), (eer, auc), or with
         curve=True (eer, auc, fpr, tpr): sklearn's roc_curve(drop_intermediate=True) as float64 NumPy arrays, fps / fps[-1]

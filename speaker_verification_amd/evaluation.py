@@ -157,7 +157,7 @@ def make_trials(speaker_ids, n_target, n_nontarget, seed):
 
 
 def evaluate_trials(embeddings, labels, idx_a, idx_b, metric="cosine", operating_points=DEFAULT_OPERATING_POINTS, device=True,
-                    backend=None, plda=None):
+                    backend=None, plda=None, calibration=None):
     """Verification over a trial list: trial p compares embeddings[idx_a[p]] with embeddings[idx_b[p]] (`svk_pair_scores`,
     metric "cosine" or "l2"), labels[p] = 1 for the same speaker.  Returns a dict: eer, auc, eer_threshold, and per operating
     point (p_target, c_miss, c_fa) the lists min_dcf, threshold, p_miss, p_fa; scores = the float32 trial scores on the device.
@@ -165,7 +165,10 @@ def evaluate_trials(embeddings, labels, idx_a, idx_b, metric="cosine", operating
     `get_min_dcf`; eer_threshold by the same rule, the first point of the curve where 1 - fpr - tpr <= 0).  An index outside
     the embeddings raises ValueError.  backend: a fitted `backend.EmbeddingBackend`; the embeddings go through it first.
     plda: a fitted `plda.Plda` (fitted behind the back end, if any): the rows are projected and the scores are PLDA
-    log-likelihood ratios (`svk_plda_pair_scores`, idx_a the test side); metric must then be left at its default."""
+    log-likelihood ratios (`svk_plda_pair_scores`, idx_a the test side); metric must then be left at its default.
+    calibration: a fitted one-system `calibration.Calibration`: the trial scores go through it before the metrics (scores = the
+    calibrated LLRs) and the dict gains cllr and the list act_dcf, the cost of deciding at each operating point's Bayes
+    threshold (`svk_decision_counts`; min_dcf <= act_dcf, the gap is the calibration loss).  None (the default) changes nothing."""
     eng = get_engine()
     bad = torch.zeros((1,), dtype=torch.int32, device=eng.device)
     emb = eng.to_device(embeddings, torch.float32)
@@ -183,6 +186,10 @@ def evaluate_trials(embeddings, labels, idx_a, idx_b, metric="cosine", operating
     labels = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1)
     if labels.size != scores.numel():
         raise ValueError("one label per trial")
+    if calibration is not None:
+        if calibration.n_sys != 1:
+            raise ValueError("evaluate_trials scores one system: the calibration must be fitted on one, not %r" % (calibration.n_sys,))
+        scores = calibration.apply(scores, engine=eng, out=scores)
     ops = [tuple(float(v) for v in op) for op in operating_points]
     if device:
         res = eng.roc_dcf(scores, labels, ops)
@@ -197,6 +204,10 @@ def evaluate_trials(embeddings, labels, idx_a, idx_b, metric="cosine", operating
         out = {"eer": float(eer), "auc": float(auc), "eer_threshold": float(thr[at]),
                "min_dcf": [r[0] for r in rows], "threshold": [r[1] for r in rows], "p_miss": [r[2] for r in rows],
                "p_fa": [r[3] for r in rows]}
+    if calibration is not None:
+        from . import calibration as cal
+        out["cllr"] = cal.cllr(scores, labels, engine=eng)
+        out["act_dcf"] = cal.act_dcf(scores, labels, ops, engine=eng)[0]
     out["scores"] = scores
     return out
 

@@ -114,7 +114,8 @@ def speaker_segments(speaker_ids):
 class VerificationPipeline:
     def __init__(self, model, use_vad=True, vad_threshold=c.VAD_ENERGY_THRESHOLD, normalize=c.NORMALIZE,
                  crop_seed=12345, micro_batch=1024, preemph_cof=None, crop_rng="reference", overlap_front=False,
-                 pcm_scale=1.0 / 32768.0, cubes_per_clip=1, pool="mean", backend=None, plda=None):
+                 pcm_scale=1.0 / 32768.0, cubes_per_clip=1, pool="mean", backend=None, plda=None,
+                 calibration=None):
         """model: a `model.C3D2` with one channel, or with three (static, delta, delta-delta features: utils.py:325-348,
         :382-397; every method then carries [n, 3, T, 40] feature rows and [n, 3, 20, 80, 40] cubes): its inference form is
         `model.fused_inference()`, seven libsvk kernels.  Any other channel count raises ValueError.
@@ -142,7 +143,11 @@ class VerificationPipeline:
         plda: a fitted `plda.Plda` (fitted on what the back end returns, if there is one), or None.  With one, `project` applies
         the back end and then the PLDA projection, and `score` / `score_trials` return PLDA log-likelihood ratios
         (svk_plda_scores / svk_plda_pair_scores) instead of cosines; `search` raises ValueError (top-k by LLR is not built).
-        None (the default) changes no code path."""
+        None (the default) changes no code path.
+        calibration: a fitted one-system `calibration.Calibration` (fitted on the scores this pipeline produces: cosines, or
+        with `plda` its LLRs), or None.  With one, `score` and `score_trials` return calibrated log-likelihood ratios
+        (svk_calibration_apply, in place on the fresh scores) and `decide` thresholds them; `search` raises ValueError.  None
+        (the default) changes no code path."""
         self.channels = int(getattr(model, "num_channels", 0))
         if self.channels not in (1, 3):
             raise ValueError("VerificationPipeline runs C3D2 models with 1 or 3 input channels, got num_channels = %r"
@@ -161,6 +166,9 @@ class VerificationPipeline:
         self.pool = pool
         self.backend = backend
         self.plda = plda
+        if calibration is not None and calibration.n_sys != 1:
+            raise ValueError("the pipeline scores one system: its calibration must be fitted on one, not %r" % (calibration.n_sys,))
+        self.calibration = calibration
         # model front end: lmfe(signal, 16000, 0.025, 0.01, 40, 1024)  (load_data.py:64-70, Q14)
         self.spec = spec_from_seconds(c.SAMPLE_RATE, c.FRAME_LEN, c.FRAME_STEP, c.NUM_FFT, c.NUM_COEF, c.NUM_COEF,
                                       _lib.OUT_LMFE, preemph=preemph_cof is not None,
@@ -760,12 +768,26 @@ class VerificationPipeline:
         with l2_in=False, whose projection is the mean of the projections; otherwise build the models with `Plda.enroll` and
         score them with `Plda.score`)."""
         if self.plda is not None:
-            return self.plda.score(self.project(test_emb), self.project(enroll_emb), counts=counts, engine=self.eng)
+            return self._calibrated(self.plda.score(self.project(test_emb), self.project(enroll_emb), counts=counts,
+                                                    engine=self.eng))
         if counts is not None:
             raise ValueError("counts belong to PLDA scoring: the cosine does not use them")
         if self.backend is not None:
             test_emb, enroll_emb = self.project(test_emb), self.project(enroll_emb)
-        return self.eng.cosine_scores(test_emb, enroll_emb)
+        return self._calibrated(self.eng.cosine_scores(test_emb, enroll_emb))
+
+    def _calibrated(self, scores):
+        """Fresh scores of any shape -> the same tensor holding calibrated LLRs; untouched without a calibration."""
+        if self.calibration is None:
+            return scores
+        self.calibration.apply(scores.reshape(-1), engine=self.eng, out=scores.reshape(-1))
+        return scores
+
+    def decide(self, llr, p_target, c_miss=1, c_fa=1):
+        """Accept / reject calibrated LLRs at the Bayes threshold of an operating point -> a bool tensor, llr >=
+        log(c_fa (1 - p_target) / (c_miss p_target)) (the threshold as float32, the precision of the scores)."""
+        from .calibration import bayes_threshold
+        return self.eng.to_device(llr, torch.float32) >= float(np.float32(bayes_threshold(p_target, c_miss, c_fa)))
 
     SEARCH_UPLOAD_BYTES = 1 << 30       # a host gallery above this is uploaded and searched in chunks of about this size
 
@@ -778,6 +800,8 @@ class VerificationPipeline:
         back end both sides are projected first, a chunked gallery chunk by chunk (a row's projection depends on that row alone)."""
         if self.plda is not None:
             raise ValueError("search ranks by cosine score: top-k by PLDA log-likelihood ratio is not built (use score)")
+        if self.calibration is not None:
+            raise ValueError("search ranks by raw cosine score: calibrated top-k is not built (use score)")
         eng = self.eng
         n_gallery, dim = int(enroll_emb.shape[0]), int(enroll_emb.shape[1])
         query = self.project(eng.to_device(test_emb, torch.float32))
@@ -810,10 +834,11 @@ class VerificationPipeline:
             if metric != "cosine":
                 raise ValueError("PLDA scores are log-likelihood ratios: metric does not apply")
             u_a = self.project(emb_a)
-            return self.plda.score_trials(u_a, idx_a, idx_b, u_b=None if emb_b is None else self.project(emb_b), engine=self.eng)
+            return self._calibrated(self.plda.score_trials(u_a, idx_a, idx_b, u_b=None if emb_b is None else self.project(emb_b),
+                                                           engine=self.eng))
         if self.backend is not None:
             emb_a, emb_b = self.project(emb_a), None if emb_b is None else self.project(emb_b)
-        return self.eng.pair_scores(emb_a, emb_a if emb_b is None else emb_b, idx_a, idx_b, metric=metric)
+        return self._calibrated(self.eng.pair_scores(emb_a, emb_a if emb_b is None else emb_b, idx_a, idx_b, metric=metric))
 
 
 def enroll_last_utterance(embeddings, speaker_ids):
