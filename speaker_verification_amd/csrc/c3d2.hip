@@ -932,63 +932,127 @@ struct Stage2Params {
   unsigned* queue;
 };
 
-// piece e = tp + 256 m of producer thread tp: channels 4 (e & 3) .. + 3 of pixel (d = D0 + q / 36, row q % 36, column (e % 20) / 4), q = e / 20
-__device__ __forceinline__ void s2s_fetch(const float* col0, int D0, int tp, f32x4 (&sv)[6]) {
+// A producer lane's step-invariant addresses.  None depends on the data, the item or (but for a ring's depth-slot base, a wave-uniform
+// scalar) the step, so they are computed ONCE per kernel (s2s_lane_addr) and only scalars are added inside the step: decoded per
+// tile and per piece they were 25 of a tile's 37 vector instructions and 24 in front of a fetch's six loads, on the SIMD whose matrix
+// pipe the same waves feed.  Byte offsets; the compiler is kept from rematerialising the arithmetic where they are used
+// (s2s_lane_addr's empty asm statements).
+struct S2sLane {
+  // the wave's four REGULAR tiles 5 half + k, k = 0 .. 3: position 16 (5 half + k) + i = (dd = half, row = 4 half + 8 k + (i >> 1),
+  // col = i & 1).  in_reg, act_reg: tile k = 0 in the input ring (depth slot 0) and in the activation ring (depth slot half); tile
+  // k is S2S_TILE_IN / S2S_TILE_ACT bytes on
+  unsigned in_reg, act_reg;
+  // tile 4 (the waves of half 0 only): lanes i < 8 = (dd 0, rows 32 - 35), lanes i >= 8 = (dd 1, rows 0 - 3)
+  unsigned in_t4, act_t4;
+  // piece e = tp + 256 m of producer thread tp: channels 4 (e & 3) .. + 3 of pixel (dd = q / 36, row q % 36, column (e % 20) / 4),
+  // q = e / 20: its bytes from the depth pair's first float at column 2 j, and its h words from the pair's first depth slot
+  unsigned fetch[6], park[6];
+};
+constexpr int S2S_TILE_IN = 16 * 8 * 6, S2S_TILE_ACT = 16 * 8;   // eight rows on: 48 slots of the input ring, 8 of the activation ring
+// conv2_1 position (row, col), lane group kk: plane (kk & 1) [l: + 2] of the input ring; tap b = + 1 slot
+__device__ __forceinline__ unsigned s2s_in_off(int kk, int row, int col) {
+  return 16 * ((kk & 1) * S2S_IN_PLANE + row * 6 + col + (kk >= 2 ? 1 : 0));
+}
+// channels 16 nt + 4 kk .. + 3 of position (dd, row, col): plane 2 nt + kk / 2 [l: + 4], bytes 8 (kk & 1) .. + 7 of its slot
+__device__ __forceinline__ unsigned s2s_act_off(int nt, int kk, int dd, int row, int col) {
+  const int slot = dd * S2S_ACT_DSLOT + (row & 1) * S2_H + (row >> 1) * 2 + col;
+  return 4 * (4 * ((2 * nt + (kk >> 1)) * S2S_ACT_PLANE + slot) + 2 * (kk & 1));
+}
+__device__ __forceinline__ S2sLane s2s_lane_addr(int lane, int nt, int half, int tp) {
+  const int i = lane & 15, kk = lane >> 4, col = i & 1;
+  S2sLane A;
+  A.in_reg = s2s_in_off(kk, 4 * half + (i >> 1), col);
+  A.act_reg = s2s_act_off(nt, kk, half, 4 * half + (i >> 1), col);
+  A.in_t4 = s2s_in_off(kk, i < 8 ? 32 + (i >> 1) : (i - 8) >> 1, col);
+  A.act_t4 = s2s_act_off(nt, kk, i < 8 ? 0 : 1, i < 8 ? 32 + (i >> 1) : (i - 8) >> 1, col);
 #pragma unroll
   for (int m = 0; m < 6; ++m) {
     // (threads past the last piece load it again and park nothing: a load under a condition of its own made the compiler wait
     // for every load of the pair right behind their issue)
-    const int e = min(tp + 256 * m, S2S_PIECES - 1), q = (e * 3277) >> 16, r = e - 20 * q;   // e / 20 for e < 1 536
-    sv[m] = *reinterpret_cast<const f32x4*>(col0 + (D0 * S2_H + q) * (S2_W * 16) + 4 * r);
-  }
-}
-__device__ __forceinline__ void s2s_park(unsigned* in_lds, int D0, int tp, const f32x4 (&sv)[6]) {
-#pragma unroll
-  for (int m = 0; m < 6; ++m) {
+    const int ef = min(tp + 256 * m, S2S_PIECES - 1), qf = (ef * 3277) >> 16, rf = ef - 20 * qf;   // e / 20 for e < 1 536
+    A.fetch[m] = 4 * (qf * (S2_W * 16) + 4 * rf);
     const int e = tp + 256 * m, q = (e * 3277) >> 16, r = e - 20 * q;
-    const int dd = q >= S2_H ? 1 : 0, row = q - S2_H * dd, col = r >> 2, piece = r & 3;
-    const int slot = ((D0 + dd) & 7) * S2S_IN_DSLOT + row * 6 + col;
-    park_pieces(in_lds + 4 * ((piece >> 1) * S2S_IN_PLANE + slot) + 2 * (piece & 1), 4 * 2 * S2S_IN_PLANE, sv[m], e < S2S_PIECES);
+    const int dd = q >= S2_H ? 1 : 0, row = q - S2_H * dd, c = r >> 2, piece = r & 3;
+    A.park[m] = 4 * (4 * ((piece >> 1) * S2S_IN_PLANE + dd * S2S_IN_DSLOT + row * 6 + c) + 2 * (piece & 1));
   }
+  asm volatile("" : "+v"(A.in_reg), "+v"(A.act_reg), "+v"(A.in_t4), "+v"(A.act_t4));
+#pragma unroll
+  for (int m = 0; m < 6; ++m) asm volatile("" : "+v"(A.fetch[m]), "+v"(A.park[m]));
+  return A;
 }
 
-// conv2_1's output depths 2 t, 2 t + 1 of the item's two columns: tiles t0 .. t0 + nt_tiles - 1 of N tile nt -> activation depth slots
-// act_d0, act_d0 + 1.  Position P = 16 tile + i -> (dd = P / 72, row = (P % 72) / 2, column P % 2)
+// input depths D0, D0 + 1 of the item whose column 2 j starts at col0: one wave-uniform base + the lane's six offsets, as loads with a
+// scalar base and a 32-bit offset register.  (The offsets pass through an empty asm statement HERE, in place: the compiler otherwise
+// widens them to 64 bits once, outside the step loop, and adds the base to each pair with a 64-bit vector add per piece.)
+__device__ __forceinline__ void s2s_fetch(const float* col0, int D0, S2sLane& A, f32x4 (&sv)[6]) {
+  const char* const base = reinterpret_cast<const char*>(col0 + D0 * (S2_H * S2_W * 16));
+#pragma unroll
+  for (int m = 0; m < 6; ++m) {
+    asm volatile("" : "+v"(A.fetch[m]));
+    sv[m] = *reinterpret_cast<const f32x4*>(base + A.fetch[m]);
+  }
+}
+// (D0 is even: depth D0 + dd lies in depth slot (D0 & 7) + dd)
+__device__ __forceinline__ void s2s_park(unsigned* in_lds, int D0, int tp, const S2sLane& A, const f32x4 (&sv)[6]) {
+  char* const base = reinterpret_cast<char*>(in_lds + 4 * (D0 & 7) * S2S_IN_DSLOT);
+#pragma unroll
+  for (int m = 0; m < 6; ++m)
+    park_pieces(reinterpret_cast<unsigned*>(base + A.park[m]), 4 * 2 * S2S_IN_PLANE, sv[m], tp + 256 * m < S2S_PIECES);
+}
+
+// One tile of conv2_1: 16 positions; a2[kd] = the lane's fragment of input depth kd of the tile's three (h plane, tap a), dst = its
+// four channels' h words in the activation ring
 template <bool SLOPE01>
-__device__ __forceinline__ void s2s_conv21_step(const unsigned* in_lds, unsigned* act_lds, int t, int act_d0, int nt, int t0, int nt_tiles,
-                                                int lane, const u32x4 (&W)[6][2], f32x4 b4, f32x4 sl4) {
-  const int i = lane & 15, kk = lane >> 4;
+__device__ __forceinline__ void s2s_conv21_tile(const char* const (&a2)[3], unsigned* dst, const u32x4 (&W)[6][2], f32x4 b4, f32x4 sl4) {
   // (fragments fetched across tiles -- pairs 4 and 5 of a tile reading pairs 0 and 1 of the next -- measured 3 - 4 % SLOWER)
-#pragma unroll 1
-  for (int tile = t0; tile < t0 + nt_tiles; ++tile) {
-    const int P = 16 * tile + i, dd = P >= 2 * S2_H ? 1 : 0, rem = P - 2 * S2_H * dd, row = rem >> 1, col = rem & 1;
-    // input pixel (2 t + dd + kd, row, col + kw): depth slot (2 t + dd + kd) & 7 of plane (kk & 1) [l: + 2]; tap b = + 1 slot
-    const char* const a0 = reinterpret_cast<const char*>(in_lds) + 16 * ((kk & 1) * S2S_IN_PLANE + row * 6 + col + (kk >= 2 ? 1 : 0));
+  auto rd = [&](int pr, int piece) -> u32x4 {
+    return *reinterpret_cast<const u32x4*>(a2[pr >> 1] + 16 * 2 * (pr & 1) + 16 * 2 * S2S_IN_PLANE * piece);
+  };
+  f32x4 acc = b4;
+  u32x4 bh[3], bl[3];
+  bh[0] = rd(0, 0);
+  bl[0] = rd(0, 1);
+  bh[1] = rd(1, 0);
+  bl[1] = rd(1, 1);
+#pragma unroll
+  for (int pr = 0; pr < 6; ++pr) {
+    if (pr + 2 < 6) {
+      bh[(pr + 2) % 3] = rd(pr + 2, 0);
+      bl[(pr + 2) % 3] = rd(pr + 2, 1);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    acc = mfma_pieces(W[pr][0], W[pr][1], bh[pr % 3], bl[pr % 3], acc);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  park_pieces(dst, 4 * 4 * S2S_ACT_PLANE, prelu4<SLOPE01>(acc, sl4), true);
+}
+
+// conv2_1's output depths 2 t, 2 t + 1 of the item's two columns: the wave's tiles (half 0: tiles 0 - 4, half 1: tiles 5 - 8) of its N
+// tile -> activation depth slots act_d0, act_d0 + 1.  Position P = 16 tile + i -> (dd = P / 72, row = (P % 72) / 2, column P % 2); input
+// pixel (2 t + dd + kd, row, col + kw) is in depth slot (2 t + dd + kd) & 7.  The step adds wave-uniform scalars to the lane's
+// addresses of S2sLane: the depth-slot bases once per step, the tiles at compile-time offsets from them
+template <bool SLOPE01>
+__device__ __forceinline__ void s2s_conv21_step(const unsigned* in_lds, unsigned* act_lds, int t, int act_d0, int half, bool hi4, const S2sLane& A,
+                                                const u32x4 (&W)[6][2], f32x4 b4, f32x4 sl4) {
+  const char* const in_b = reinterpret_cast<const char*>(in_lds);
+  char* const act_b = reinterpret_cast<char*>(act_lds) + 16 * S2S_ACT_DSLOT * act_d0;
+  auto dslot = [&](int d) -> unsigned { return 16 * S2S_IN_DSLOT * ((2 * t + d) & 7); };
+  {
+    const char* a0[3];
+#pragma unroll
+    for (int kd = 0; kd < 3; ++kd) a0[kd] = in_b + (A.in_reg + dslot(half + kd));
+    char* const d0 = act_b + A.act_reg;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const char* const a2[3] = {a0[0] + S2S_TILE_IN * k, a0[1] + S2S_TILE_IN * k, a0[2] + S2S_TILE_IN * k};
+      s2s_conv21_tile<SLOPE01>(a2, reinterpret_cast<unsigned*>(d0 + S2S_TILE_ACT * k), W, b4, sl4);
+    }
+  }
+  if (half == 0) {   // tile 4: the depth of lanes i >= 8 (hi4) is one on
     const char* a2[3];
 #pragma unroll
-    for (int kd = 0; kd < 3; ++kd) a2[kd] = a0 + 16 * S2S_IN_DSLOT * ((2 * t + dd + kd) & 7);
-    auto rd = [&](int pr, int piece) -> u32x4 {
-      return *reinterpret_cast<const u32x4*>(a2[pr >> 1] + 16 * 2 * (pr & 1) + 16 * 2 * S2S_IN_PLANE * piece);
-    };
-    f32x4 acc = b4;
-    u32x4 bh[3], bl[3];
-    bh[0] = rd(0, 0);
-    bl[0] = rd(0, 1);
-    bh[1] = rd(1, 0);
-    bl[1] = rd(1, 1);
-#pragma unroll
-    for (int pr = 0; pr < 6; ++pr) {
-      if (pr + 2 < 6) {
-        bh[(pr + 2) % 3] = rd(pr + 2, 0);
-        bl[(pr + 2) % 3] = rd(pr + 2, 1);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      acc = mfma_pieces(W[pr][0], W[pr][1], bh[pr % 3], bl[pr % 3], acc);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // channels 16 nt + 4 kk .. + 3 of the position: plane 2 nt + kk / 2 [l: + 4], bytes 8 (kk & 1) .. + 7 of its slot
-    const int slot = (act_d0 + dd) * S2S_ACT_DSLOT + (row & 1) * S2_H + (row >> 1) * 2 + col;
-    park_pieces(act_lds + 4 * ((2 * nt + (kk >> 1)) * S2S_ACT_PLANE + slot) + 2 * (kk & 1), 4 * 4 * S2S_ACT_PLANE, prelu4<SLOPE01>(acc, sl4), true);
+    for (int kd = 0; kd < 3; ++kd) a2[kd] = in_b + (A.in_t4 + (hi4 ? dslot(kd + 1) : dslot(kd)));
+    s2s_conv21_tile<SLOPE01>(a2, reinterpret_cast<unsigned*>(act_b + A.act_t4), W, b4, sl4);
   }
 }
 
@@ -1077,12 +1141,14 @@ __device__ __forceinline__ void s2s_run(const Stage2Params& p, unsigned* in_lds,
   };
   int item = blockIdx.x, prev = n_items, nxt = n_items;   // the producers' item, the one before it, the one after it
   const int tp = threadIdx.x & 255;
-  if (PRODUCER) {   // the first item's first two input depth pairs
+  S2sLane A;
+  if constexpr (PRODUCER) {   // the first item's first two input depth pairs
+    A = s2s_lane_addr(lane, nt, half, tp);
     f32x4 sa[6], sb[6];
-    s2s_fetch(col0_of(item), 0, tp, sa);
-    s2s_fetch(col0_of(item), 2, tp, sb);
-    s2s_park(in_lds, 0, tp, sa);
-    s2s_park(in_lds, 2, tp, sb);
+    s2s_fetch(col0_of(item), 0, A, sa);
+    s2s_fetch(col0_of(item), 2, A, sb);
+    s2s_park(in_lds, 0, tp, A, sa);
+    s2s_park(in_lds, 2, tp, A, sb);
   }
   __syncthreads();
   // every load of the prologue has landed, and the compiler is told so (vmcnt(0) as an instruction it tracks): it keeps no count of
@@ -1110,11 +1176,11 @@ __device__ __forceinline__ void s2s_run(const Stage2Params& p, unsigned* in_lds,
           const int fitem = t < 6 ? item : nxt, fD = t < 6 ? 2 * t + 4 : 0;
           const bool fa = fitem < n_items, fb = fa && t == 6;
           f32x4 sa[6], sb[6];
-          if (fa) s2s_fetch(col0_of(fitem), fD, tp, sa);
-          if (fb) s2s_fetch(col0_of(fitem), 2, tp, sb);
-          s2s_conv21_step<SLOPE01>(in_lds, act_lds, t, 2 * gp, nt, half ? 5 : 0, half ? 4 : 5, lane, W, b4, sl4);
-          if (fa) s2s_park(in_lds, fD, tp, sa);
-          if (fb) s2s_park(in_lds, 2, tp, sb);
+          if (fa) s2s_fetch(col0_of(fitem), fD, A, sa);
+          if (fb) s2s_fetch(col0_of(fitem), 2, A, sb);
+          s2s_conv21_step<SLOPE01>(in_lds, act_lds, t, 2 * gp, half, i >= 8, A, W, b4, sl4);
+          if (fa) s2s_park(in_lds, fD, tp, A, sa);
+          if (fb) s2s_park(in_lds, 2, tp, A, sb);
         }
         if (t == 5 && threadIdx.x == 0) *q_next = p.queue ? (int)q_ticket + (int)gridDim.x : item + (int)gridDim.x;
       } else {
