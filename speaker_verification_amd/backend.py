@@ -77,6 +77,18 @@ def solve(class_mean, counts, sw, method, out_dim=None, shrinkage=0.0):
     return mean, np.ascontiguousarray(p @ u[:, ::-1][:, :out_dim])
 
 
+def class_statistics(embeddings, speaker_ids, l2_in, engine):
+    """(class_mean [n_class, dim], counts [n_class], sw [dim, dim]) of embeddings [n, dim] (device tensor or array) under
+    speaker_ids [n]: svk_class_scatter on the device (engine None: the current device's), as NumPy float64 (counts int64)."""
+    from .engine import get_engine
+    from .pipeline import speaker_segments
+    uniq, seg_start, row_index = speaker_segments(speaker_ids)
+    if int(row_index.size) != int(embeddings.shape[0]):
+        raise ValueError("fit wants one speaker id per embedding row")
+    class_mean, sw = (engine or get_engine()).class_scatter(embeddings, seg_start, row_index=row_index, l2_rows=l2_in)
+    return class_mean.cpu().numpy(), np.diff(seg_start), sw.cpu().numpy()
+
+
 class EmbeddingBackend:
     """A fitted back end.  `fit` on labelled development embeddings, `transform` anything scored afterwards (both sides of a
     trial); `VerificationPipeline(..., backend=b)` and `evaluation.evaluate_trials(..., backend=b)` do the latter themselves."""
@@ -101,13 +113,7 @@ class EmbeddingBackend:
         """Class statistics of embeddings [n, dim] (device tensor or array) under speaker_ids [n] on the device, then `solve`.
         l2_in: rows are L2-normalised before the statistics -- and in `transform`.  engine: the `Engine` (device) to run on,
         default the current device's.  Returns self."""
-        from .engine import get_engine
-        from .pipeline import speaker_segments
-        uniq, seg_start, row_index = speaker_segments(speaker_ids)
-        if int(row_index.size) != int(embeddings.shape[0]):
-            raise ValueError("fit wants one speaker id per embedding row")
-        class_mean, sw = (engine or get_engine()).class_scatter(embeddings, seg_start, row_index=row_index, l2_rows=l2_in)
-        mean, w = solve(class_mean.cpu().numpy(), np.diff(seg_start), sw.cpu().numpy(), method, out_dim=out_dim, shrinkage=shrinkage)
+        mean, w = solve(*class_statistics(embeddings, speaker_ids, l2_in, engine), method, out_dim=out_dim, shrinkage=shrinkage)
         self.mean, self.w, self.l2_in, self.method, self.shrinkage = mean, w, bool(l2_in), method, float(shrinkage)
         self._device = {}
         return self

@@ -4,12 +4,12 @@
 //       row / column terms; the product runs on v_mfma_f32_16x16x4_f32 (exact f32 products, f32 accumulation), one pass
 //       over the output.
 //   svk_plda_pair_scores  one LLR per trial of a list, float64 throughout, a team of 16 lanes per trial.
-// Nothing here is shared with the cosine kernels of scoring.hip / search.hip: those keep their bits.
+// The leaf helpers of score_common.h are shared with the cosine kernels of scoring.hip / search.hip; the tile loop of the
+// product and its K order are this kernel's own, as theirs are theirs: each keeps its bits.
 #include <algorithm>
 
+#include "score_common.h"
 #include "svk_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -29,16 +29,6 @@ __device__ __forceinline__ PldaCoef plda_coef(double psi, double n) {
   c.gamma = c.alpha * np / d2;
   c.half_log = 0.5 * log1p(-(np * psi) / (d2 * d3));
   return c;
-}
-
-__device__ __forceinline__ f32x4 plda_load4(const float* row, int col, int dim, bool row_ok, bool vec_ok) {
-  f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-  if (!row_ok) return v;
-  if (vec_ok && col + 4 <= dim) return *reinterpret_cast<const f32x4*>(row + col);
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    if (col + e < dim) v[e] = row[col + e];
-  return v;
 }
 
 // ---- pre-pass ----------------------------------------------------------------------------------------------------------
@@ -130,7 +120,7 @@ __global__ __launch_bounds__(256) void plda_product_kernel(const float* __restri
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int64_t r = (int64_t)cb * PT_BN + srow + 8 * j;
-      regs[j] = plda_load4(b + r * dim, kb * PT_KB + scol, dim, r < ne, vec_b);
+      regs[j] = load4(b + r * dim, kb * PT_KB + scol, dim, r < ne, vec_b);
     }
   };
   auto stash = [&](float* buf, const f32x4 (&regs)[4]) {
@@ -141,7 +131,7 @@ __global__ __launch_bounds__(256) void plda_product_kernel(const float* __restri
     const bool first = step < nkb;
     const int kb = first ? step : step - nkb;
     const int64_t row = m0 + 16 * rt + i;
-    return plda_load4((first ? a0 : a1) + row * dim, kb * PT_KB + 16 * u + 4 * g, dim, row < nt, first ? vec_a0 : vec_b);
+    return load4((first ? a0 : a1) + row * dim, kb * PT_KB + 16 * u + 4 * g, dim, row < nt, first ? vec_a0 : vec_b);
   };
 
   f32x4 ah[2][8];

@@ -10,9 +10,8 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "score_common.h"
 #include "svk_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -21,16 +20,6 @@ namespace {
 // kk = l >> 4) reads row i, floats [16 u + 4 kk, +4) of chunk u, and MFMA step (u, e) uses
 // element e of both operands, so the K order is permuted identically on both sides.
 // The same registers give the squared row norms (reduced over kk with two shuffles).
-__device__ __forceinline__ f32x4 load4(const float* row, int col, int dim, bool row_ok, bool vec_ok) {
-  f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-  if (!row_ok) return v;
-  if (vec_ok && col + 4 <= dim) return *reinterpret_cast<const f32x4*>(row + col);
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    if (col + e < dim) v[e] = row[col + e];
-  return v;
-}
-
 __global__ __launch_bounds__(256) void cosine_kernel(const float* __restrict__ test, const float* __restrict__ enroll,
                                                      int nt, int ns, int dim, float* __restrict__ out) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -202,9 +191,7 @@ __device__ __forceinline__ void cosine_tiled_body(const float* __restrict__ test
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           stage[(16 * rt + 4 * kk + r) * CT_SLD + 16 * ct + i] = accv[rt][ct][r] * rinv[rt][r] * sinv_e[ct];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     const int c4 = 4 * (lane & 7);
     float* const ob = out + (int64_t)m0 * ns + st_e * CT_BN + c4;
     const bool cols_in = (st_e + 1) * CT_BN <= ns;  // wave-uniform
@@ -215,9 +202,6 @@ __device__ __forceinline__ void cosine_tiled_body(const float* __restrict__ test
       if (rows_in || m0 + row < nt) {
         float* const dst = ob + (int64_t)row * ns;
         if (cols_in) {
-#ifdef SVK_COS_NOSTORE
-          if (v[0] == 123456.0f)
-#endif
           *reinterpret_cast<f32x4_u*>(dst) = v;
         } else {
 #pragma unroll
@@ -421,6 +405,11 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_scores_kernel(const float* 
 
 }  // namespace
 
+void svk_launch_inv_norm(svk_ctx* ctx, const float* d_x, int n, int dim, float* d_out) {
+  hipLaunchKernelGGL(inv_norm_kernel, dim3((unsigned)std::min((n + 3) / 4, ctx->num_cu * 8)), dim3(256), 0, ctx->stream, d_x, n,
+                     dim, d_out);
+}
+
 extern "C" {
 
 int svk_cosine_scores(svk_ctx* ctx, const float* d_test, const float* d_enroll, int32_t n_test, int32_t n_enroll,
@@ -437,8 +426,7 @@ int svk_cosine_scores(svk_ctx* ctx, const float* d_test, const float* d_enroll, 
     const int rc = svk_ensure_work(ctx, sizeof(float) * (size_t)n_enroll);
     if (rc != SVK_OK) return rc;
     float* einv = static_cast<float*>(ctx->work);
-    hipLaunchKernelGGL(inv_norm_kernel, dim3((unsigned)std::min((n_enroll + 3) / 4, ctx->num_cu * 8)), dim3(256), 0,
-                       ctx->stream, d_enroll, n_enroll, dim, einv);
+    svk_launch_inv_norm(ctx, d_enroll, n_enroll, dim, einv);
     const char* wenv = getenv("SVK_COS_WAVES");
     const bool w3 = wenv ? atoi(wenv) == 3 : false;
     auto kern = dim <= CT_KB ? (w3 ? cosine_tiled_kernel_w3<true> : cosine_tiled_kernel<true>)

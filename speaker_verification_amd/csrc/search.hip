@@ -1,14 +1,13 @@
 // Speaker search: the k best gallery rows of every query row by cosine score, without the score matrix.
 //   svk_cosine_topk <- 1:N identification against enrolled embeddings (evaluation.py:112-134 takes the argmax of a row of
 //       the [n_test x n_enroll] matrix; open-set search and large galleries cannot hold that matrix).
-// Phase 1 is the tiled product of svk_cosine_scores (scoring.hip: cosine_tiled_body's LDS-staged, double-buffered 32-row
+// Phase 1 is the tiled product of svk_cosine_scores (scoring.hip: cosine_tiled_kernel's LDS-staged, double-buffered 32-row
 // gallery block on v_mfma_f32_16x16x4_f32) with an on-chip selection in place of the store epilogue; phase 2 merges the
 // partial lists of the gallery spans, and the list of earlier calls with the accumulate flag, under the same total order.
 #include <algorithm>
 
+#include "score_common.h"
 #include "svk_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -60,20 +59,12 @@ __device__ __forceinline__ bool sr_before(float sa, long long ia, float sb, long
   return ka > kb || (ka == kb && ia < ib);
 }
 
-// One wave's DS instructions execute in order; this keeps the compiler from moving a lane's list accesses across the point
-// where another lane's become visible to it.
-__device__ __forceinline__ void sr_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 constexpr unsigned SR_EMPTY_SCORE = 0xFF800000u, SR_EMPTY_INDEX = 0xFFFFFFFFu;   // -inf, -1
 
 // Inserts (cs, col) into one row's sorted list of k entries, the whole wave at it: lane j holds entry j, the entries that
 // stay in front of the candidate are a prefix, the others move down one slot and the last one falls off.
 __device__ __forceinline__ void sr_insert(uint2* __restrict__ row_list, int k, int lane, float cs, int col) {
-  sr_wave_sync();
+  wave_sync();
   uint2 e = make_uint2(SR_EMPTY_SCORE, SR_EMPTY_INDEX);
   if (lane < k) e = row_list[lane];
   const bool stays = lane < k && sr_before(__uint_as_float(e.x), (long long)(int)e.y, cs, (long long)col);
@@ -84,32 +75,10 @@ __device__ __forceinline__ void sr_insert(uint2* __restrict__ row_list, int k, i
   }
 }
 
-__device__ __forceinline__ f32x4 sr_load4(const float* row, int col, int dim, bool row_ok, bool vec_ok) {
-  f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-  if (!row_ok) return v;
-  if (vec_ok && col + 4 <= dim) return *reinterpret_cast<const f32x4*>(row + col);
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    if (col + e < dim) v[e] = row[col + e];
-  return v;
-}
-
-// out[row] = 1 / ||x[row]||, a zero norm divides by 1: scoring.hip's pre-pass (one wave per row), here for both matrices.
-__global__ __launch_bounds__(256) void sr_inv_norm_kernel(const float* __restrict__ x, int n, int dim, float* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += gridDim.x * 4) {
-    const float* p = x + (int64_t)row * dim;
-    float s = 0.f;
-    for (int k = lane; k < dim; k += 64) s = fmaf(p[k], p[k], s);
-    s = wave_sum(s);
-    if (lane == 0) out[row] = s == 0.f ? 1.f : 1.0f / sqrtf(s);
-  }
-}
-
 // ---- phase 1 -------------------------------------------------------------------------------------------------------
 // Workgroup = (128-row query block rb, gallery span sp); wave w owns rows [32 w, 32 w + 32) of the block: two 16-row MFMA
 // tiles whose fragments stay in registers when dim <= 128 (HOIST).  K order, staging and MFMA sequence are
-// cosine_tiled_body's: kb, u, element e, so a score's bits depend on its two rows and dim alone.
+// cosine_tiled_kernel's: kb, u, element e, so a score's bits depend on its two rows and dim alone.
 // Accumulator layout: acc[rt][ct][r] of lane (i = l & 15, kk = l >> 4) = row 16 rt + 4 kk + r, column 16 ct + i.
 // Selection: every row has a sorted list of k (score, column) entries in LDS, private to its wave; the lane keeps its eight
 // rows' k-th scores as thresholds (NaN while the list is not full: everything passes; +inf for a k-th score of NaN).
@@ -147,7 +116,7 @@ __global__ __launch_bounds__(256) void search_tiles_kernel(const float* __restri
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int r = st * SR_BN + srow + 8 * j;
-        regs[j] = sr_load4(gallery + (int64_t)r * dim, kb * SR_KB + scol, dim, r < ng, vec_ok);
+        regs[j] = load4(gallery + (int64_t)r * dim, kb * SR_KB + scol, dim, r < ng, vec_ok);
       }
     }
   };
@@ -163,7 +132,7 @@ __global__ __launch_bounds__(256) void search_tiles_kernel(const float* __restri
     for (int rt = 0; rt < 2; ++rt) {
       const int row = m0 + 16 * rt + i;
 #pragma unroll
-      for (int u = 0; u < 8; ++u) a[rt][u] = sr_load4(query + (int64_t)row * dim, 16 * u + 4 * kk, dim, row < nq, vec_ok);
+      for (int u = 0; u < 8; ++u) a[rt][u] = load4(query + (int64_t)row * dim, 16 * u + 4 * kk, dim, row < nq, vec_ok);
     }
   }
   float rinv[2][4], thr[2][4];
@@ -218,7 +187,7 @@ __global__ __launch_bounds__(256) void search_tiles_kernel(const float* __restri
             sr_insert(mine + (16 * rt + 4 * (l >> 4) + r) * SR_KMAX, k, lane, cs, col);
           }
         }
-    sr_wave_sync();
+    wave_sync();
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
@@ -262,7 +231,7 @@ __global__ __launch_bounds__(256) void search_tiles_kernel(const float* __restri
             av[rt] = a[rt][u];
           } else {
             const int row = m0 + 16 * rt + i;
-            av[rt] = sr_load4(query + (int64_t)row * dim, kb * SR_KB + 16 * u + 4 * kk, dim, row < nq, vec_ok);
+            av[rt] = load4(query + (int64_t)row * dim, kb * SR_KB + 16 * u + 4 * kk, dim, row < nq, vec_ok);
           }
         }
 #pragma unroll
@@ -285,7 +254,7 @@ __global__ __launch_bounds__(256) void search_tiles_kernel(const float* __restri
   }
 
   // this unit's partial lists: [span][query row][k], columns still local to this call's gallery
-  sr_wave_sync();
+  wave_sync();
   for (int e = lane; e < 32 * k; e += 64) {
     const int rl = e / k, j = e - rl * k;
     const int row = m0 + rl;
@@ -330,14 +299,14 @@ __global__ __launch_bounds__(64) void search_merge_kernel(const float* __restric
   const int lane = threadIdx.x;
   const int n_lists = spans + (accumulate ? 1 : 0);
   for (int q = blockIdx.x; q < nq; q += gridDim.x) {
-    sr_wave_sync();   // the previous query's reads of old_s / old_i are done
+    wave_sync();   // the previous query's reads of old_s / old_i are done
     const size_t ob = (size_t)q * (size_t)k;
     if (accumulate && lane < k) {
       old_s[lane] = out_score[ob + lane];
       old_i[lane] = out_idx[ob + lane];
     }
     for (int c = lane; c < n_lists; c += 64) cursor[c] = 0;
-    sr_wave_sync();
+    wave_sync();
 
     float bs = 0.f;
     long long bi = -1;
@@ -450,10 +419,8 @@ int svk_cosine_topk(svk_ctx* ctx, const float* d_query, int32_t n_query, const f
   float* const ws_score = reinterpret_cast<float*>(w + p.off_score);
   int* const ws_idx = reinterpret_cast<int*>(w + p.off_idx);
 
-  hipLaunchKernelGGL(sr_inv_norm_kernel, dim3((unsigned)std::min((n_query + 3) / 4, ctx->num_cu * 8)), dim3(256), 0, ctx->stream,
-                     d_query, n_query, dim, qinv);
-  hipLaunchKernelGGL(sr_inv_norm_kernel, dim3((unsigned)std::min((n_gallery + 3) / 4, ctx->num_cu * 8)), dim3(256), 0,
-                     ctx->stream, d_gallery, n_gallery, dim, ginv);
+  svk_launch_inv_norm(ctx, d_query, n_query, dim, qinv);   // scoring.hip's pre-pass (one wave per row), here for both matrices
+  svk_launch_inv_norm(ctx, d_gallery, n_gallery, dim, ginv);
   auto kern = dim <= SR_KB ? search_tiles_kernel<true> : search_tiles_kernel<false>;
   hipLaunchKernelGGL(kern, dim3((unsigned)(p.n_rb * p.spans)), dim3(256), 0, ctx->stream, d_query, d_gallery, qinv, ginv,
                      n_query, n_gallery, dim, k, p.spans, p.tiles, (long long)index_base,

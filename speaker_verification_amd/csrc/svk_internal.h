@@ -117,6 +117,10 @@ int svk_persistent_grid(svk_ctx* ctx, const char* name, void (*kern)(P), size_t 
   return SVK_OK;
 }
 
+// out[row] = 1 / ||x[row]|| for the n rows of x, a zero norm as 1, on the handle's stream (scoring.hip's inv_norm_kernel: the
+// pre-pass of the tiled cosine product and of the search, which runs it on both operands).  The caller checks the launch.
+void svk_launch_inv_norm(svk_ctx* ctx, const float* d_x, int n, int dim, float* d_out);
+
 // 64-lane wave sum; every lane gets the total.
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

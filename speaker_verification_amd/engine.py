@@ -123,6 +123,76 @@ class Engine:
     def _ptr(t):
         return C.c_void_p(t.data_ptr()) if t is not None else None
 
+    # ---- argument rules, each stated once ------------------------------------------------------------------------
+    def _frames(self, n_frames):
+        """Per-clip counts (frames, samples) as int32 on the device, or None."""
+        return self.to_device(n_frames, _torch().int32) if n_frames is not None else None
+
+    def _workspace(self, nbytes):
+        """A workspace sized by the library (svk_*_workspace_bytes): a torch allocation of at least 16 bytes, so that its
+        pointer is never NULL; every entry accepts a larger workspace than it asks for."""
+        return _torch().empty((max(16, int(nbytes)),), dtype=_torch().uint8, device=self.device)
+
+    def _given_out(self, out, shape, dtype, what):
+        """A caller-supplied output: a contiguous device tensor of that dtype and shape (an int: that many elements)."""
+        ok = isinstance(out, _torch().Tensor) and out.is_cuda and out.dtype == dtype and out.is_contiguous() and \
+            (out.numel() == shape if isinstance(shape, int) else tuple(out.shape) == tuple(shape))
+        if not ok:
+            raise ValueError(what)
+
+    def _labels01(self, labels, n):
+        """0/1 labels as uint8 [n] on the device (anything non-zero is a target)."""
+        torch = _torch()
+        lb = self.to_device(labels).reshape(-1)
+        lb = (lb != 0).to(torch.uint8) if lb.dtype != torch.uint8 else lb
+        if lb.numel() != n:
+            raise ValueError("scores and labels differ in length")
+        return lb
+
+    def _scores_labels(self, scores, labels):
+        sc = self.to_device(scores, _torch().float32).reshape(-1)
+        return sc, self._labels01(labels, sc.numel())
+
+    def _two_matrices(self, a, b, who):
+        """Two float32 matrices (Na, D) and (Nb, D) on the device; `b is a` stays one tensor."""
+        f32 = _torch().float32
+        x = self.to_device(a, f32)
+        y = x if b is a else self.to_device(b, f32)
+        if x.dim() != 2 or y.dim() != 2 or x.shape[1] != y.shape[1]:
+            raise ValueError("%s wants (Na, D) and (Nb, D)" % who)
+        return x, y
+
+    def _counter(self, t, name):
+        """An optional int32 device counter (the caller zeroes it)."""
+        torch = _torch()
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.numel() >= 1):
+            raise ValueError("%s must be an int32 device tensor" % name)
+        return t
+
+    def _trials(self, idx_a, idx_b, bad_count):
+        """The two index lists of a trial list as int64 on the device, and its bad-index counter."""
+        i64 = _torch().int64
+        ia, ib = self.to_device(idx_a, i64).reshape(-1), self.to_device(idx_b, i64).reshape(-1)
+        if ia.numel() != ib.numel():
+            raise ValueError("idx_a and idx_b differ in length")
+        return ia, ib, self._counter(bad_count, "bad_count")
+
+    def _row_index(self, row_index, n_rows):
+        """The optional row permutation of the grouped entries as int64 [n_rows] on the device."""
+        if row_index is None:
+            return None
+        index = self.to_device(row_index, _torch().int64).reshape(-1)
+        if index.numel() != n_rows:
+            raise ValueError("row_index holds one entry per row of emb")
+        return index
+
+    def _segments(self, seg_start, row_index, n_rows):
+        """CSR groups of rows: seg_start int64 [n_seg + 1] and the optional row_index on the device."""
+        start = self.to_device(seg_start, _torch().int64).reshape(-1)
+        if start.numel() < 1:
+            raise ValueError("seg_start holds n_seg + 1 offsets")
+        return start, self._row_index(row_index, n_rows)
+
     def synchronize(self):
         check(self.lib.svk_sync(self.ctx), self.ctx)
 
@@ -301,7 +371,7 @@ class Engine:
                 and feat.is_contiguous()):
             raise ValueError("cmvn_ works in place on a contiguous float32 CUDA tensor")
         shape = feat.shape if feat.dim() == 3 else (1,) + tuple(feat.shape)
-        nf = self.to_device(n_frames, torch.int32) if n_frames is not None else None
+        nf = self._frames(n_frames)
         self._stream()
         check(self.lib.svk_cmvn(self.ctx, self._ptr(feat), shape[0], shape[1], shape[2], self._ptr(nf),
                                 int(bool(variance))), self.ctx)
@@ -314,7 +384,7 @@ class Engine:
         if not (isinstance(feat, torch.Tensor) and feat.is_cuda and feat.dtype == torch.float32 and feat.is_contiguous()
                 and feat.dim() == 3):
             raise ValueError("cmvn_stats wants a contiguous float32 CUDA tensor [n_utt, max_frames, cols]")
-        nf = self.to_device(n_frames, torch.int32) if n_frames is not None else None
+        nf = self._frames(n_frames)
         stats = torch.zeros((feat.shape[0], 2, feat.shape[2]), dtype=torch.float64, device=self.device)
         self._stream()
         check(self.lib.svk_cmvn_stats(self.ctx, self._ptr(feat), feat.shape[0], feat.shape[1], feat.shape[2], self._ptr(nf),
@@ -340,7 +410,7 @@ class Engine:
         [:, ch] is bit-identical to cmvn_stats of plane ch.  delta_planes / cube_gather_delta(..., stats=...) apply them."""
         torch = _torch()
         feat = self._static_rows(feat, "delta_cmvn_stats")
-        nf = self.to_device(n_frames, torch.int32) if n_frames is not None else None
+        nf = self._frames(n_frames)
         stats = torch.zeros((feat.shape[0], 3, 2, feat.shape[2]), dtype=torch.float64, device=self.device)
         self._stream()
         check(self.lib.svk_delta_cmvn_stats(self.ctx, self._ptr(feat), feat.shape[0], feat.shape[1], feat.shape[2], self._ptr(nf),
@@ -354,12 +424,12 @@ class Engine:
         torch = _torch()
         feat = self._static_rows(feat, "delta_planes")
         n, T, Cc = feat.shape
-        nf = self.to_device(n_frames, torch.int32) if n_frames is not None else None
+        nf = self._frames(n_frames)
         stats = self._stats3(stats, n, Cc)
         if out is None:
             out = torch.empty((n, 3, T, Cc), dtype=torch.float32, device=self.device)
-        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 3, T, Cc)):
-            raise ValueError("out must be a contiguous float32 CUDA tensor [n, 3, max_frames, cols]")
+        else:
+            self._given_out(out, (n, 3, T, Cc), torch.float32, "out must be a contiguous float32 CUDA tensor [n, 3, max_frames, cols]")
         self._stream()
         check(self.lib.svk_delta_planes(self.ctx, self._ptr(feat), n, T, Cc, self._ptr(nf), int(delta), self._ptr(stats),
                                         self._ptr(out)), self.ctx)
@@ -386,7 +456,7 @@ class Engine:
         torch = _torch()
         x = self.to_device(feat, torch.float32)
         shape = x.shape if x.dim() == 3 else (1,) + tuple(x.shape)
-        nf = self.to_device(n_frames, torch.int32) if n_frames is not None else None
+        nf = self._frames(n_frames)
         out = x.clone()                         # rows past n_frames keep the input
         tmp = torch.empty_like(x) if variance else None
         self._stream()
@@ -424,7 +494,7 @@ class Engine:
         fsamp = int(frame_samples) if frame_samples else int(fs * (frame_ms / 1000.0) * 2) // 2   # vad.py:50
         ring_len = int(ring_len) if ring_len else int(padding_ms / frame_ms)                       # vad.py:81
         ring_thresh = int(math.floor(0.9 * ring_len))                    # count > 0.9 * maxlen, vad.py:99,117
-        lens = self.to_device(lengths, torch.int32) if lengths is not None else None
+        lens = self._frames(lengths)
         if offsets is not None:
             if lens is None:
                 raise ValueError("offsets need lengths")
@@ -518,8 +588,8 @@ class Engine:
         shape = (n, 3, n_crops, crop_frames, Cc)
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
-            raise ValueError("out must be a contiguous float32 CUDA tensor [n, 3, n_crops, crop_frames, cols]")
+        else:
+            self._given_out(out, shape, torch.float32, "out must be a contiguous float32 CUDA tensor [n, 3, n_crops, crop_frames, cols]")
         self._stream()
         check(self.lib.svk_cube_gather_delta(self.ctx, self._ptr(feat), n, T, Cc, self._ptr(idx), n_crops, int(crop_frames),
                                              int(delta), self._ptr(stats), self._ptr(out)), self.ctx)
@@ -676,10 +746,7 @@ class Engine:
 
     def cosine_scores(self, test, enroll):
         torch = _torch()
-        t = self.to_device(test, torch.float32)
-        e = self.to_device(enroll, torch.float32)
-        if t.dim() != 2 or e.dim() != 2 or t.shape[1] != e.shape[1]:
-            raise ValueError("cosine_scores wants (Nt, D) and (Ns, D)")
+        t, e = self._two_matrices(test, enroll, "cosine_scores")
         out = torch.empty((t.shape[0], e.shape[0]), dtype=torch.float32, device=self.device)
         self._stream()
         check(self.lib.svk_cosine_scores(self.ctx, self._ptr(t), self._ptr(e), t.shape[0], e.shape[0], t.shape[1],
@@ -688,28 +755,14 @@ class Engine:
 
     def roc_eer(self, scores, labels):
         """(eer, auc) of flat scores / 0-1 labels, computed on the device (svk_roc_eer)."""
-        torch = _torch()
-        sc = self.to_device(scores, torch.float32).reshape(-1)
-        lb = self.to_device(labels).reshape(-1)
-        lb = (lb != 0).to(torch.uint8) if lb.dtype != torch.uint8 else lb
+        sc, lb = self._scores_labels(scores, labels)
         n = sc.numel()
-        if lb.numel() != n:
-            raise ValueError("scores and labels differ in length")
-        work = torch.empty((int(self.lib.svk_roc_workspace_bytes(n)),), dtype=torch.uint8, device=self.device)
+        work = self._workspace(self.lib.svk_roc_workspace_bytes(n))
         out = (C.c_double * 4)()
         self._stream()
         check(self.lib.svk_roc_eer(self.ctx, self._ptr(sc), self._ptr(lb), n, self._ptr(work), work.numel(), out),
               self.ctx)
         return float(out[0]), float(out[1])
-
-    def _scores_labels(self, scores, labels):
-        torch = _torch()
-        sc = self.to_device(scores, torch.float32).reshape(-1)
-        lb = self.to_device(labels).reshape(-1)
-        lb = (lb != 0).to(torch.uint8) if lb.dtype != torch.uint8 else lb
-        if lb.numel() != sc.numel():
-            raise ValueError("scores and labels differ in length")
-        return sc, lb
 
     def roc_dcf(self, scores, labels, operating_points=()):
         """svk_roc_dcf: EER, AUC, minDCF and the thresholds of flat scores / 0-1 labels from one sort on the device.
@@ -717,12 +770,11 @@ class Engine:
         entry per operating point in the lists min_dcf, threshold, p_miss, p_fa (accept when score >= threshold; the origin of
         the ROC, "reject everything", has threshold +inf).  eer and auc are roc_eer's values, bit for bit.  Raises for a
         non-finite score or a single class."""
-        torch = _torch()
         sc, lb = self._scores_labels(scores, labels)
         n = sc.numel()
         ops = np.ascontiguousarray(np.asarray(operating_points, dtype=np.float64).reshape(-1, 3))
         n_op = int(ops.shape[0])
-        work = torch.empty((max(1, int(self.lib.svk_roc_dcf_workspace_bytes(n))),), dtype=torch.uint8, device=self.device)
+        work = self._workspace(self.lib.svk_roc_dcf_workspace_bytes(n))
         out = (C.c_double * (5 + 4 * max(n_op, 0)))()
         self._stream()
         check(self.lib.svk_roc_dcf(self.ctx, self._ptr(sc), self._ptr(lb), n, ops.ctypes.data_as(C.POINTER(C.c_double)), n_op,
@@ -776,20 +828,15 @@ class Engine:
         float64 [n_sys + 1] and Hessian float64 [n_sys + 1, n_sys + 1] (symmetric, filled from the packed triangle) of
         z = w . (s, 1) + tau, and counts = (targets, non-targets, skipped): a trial with a non-finite score is left out and
         counted as skipped.  class_weight = (target, non-target).  value_only: grad and hess are None (not computed)."""
-        torch = _torch()
         sc, stride = self._score_planes(scores)
         n_sys, n = int(sc.shape[0]), int(sc.shape[1])
-        lb = self.to_device(labels).reshape(-1)
-        lb = (lb != 0).to(torch.uint8) if lb.dtype != torch.uint8 else lb
-        if lb.numel() != n:
-            raise ValueError("scores and labels differ in length")
+        lb = self._labels01(labels, n)
         w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
         cw = np.ascontiguousarray(np.asarray(class_weight, dtype=np.float64).reshape(-1))
         if w.size != n_sys + 1 or cw.size != 2:
             raise ValueError("calibration_stats wants n_sys + 1 = %d weights and 2 class weights" % (n_sys + 1))
         dim = n_sys + 1
-        work = torch.empty((max(16, int(self.lib.svk_calibration_stats_workspace_bytes(n, n_sys))),), dtype=torch.uint8,
-                           device=self.device)
+        work = self._workspace(self.lib.svk_calibration_stats_workspace_bytes(n, n_sys))
         out = (C.c_double * (2 + dim + dim * (dim + 1) // 2))()
         count = (C.c_int64 * 3)()
         dp = C.POINTER(C.c_double)
@@ -817,8 +864,8 @@ class Engine:
             raise ValueError("calibration_apply wants n_sys + 1 = %d weights, got %d" % (n_sys + 1, w.size))
         if out is None:
             out = torch.empty((n,), dtype=torch.float32, device=self.device)
-        elif not (out.device == self.device and out.dtype == torch.float32 and out.numel() == n and out.is_contiguous()):
-            raise ValueError("out wants a contiguous float32 device tensor of %d elements" % n)
+        else:
+            self._given_out(out, n, torch.float32, "out wants a contiguous float32 device tensor of %d elements" % n)
         self._stream()
         check(self.lib.svk_calibration_apply(self.ctx, self._ptr(sc), n_sys, stride, n, w.ctypes.data_as(C.POINTER(C.c_double)),
                                              self._ptr(out)), self.ctx)
@@ -829,14 +876,10 @@ class Engine:
         curve=True (eer, auc, fpr, tpr): sklearn's roc_curve(drop_intermediate=True) as float64 NumPy arrays, fps / fps[-1]
         and tps / tps[-1] on the device's integer counts.  Raises for a split with one class or a non-finite score."""
         torch = _torch()
-        sc = self.to_device(scores, torch.float32).reshape(-1)
-        lb = self.to_device(labels).reshape(-1)
-        lb = (lb != 0).to(torch.uint8) if lb.dtype != torch.uint8 else lb
+        sc, lb = self._scores_labels(scores, labels)
         n, k = sc.numel(), int(k)
-        if lb.numel() != n:
-            raise ValueError("scores and labels differ in length")
         step = split_step(n, k) if k >= 1 else 0
-        work = torch.empty((max(1, int(self.lib.svk_roc_k_workspace_bytes(n, k))),), dtype=torch.uint8, device=self.device)
+        work = self._workspace(self.lib.svk_roc_k_workspace_bytes(n, k))
         planes = torch.empty((2, k, step + 1), dtype=torch.int32, device=self.device) if curve and step >= 2 else None
         out = (C.c_double * (4 * max(k, 1)))()
         self._stream()
@@ -884,25 +927,17 @@ class Engine:
         n_rows, dim = int(x.shape[0]), int(x.shape[1])
         if (rows_per_seg is None) == (seg_start is None):
             raise ValueError("embedding_pool wants either rows_per_seg or seg_start")
-        start, K = None, 0
+        K = 0
         if seg_start is not None:
-            start = self.to_device(seg_start, torch.int64).reshape(-1)
-            if start.numel() < 1:
-                raise ValueError("seg_start holds n_seg + 1 offsets")
+            start, index = self._segments(seg_start, row_index, n_rows)
             n_seg = start.numel() - 1
         else:
             K = int(rows_per_seg)
             if K < 1 or n_rows % K:
                 raise ValueError("rows_per_seg = %d does not divide the %d rows" % (K, n_rows))
             n_seg = n_rows // K
-        index = None
-        if row_index is not None:
-            index = self.to_device(row_index, torch.int64).reshape(-1)
-            if index.numel() != n_rows:
-                raise ValueError("row_index holds one entry per row of emb")
-        if empty_count is not None and not (isinstance(empty_count, torch.Tensor) and empty_count.is_cuda
-                                            and empty_count.dtype == torch.int32 and empty_count.numel() >= 1):
-            raise ValueError("empty_count must be an int32 device tensor")
+            start, index = None, self._row_index(row_index, n_rows)
+        self._counter(empty_count, "empty_count")
         out = torch.empty((n_seg, dim), dtype=torch.float32, device=self.device)
         self._stream()
         check(self.lib.svk_embedding_pool(self.ctx, self._ptr(x), n_rows, dim, n_seg, K, self._ptr(start), self._ptr(index),
@@ -920,17 +955,9 @@ class Engine:
         if x.dim() != 2:
             raise ValueError("class_scatter wants rows (n_rows, dim)")
         n_rows, dim = int(x.shape[0]), int(x.shape[1])
-        start = self.to_device(seg_start, torch.int64).reshape(-1)
-        if start.numel() < 1:
-            raise ValueError("seg_start holds n_class + 1 offsets")
+        start, index = self._segments(seg_start, row_index, n_rows)
         n_class = start.numel() - 1
-        index = None
-        if row_index is not None:
-            index = self.to_device(row_index, torch.int64).reshape(-1)
-            if index.numel() != n_rows:
-                raise ValueError("row_index holds one entry per row of emb")
-        work = torch.empty((max(16, int(self.lib.svk_class_scatter_workspace_bytes(n_rows, dim, n_class))),), dtype=torch.uint8,
-                           device=self.device)
+        work = self._workspace(self.lib.svk_class_scatter_workspace_bytes(n_rows, dim, n_class))
         mean = torch.empty((n_class, dim), dtype=torch.float64, device=self.device)
         sw = torch.empty((dim, dim), dtype=torch.float64, device=self.device)
         self._stream()
@@ -974,17 +1001,8 @@ class Engine:
         torch = _torch()
         if metric not in self.PAIR_METRICS:
             raise ValueError("metric must be 'cosine' or 'l2', got %r" % (metric,))
-        x = self.to_device(a, torch.float32)
-        y = x if b is a else self.to_device(b, torch.float32)
-        if x.dim() != 2 or y.dim() != 2 or x.shape[1] != y.shape[1]:
-            raise ValueError("pair_scores wants (Na, D) and (Nb, D)")
-        ia = self.to_device(idx_a, torch.int64).reshape(-1)
-        ib = self.to_device(idx_b, torch.int64).reshape(-1)
-        if ia.numel() != ib.numel():
-            raise ValueError("idx_a and idx_b differ in length")
-        if bad_count is not None and not (isinstance(bad_count, torch.Tensor) and bad_count.is_cuda
-                                          and bad_count.dtype == torch.int32 and bad_count.numel() >= 1):
-            raise ValueError("bad_count must be an int32 device tensor")
+        x, y = self._two_matrices(a, b, "pair_scores")
+        ia, ib, bad_count = self._trials(idx_a, idx_b, bad_count)
         out = torch.empty((ia.numel(),), dtype=torch.float32, device=self.device)
         self._stream()
         check(self.lib.svk_pair_scores(self.ctx, self._ptr(x), x.shape[0], self._ptr(y), y.shape[0], x.shape[1], self._ptr(ia),
@@ -1012,14 +1030,10 @@ class Engine:
         float64 [D], the between-speaker variances (`plda.Plda`).  A float64 pre-pass and one f32 MFMA product; the workspace
         is a torch allocation sized by the library."""
         torch = _torch()
-        t = self.to_device(test, torch.float32)
-        e = self.to_device(enroll, torch.float32)
-        if t.dim() != 2 or e.dim() != 2 or t.shape[1] != e.shape[1]:
-            raise ValueError("plda_scores wants (Nt, D) and (Ns, D)")
+        t, e = self._two_matrices(test, enroll, "plda_scores")
         nt, ns, dim = int(t.shape[0]), int(e.shape[0]), int(t.shape[1])
         p, cnt = self._plda_operands(psi, counts, dim, ns)
-        work = torch.empty((max(16, int(self.lib.svk_plda_scores_workspace_bytes(nt, ns, dim, int(cnt is not None)))),),
-                           dtype=torch.uint8, device=self.device)
+        work = self._workspace(self.lib.svk_plda_scores_workspace_bytes(nt, ns, dim, int(cnt is not None)))
         out = torch.empty((nt, ns), dtype=torch.float32, device=self.device)
         self._stream()
         check(self.lib.svk_plda_scores(self.ctx, self._ptr(t), nt, self._ptr(e), ns, dim, self._ptr(p), self._ptr(cnt),
@@ -1032,17 +1046,8 @@ class Engine:
         be a itself.  An index outside its matrix gives NaN at that trial and counts in bad_count (an int32 [1] device tensor
         the caller zeroes), if given."""
         torch = _torch()
-        x = self.to_device(a, torch.float32)
-        y = x if b is a else self.to_device(b, torch.float32)
-        if x.dim() != 2 or y.dim() != 2 or x.shape[1] != y.shape[1]:
-            raise ValueError("plda_pair_scores wants (Na, D) and (Nb, D)")
-        ia = self.to_device(idx_a, torch.int64).reshape(-1)
-        ib = self.to_device(idx_b, torch.int64).reshape(-1)
-        if ia.numel() != ib.numel():
-            raise ValueError("idx_a and idx_b differ in length")
-        if bad_count is not None and not (isinstance(bad_count, torch.Tensor) and bad_count.is_cuda
-                                          and bad_count.dtype == torch.int32 and bad_count.numel() >= 1):
-            raise ValueError("bad_count must be an int32 device tensor")
+        x, y = self._two_matrices(a, b, "plda_pair_scores")
+        ia, ib, bad_count = self._trials(idx_a, idx_b, bad_count)
         p, cnt = self._plda_operands(psi, counts_b, int(x.shape[1]), int(y.shape[0]))
         out = torch.empty((ia.numel(),), dtype=torch.float32, device=self.device)
         self._stream()
@@ -1059,10 +1064,7 @@ class Engine:
         accumulate into those tensors (lists of earlier calls over other chunks of the gallery, disjoint index ranges); the
         result equals one call over the whole gallery bit for bit.  The workspace is a torch allocation sized by the library."""
         torch = _torch()
-        q = self.to_device(query, torch.float32)
-        g = self.to_device(gallery, torch.float32)
-        if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
-            raise ValueError("cosine_topk wants (Nq, D) and (Ng, D)")
+        q, g = self._two_matrices(query, gallery, "cosine_topk")
         n, ng, dim, k = int(q.shape[0]), int(g.shape[0]), int(q.shape[1]), int(k)
         ex = None
         if exclude is not None:
@@ -1075,11 +1077,8 @@ class Engine:
         else:
             scores, indices = into
             for t, dt in ((scores, torch.float32), (indices, torch.int64)):
-                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()
-                        and tuple(t.shape) == (n, k)):
-                    raise ValueError("into wants contiguous device tensors (float32 [n, k], int64 [n, k])")
-        work = torch.empty((max(16, int(self.lib.svk_cosine_topk_workspace_bytes(n, ng, dim, k))),), dtype=torch.uint8,
-                           device=self.device)
+                self._given_out(t, (n, k), dt, "into wants contiguous device tensors (float32 [n, k], int64 [n, k])")
+        work = self._workspace(self.lib.svk_cosine_topk_workspace_bytes(n, ng, dim, k))
         self._stream()
         check(self.lib.svk_cosine_topk(self.ctx, self._ptr(q), n, self._ptr(g), ng, dim, k, int(index_base), self._ptr(ex),
                                        0 if into is None else 1, self._ptr(work), work.numel(), self._ptr(scores),
@@ -1088,9 +1087,8 @@ class Engine:
 
     def l2_dist(self, a, b):
         torch = _torch()
-        a = self.to_device(a, torch.float32)
-        b = self.to_device(b, torch.float32)
-        if a.shape != b.shape or a.dim() != 2:
+        a, b = self._two_matrices(a, b, "l2_dist")
+        if a.shape != b.shape:
             raise ValueError("l2_dist wants two (n, D) matrices")
         out = torch.empty((a.shape[0],), dtype=torch.float32, device=self.device)
         self._stream()

@@ -169,27 +169,18 @@ def evaluate_trials(embeddings, labels, idx_a, idx_b, metric="cosine", operating
     calibration: a fitted one-system `calibration.Calibration`: the trial scores go through it before the metrics (scores = the
     calibrated LLRs) and the dict gains cllr and the list act_dcf, the cost of deciding at each operating point's Bayes
     threshold (`svk_decision_counts`; min_dcf <= act_dcf, the gap is the calibration loss).  None (the default) changes nothing."""
+    from .pipeline import trial_scores
     eng = get_engine()
+    if calibration is not None and calibration.n_sys != 1:
+        raise ValueError("evaluate_trials scores one system: the calibration must be fitted on one, not %r" % (calibration.n_sys,))
     bad = torch.zeros((1,), dtype=torch.int32, device=eng.device)
     emb = eng.to_device(embeddings, torch.float32)
-    if backend is not None:
-        emb = backend.transform(emb, engine=eng)
-    if plda is not None:
-        if metric != "cosine":
-            raise ValueError("PLDA scores are log-likelihood ratios: metric does not apply")
-        emb = plda.project(emb, engine=eng)
-        scores = plda.score_trials(emb, idx_a, idx_b, bad_count=bad, engine=eng)
-    else:
-        scores = eng.pair_scores(emb, emb, idx_a, idx_b, metric=metric, bad_count=bad)
+    scores = trial_scores(eng, emb, idx_a, idx_b, None, metric, backend, plda, calibration, bad)
     if int(bad.item()):
         raise ValueError("evaluate_trials: %d trials index outside the %d embeddings" % (int(bad.item()), emb.shape[0]))
     labels = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1)
     if labels.size != scores.numel():
         raise ValueError("one label per trial")
-    if calibration is not None:
-        if calibration.n_sys != 1:
-            raise ValueError("evaluate_trials scores one system: the calibration must be fitted on one, not %r" % (calibration.n_sys,))
-        scores = calibration.apply(scores, engine=eng, out=scores)
     ops = [tuple(float(v) for v in op) for op in operating_points]
     if device:
         res = eng.roc_dcf(scores, labels, ops)

@@ -758,29 +758,20 @@ class VerificationPipeline:
 
     def project(self, emb):
         """The rows as the scorers see them: through the back end and the PLDA projection, or unchanged without either."""
-        if self.backend is not None:
-            emb = self.backend.transform(emb, engine=self.eng)
-        return emb if self.plda is None else self.plda.project(emb, engine=self.eng)
+        return project_rows(self.eng, emb, self.backend, self.plda)
 
     def score(self, test_emb, enroll_emb, counts=None):
         """Every test row against every enrolled row: cosines, or with `plda` log-likelihood ratios.  counts (PLDA only): the
         utterances behind each enrolled row when those are mean models (`enroll_mean(..., l2=False)` with a model fitted
         with l2_in=False, whose projection is the mean of the projections; otherwise build the models with `Plda.enroll` and
         score them with `Plda.score`)."""
-        if self.plda is not None:
-            return self._calibrated(self.plda.score(self.project(test_emb), self.project(enroll_emb), counts=counts,
-                                                    engine=self.eng))
-        if counts is not None:
+        if self.plda is None and counts is not None:
             raise ValueError("counts belong to PLDA scoring: the cosine does not use them")
-        if self.backend is not None:
-            test_emb, enroll_emb = self.project(test_emb), self.project(enroll_emb)
-        return self._calibrated(self.eng.cosine_scores(test_emb, enroll_emb))
-
-    def _calibrated(self, scores):
-        """Fresh scores of any shape -> the same tensor holding calibrated LLRs; untouched without a calibration."""
-        if self.calibration is None:
-            return scores
-        self.calibration.apply(scores.reshape(-1), engine=self.eng, out=scores.reshape(-1))
+        test_emb, enroll_emb = self.project(test_emb), self.project(enroll_emb)
+        scores = self.eng.cosine_scores(test_emb, enroll_emb) if self.plda is None else \
+            self.plda.score(test_emb, enroll_emb, counts=counts, engine=self.eng)
+        if self.calibration is not None:      # in place on the fresh scores
+            self.calibration.apply(scores.reshape(-1), engine=self.eng, out=scores.reshape(-1))
         return scores
 
     def decide(self, llr, p_target, c_miss=1, c_fa=1):
@@ -830,15 +821,31 @@ class VerificationPipeline:
         `score`.  On several GPUs call it on the all-gathered embeddings (`distributed.all_gather_embeddings`); every rank
         then holds the whole list's scores (the trial list itself is not sharded).  With `plda`: log-likelihood ratios through
         `svk_plda_pair_scores`, emb_a the test side and emb_b the enrolled side (one utterance each); `metric` must be left alone."""
-        if self.plda is not None:
-            if metric != "cosine":
-                raise ValueError("PLDA scores are log-likelihood ratios: metric does not apply")
-            u_a = self.project(emb_a)
-            return self._calibrated(self.plda.score_trials(u_a, idx_a, idx_b, u_b=None if emb_b is None else self.project(emb_b),
-                                                           engine=self.eng))
-        if self.backend is not None:
-            emb_a, emb_b = self.project(emb_a), None if emb_b is None else self.project(emb_b)
-        return self._calibrated(self.eng.pair_scores(emb_a, emb_a if emb_b is None else emb_b, idx_a, idx_b, metric=metric))
+        return trial_scores(self.eng, emb_a, idx_a, idx_b, emb_b, metric, self.backend, self.plda, self.calibration)
+
+
+def project_rows(eng, emb, backend, plda):
+    """emb through the back end and the PLDA projection, or unchanged without either."""
+    if backend is not None:
+        emb = backend.transform(emb, engine=eng)
+    return emb if plda is None else plda.project(emb, engine=eng)
+
+
+def trial_scores(eng, emb_a, idx_a, idx_b, emb_b=None, metric="cosine", backend=None, plda=None, calibration=None, bad_count=None):
+    """The scoring chain of a trial list (`VerificationPipeline.score_trials`, `evaluation.evaluate_trials`): both sides through
+    `project_rows`, PLDA log-likelihood ratios or `svk_pair_scores`, the calibration in place -> float32 [n_trials] on the
+    device.  emb_b None: both indices address emb_a.  bad_count: an int32 device counter of the indices outside their matrix."""
+    if plda is not None and metric != "cosine":
+        raise ValueError("PLDA scores are log-likelihood ratios: metric does not apply")
+    u_a = project_rows(eng, emb_a, backend, plda)
+    u_b = u_a if emb_b is None else project_rows(eng, emb_b, backend, plda)
+    if plda is not None:
+        scores = plda.score_trials(u_a, idx_a, idx_b, u_b=u_b, bad_count=bad_count, engine=eng)
+    else:
+        scores = eng.pair_scores(u_a, u_b, idx_a, idx_b, metric=metric, bad_count=bad_count)
+    if calibration is not None:
+        calibration.apply(scores, engine=eng, out=scores)
+    return scores
 
 
 def enroll_last_utterance(embeddings, speaker_ids):

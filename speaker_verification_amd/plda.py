@@ -16,7 +16,7 @@ An enrolled model is the mean of n >= 1 projected utterances, a test utterance i
 """
 import numpy as np
 
-from .backend import _inverse_root, scatter_matrices
+from .backend import _inverse_root, class_statistics, scatter_matrices
 
 
 def solve_plda(class_mean, counts, sw, out_dim=None, shrinkage=0.0):
@@ -133,14 +133,7 @@ class Plda:
     def fit(self, embeddings, speaker_ids, out_dim=None, l2_in=True, shrinkage=1e-3, engine=None):
         """Class statistics of embeddings [n, dim] (device tensor or array) under speaker_ids [n] on the device, then
         `solve_plda`.  l2_in: rows are L2-normalised before the statistics -- and in `project`.  Returns self."""
-        from .engine import get_engine
-        from .pipeline import speaker_segments
-        uniq, seg_start, row_index = speaker_segments(speaker_ids)
-        if int(row_index.size) != int(embeddings.shape[0]):
-            raise ValueError("fit wants one speaker id per embedding row")
-        class_mean, sw = (engine or get_engine()).class_scatter(embeddings, seg_start, row_index=row_index, l2_rows=l2_in)
-        mean, v, psi = solve_plda(class_mean.cpu().numpy(), np.diff(seg_start), sw.cpu().numpy(), out_dim=out_dim,
-                                  shrinkage=shrinkage)
+        mean, v, psi = solve_plda(*class_statistics(embeddings, speaker_ids, l2_in, engine), out_dim=out_dim, shrinkage=shrinkage)
         self.mean, self.v, self.psi, self.l2_in, self.shrinkage = mean, v, _checked_psi(psi), bool(l2_in), float(shrinkage)
         self._device = {}
         return self

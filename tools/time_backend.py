@@ -10,34 +10,8 @@ Medians of --reps calls after --warmup; the spread (min .. max) is reported besi
 SVK_TOOL_LIB=path/to/libsvk.so times another build.  One JSON line on stdout."""
 import argparse
 import json
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-HBM_PEAK = 8.0e12          # MI355X HBM3E, spec (6.3 TB/s is the measured copy rate)
-
-
-def one(torch, fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
-def alternated(torch, fns, reps, warmup):
-    """{name: sorted times in ms}: the functions take turns, call by call, so that clocks and cache state drift for all alike"""
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in fns}
-    for _ in range(reps):
-        for name, fn in fns.items():
-            times[name].append(one(torch, fn))
-    return {name: sorted(v) for name, v in times.items()}
+import _timing as T          # (puts the repository on sys.path)
 
 
 def main():
@@ -51,30 +25,13 @@ def main():
     args = ap.parse_args()
     import numpy as np
     import torch
-    if os.environ.get("SVK_TOOL_LIB"):      # A/B: time another build of the library in the same process layout
-        from speaker_verification_amd import _lib
-        _lib.LIB_PATH = os.environ["SVK_TOOL_LIB"]
-        lib = _lib.C.CDLL(_lib.LIB_PATH)
-        _lib.VERSION = lib.svk_version()
-        _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(lib, k)}
-    from speaker_verification_amd import _lib
+    _lib, lib = T.load_lib()
     from speaker_verification_amd.engine import get_engine
     from speaker_verification_amd.pipeline import speaker_segments
     eng = get_engine(0)
-    lib = _lib.load()
     F = torch.nn.functional
     n, dim, n_spk = args.rows, args.dim, args.speakers
-    res = {"lib": _lib.LIB_PATH, "version": int(lib.svk_version()), "csrc_sha": _lib.provenance()["csrc_sha"], "rows": n,
-           "dim": dim, "speakers": n_spk, "reps": args.reps, "ms": {}, "spread_ms": {}, "bytes": {}, "tb_s": {}, "ratio": {}}
-
-    def put(name, times, nbytes=None):
-        med = times[len(times) // 2]
-        res["ms"][name] = round(med, 4)
-        res["spread_ms"][name] = [round(times[0], 4), round(times[-1], 4)]
-        if nbytes:
-            res["bytes"][name] = int(nbytes)
-            res["tb_s"][name] = round(nbytes / (med * 1e-3) / 1e12, 3)
-        return med
+    res = T.header(_lib, lib, rows=n, dim=dim, speakers=n_spk, reps=args.reps, ms={}, spread_ms={}, bytes={}, tb_s={}, ratio={})
 
     g = torch.Generator(device=eng.device).manual_seed(1)
     x = torch.randn(n, dim, device=eng.device, generator=g) + 3.0
@@ -91,10 +48,10 @@ def main():
         d = xd - mean[cls]
         return mean, d.T @ d
 
-    times = alternated(torch, {"class_scatter": lambda: eng.class_scatter(x, start, row_index=index, l2_rows=True),
-                               "torch_scatter": torch_scatter}, args.reps, args.warmup)
-    ours = put("class_scatter", times["class_scatter"], n * (3 * dim * 4 + 2 * 8 + 3 * 8))
-    ref = put("torch_scatter", times["torch_scatter"])
+    times = T.alternated(torch, {"class_scatter": lambda: eng.class_scatter(x, start, row_index=index, l2_rows=True),
+                                 "torch_scatter": torch_scatter}, args.reps, args.warmup)
+    ours = T.put("class_scatter", times["class_scatter"], n * (3 * dim * 4 + 2 * 8 + 3 * 8))
+    ref = T.put("torch_scatter", times["torch_scatter"])
     res["ratio"]["torch_scatter/class_scatter"] = round(ref / ours, 3)
     sw, sw_t = eng.class_scatter(x, start, row_index=index, l2_rows=True)[1], torch_scatter()[1]
     res["scatter_max_rel_diff"] = float(((sw - sw_t).abs().max() / sw_t.abs().max()).item())
@@ -104,13 +61,13 @@ def main():
         w = torch.randn(dim, out_dim, device=eng.device, generator=g) / dim ** 0.5
         fns = {"project": lambda: eng.embedding_project(x, mean=mu, w=w, l2_in=True, l2_out=True),
                "torch_project": lambda: F.normalize((F.normalize(x, dim=1) - mu) @ w, dim=1)}
-        times = alternated(torch, fns, args.reps, args.warmup)
+        times = T.alternated(torch, fns, args.reps, args.warmup)
         tag = "_%d" % out_dim
-        ours = put("project" + tag, times["project"], n * (dim + out_dim) * 4 + dim * out_dim * 4)
-        ref = put("torch_project" + tag, times["torch_project"])
+        ours = T.put("project" + tag, times["project"], n * (dim + out_dim) * 4 + dim * out_dim * 4)
+        ref = T.put("torch_project" + tag, times["torch_project"])
         res["ratio"]["torch_project/project" + tag] = round(ref / ours, 3)
         res["project_max_diff" + tag] = float((fns["project"]() - fns["torch_project"]()).abs().max().item())
-    res["hbm_peak_tb_s"] = HBM_PEAK / 1e12
+    res["hbm_peak_tb_s"] = T.HBM_PEAK / 1e12
     print(json.dumps(res))
 
 

@@ -14,35 +14,9 @@ targets (10 %) ~ N(2, 1), non-targets ~ N(-1, 1.5), further systems noisy affine
 SVK_TOOL_LIB=path/to/libsvk.so times another build.  One JSON line on stdout."""
 import argparse
 import json
-import os
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-HBM_PEAK = 8.0e12          # MI355X HBM3E, spec (6.3 TB/s is the measured copy rate)
-
-
-def one(torch, fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
-def alternated(torch, fns, reps, warmup):
-    """{name: sorted times in ms}: the functions take turns, call by call, so that clocks and cache state drift for all alike"""
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in fns}
-    for _ in range(reps):
-        for name, fn in fns.items():
-            times[name].append(one(torch, fn))
-    return {name: sorted(v) for name, v in times.items()}
+import _timing as T          # (puts the repository on sys.path)
 
 
 def main():
@@ -57,30 +31,13 @@ def main():
     import numpy as np
     import torch
     import torch.nn.functional as F
-    if os.environ.get("SVK_TOOL_LIB"):      # A/B: time another build of the library in the same process layout
-        from speaker_verification_amd import _lib
-        _lib.LIB_PATH = os.environ["SVK_TOOL_LIB"]
-        lib = _lib.C.CDLL(_lib.LIB_PATH)
-        _lib.VERSION = lib.svk_version()
-        _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(lib, k)}
-    from speaker_verification_amd import _lib
+    _lib, lib = T.load_lib()
     from speaker_verification_amd.calibration import Calibration, logit
     from speaker_verification_amd.engine import get_engine
     eng = get_engine(0)
-    lib = _lib.load()
     n, p = args.n, args.p_target
     systems = [int(v) for v in args.systems.split(",")]
-    res = {"lib": _lib.LIB_PATH, "version": int(lib.svk_version()), "csrc_sha": _lib.provenance()["csrc_sha"], "n": n,
-           "reps": args.reps, "ms": {}, "spread_ms": {}, "bytes": {}, "tb_s": {}, "ratio": {}}
-
-    def put(name, times, nbytes=None):
-        med = times[len(times) // 2]
-        res["ms"][name] = round(med, 4)
-        res["spread_ms"][name] = [round(times[0], 4), round(times[-1], 4)]
-        if nbytes:
-            res["bytes"][name] = int(nbytes)
-            res["tb_s"][name] = round(nbytes / (med * 1e-3) / 1e12, 3)
-        return med
+    res = T.header(_lib, lib, n=n, reps=args.reps, ms={}, spread_ms={}, bytes={}, tb_s={}, ratio={})
 
     g = torch.Generator(device=eng.device).manual_seed(1)
     target = torch.rand(n, device=eng.device, generator=g) < 0.1
@@ -125,12 +82,12 @@ def main():
                "torch_value": lambda: torch_stats(sc, w_dev, True),
                "apply": lambda: eng.calibration_apply(sc, w_host, out=out),
                "torch_apply": lambda: (w_dev[:-1, None] * sc.double()).sum(0).add_(w_dev[-1]).float()}
-        times = alternated(torch, fns, args.reps, args.warmup)
+        times = T.alternated(torch, fns, args.reps, args.warmup)
         tag = "_%d" % d
         for name in ("stats", "value", "apply"):
             nbytes = n * (4 * d + (4 if name == "apply" else 1))
-            ours = put(name + tag, times[name], nbytes)
-            ref = put("torch_" + name + tag, times["torch_" + name])
+            ours = T.put(name + tag, times[name], nbytes)
+            ref = T.put("torch_" + name + tag, times["torch_" + name])
             res["ratio"]["torch_%s/%s%s" % (name, name, tag)] = round(ref / ours, 3)
         # the two routes on the same operands
         mine = eng.calibration_stats(sc, labels, w_host, tau, cw)
@@ -146,10 +103,10 @@ def main():
         cal = Calibration(p_target=p).fit(planes[0], labels, engine=eng)
         torch.cuda.synchronize()
         fit_times.append((time.perf_counter() - t0) * 1e3)
-    put("fit", sorted(fit_times[1:]))
+    T.put("fit", sorted(fit_times[1:]))
     res["fit"] = {"n_iter": cal.n_iter_, "converged": bool(cal.converged_), "weights": [float(v) for v in cal.weights_],
                   "objective": cal.objective_}
-    res["hbm_peak_tb_s"] = HBM_PEAK / 1e12
+    res["hbm_peak_tb_s"] = T.HBM_PEAK / 1e12
     print(json.dumps(res))
 
 

@@ -7,53 +7,25 @@ SVK_TOOL_LIB=path/to/libsvk.so times another build (e.g. under build_variants/);
 missing.  One JSON line on stdout."""
 import json
 import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import _timing as T          # (puts the repository on sys.path)
 
 N, D = 148642, 128
-
-
-def timed(torch, fn, reps, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    times.sort()
-    return times[len(times) // 2]
 
 
 def main():
     import torch
     import torch.nn.functional as F
-    if os.environ.get("SVK_TOOL_LIB"):
-        from speaker_verification_amd import _lib
-        _lib.LIB_PATH = os.environ["SVK_TOOL_LIB"]
-        lib = _lib.C.CDLL(_lib.LIB_PATH)
-        _lib.VERSION = lib.svk_version()
-        _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(lib, k)}
-    from speaker_verification_amd import _lib
+    _lib, lib = T.load_lib()
     from speaker_verification_amd.engine import get_engine
     eng = get_engine(0)
     reps = int(os.environ.get("SVK_HEAD_REPS", "10"))
     g = torch.Generator(device=eng.device).manual_seed(3)
     emb = torch.randn(N, D, device=eng.device, generator=g)
-    res = {"lib": _lib.LIB_PATH, "version": int(_lib.load().svk_version()), "n": N, "ms": {}, "tf_s": {}, "tb_s": {}}
-    have = hasattr(_lib.load(), "svk_c3d2_head")
+    res = T.header(_lib, lib, sha=False, n=N, ms={}, tf_s={}, tb_s={})
+    have = hasattr(lib, "svk_c3d2_head")
     if not have:
         res["missing"] = ["svk_c3d2_head"]
-
-    def put(name, ms, flop, nbytes):
-        res["ms"][name] = round(ms, 4)
-        res["tf_s"][name] = round(flop / (ms * 1e-3) / 1e12, 2)
-        res["tb_s"][name] = round(nbytes / (ms * 1e-3) / 1e12, 3)
 
     for n_labels in (1211, 100):
         w = 0.1 * torch.randn(n_labels, D, device=eng.device, generator=g)
@@ -67,16 +39,16 @@ def main():
             for probs in (True, False):
                 for k in (1, 5):
                     name = "head_%d_%s_k%d" % (n_labels, "probs" if probs else "noprobs", k)
-                    put(name, timed(torch, lambda: eng.c3d2_head(emb, tables, probs=probs, k=k), reps), 3 * gemm,
-                        base + (probs_bytes if probs else 0) + N * k * 4)
+                    T.put(name, T.timed(torch, lambda: eng.c3d2_head(emb, tables, probs=probs, k=k), reps),
+                            base + (probs_bytes if probs else 0) + N * k * 4, 3 * gemm)
 
         def torch_head(k):
             p = F.softmax(F.linear(F.prelu(emb, slope), w, b), dim=1)
             return p, (torch.argmax(p, 1) if k == 1 else torch.topk(p, k, 1)[1])
         # logits written and read by softmax, probabilities written and read by the argmax / topk
         for k in (1, 5):
-            put("torch_%d_k%d" % (n_labels, k), timed(torch, lambda: torch_head(k), reps), gemm,
-                base + 4 * probs_bytes + N * k * 8)
+            T.put("torch_%d_k%d" % (n_labels, k), T.timed(torch, lambda: torch_head(k), reps),
+                    base + 4 * probs_bytes + N * k * 8, gemm)
     print(json.dumps(res))
 
 

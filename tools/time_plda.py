@@ -14,35 +14,10 @@ Medians of --reps calls after --warmup; the spread (min .. max) is reported besi
 SVK_TOOL_LIB=path/to/libsvk.so times another build.  One JSON line on stdout."""
 import argparse
 import json
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import _timing as T          # (puts the repository on sys.path)
 
-HBM_PEAK = 8.0e12          # MI355X HBM3E, spec (6.3 TB/s is the measured copy rate)
 F32_MATRIX_PEAK = 157.3e12
-
-
-def one(torch, fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
-def alternated(torch, fns, reps, warmup):
-    """{name: sorted times in ms}: the functions take turns, call by call, so that clocks and cache state drift for all alike"""
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in fns}
-    for _ in range(reps):
-        for name, fn in fns.items():
-            times[name].append(one(torch, fn))
-    return {name: sorted(v) for name, v in times.items()}
 
 
 def main():
@@ -56,33 +31,13 @@ def main():
     args = ap.parse_args()
     import numpy as np
     import torch
-    if os.environ.get("SVK_TOOL_LIB"):      # A/B: time another build of the library in the same process layout
-        from speaker_verification_amd import _lib
-        _lib.LIB_PATH = os.environ["SVK_TOOL_LIB"]
-        lib = _lib.C.CDLL(_lib.LIB_PATH)
-        _lib.VERSION = lib.svk_version()
-        _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(lib, k)}
-    from speaker_verification_amd import _lib
+    _lib, lib = T.load_lib()
     from speaker_verification_amd import plda as plda_mod
     from speaker_verification_amd.engine import get_engine
     eng = get_engine(0)
-    lib = _lib.load()
     n, ns, dim = args.rows, args.speakers, args.dim
-    res = {"lib": _lib.LIB_PATH, "version": int(lib.svk_version()), "csrc_sha": _lib.provenance()["csrc_sha"], "rows": n,
-           "speakers": ns, "dim": dim, "reps": args.reps, "ms": {}, "spread_ms": {}, "bytes": {}, "tb_s": {}, "flop": {},
-           "tf_s": {}, "ratio": {}}
-
-    def put(name, times, nbytes=None, flop=None):
-        med = times[len(times) // 2]
-        res["ms"][name] = round(med, 4)
-        res["spread_ms"][name] = [round(times[0], 4), round(times[-1], 4)]
-        if nbytes:
-            res["bytes"][name] = int(nbytes)
-            res["tb_s"][name] = round(nbytes / (med * 1e-3) / 1e12, 3)
-        if flop:
-            res["flop"][name] = int(flop)
-            res["tf_s"][name] = round(flop / (med * 1e-3) / 1e12, 2)
-        return med
+    res = T.header(_lib, lib, rows=n, speakers=ns, dim=dim, reps=args.reps, ms={}, spread_ms={}, bytes={}, tb_s={}, flop={},
+                   tf_s={}, ratio={})
 
     g = torch.Generator(device=eng.device).manual_seed(1)
     psi_host = np.sort(np.random.default_rng(2).random(dim) ** 3 * 100.0)[::-1].copy()
@@ -100,12 +55,12 @@ def main():
            "cosine": lambda: eng.cosine_scores(v, u),
            "plda_counts": lambda: eng.plda_scores(v, u, psi, counts),
            "torch": lambda: (v @ b_t.T).add_(s_t[:, None]).add_(t_t[None, :])}
-    times = alternated(torch, fns, args.reps, args.warmup)
+    times = T.alternated(torch, fns, args.reps, args.warmup)
     out_bytes, in_bytes = 4 * n * ns, 4 * (n + ns) * dim
-    ours = put("plda", times["plda"], out_bytes + in_bytes + 4 * n * dim + 3 * 4 * ns * dim, 2 * n * ns * dim)
-    cos = put("cosine", times["cosine"], out_bytes + in_bytes, 2 * n * ns * dim)
-    with_counts = put("plda_counts", times["plda_counts"], out_bytes + in_bytes + 3 * 4 * n * dim + 5 * 4 * ns * dim, 4 * n * ns * dim)
-    ref = put("torch", times["torch"], 5 * out_bytes + in_bytes, 2 * n * ns * dim)
+    ours = T.put("plda", times["plda"], out_bytes + in_bytes + 4 * n * dim + 3 * 4 * ns * dim, 2 * n * ns * dim)
+    cos = T.put("cosine", times["cosine"], out_bytes + in_bytes, 2 * n * ns * dim)
+    with_counts = T.put("plda_counts", times["plda_counts"], out_bytes + in_bytes + 3 * 4 * n * dim + 5 * 4 * ns * dim, 4 * n * ns * dim)
+    ref = T.put("torch", times["torch"], 5 * out_bytes + in_bytes, 2 * n * ns * dim)
     res["ratio"]["plda/cosine"] = round(ours / cos, 3)
     res["ratio"]["plda_counts/plda"] = round(with_counts / ours, 3)
     res["ratio"]["torch/plda"] = round(ref / ours, 3)
@@ -120,14 +75,14 @@ def main():
         fns = {"plda_pairs": lambda: eng.plda_pair_scores(x, x, ia, ib, psi),
                "cosine_pairs": lambda: eng.pair_scores(x, x, ia, ib),
                "plda_pairs_counts": lambda: eng.plda_pair_scores(x, x, ia, ib, psi, counts_b=cnt)}
-        times = alternated(torch, fns, args.reps, args.warmup)
+        times = T.alternated(torch, fns, args.reps, args.warmup)
         tag = "_%d" % n_trials
         nbytes = n_trials * (2 * dim * 4 + 2 * 8 + 4)
-        a = put("plda_pairs" + tag, times["plda_pairs"], nbytes)
-        b = put("cosine_pairs" + tag, times["cosine_pairs"], nbytes)
-        put("plda_pairs_counts" + tag, times["plda_pairs_counts"], nbytes + 4 * n_trials)
+        a = T.put("plda_pairs" + tag, times["plda_pairs"], nbytes)
+        b = T.put("cosine_pairs" + tag, times["cosine_pairs"], nbytes)
+        T.put("plda_pairs_counts" + tag, times["plda_pairs_counts"], nbytes + 4 * n_trials)
         res["ratio"]["plda_pairs/cosine_pairs" + tag] = round(a / b, 3)
-    res["hbm_peak_tb_s"] = HBM_PEAK / 1e12
+    res["hbm_peak_tb_s"] = T.HBM_PEAK / 1e12
     res["f32_matrix_peak_tf_s"] = F32_MATRIX_PEAK / 1e12
     print(json.dumps(res))
 

@@ -8,28 +8,10 @@ lacks are reported as missing.  SVK_ROC_SKIP_E2E=1 leaves out the end-to-end pai
 One JSON line on stdout."""
 import json
 import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import _timing as T          # (puts the repository on sys.path)
 
-HBM_PEAK = 8.0e12          # MI355X HBM3E, spec (6.3 TB/s is the measured copy rate)
 NT, NS, D = 148642, 1211, 128
-
-
-def timed(torch, fn, reps, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    times.sort()
-    return times[len(times) // 2]
 
 
 def sort_bytes(n, passes):
@@ -41,13 +23,8 @@ def sort_bytes(n, passes):
 def main():
     import numpy as np
     import torch
-    if os.environ.get("SVK_TOOL_LIB"):      # A/B: time another build of the library in the same process layout
-        from speaker_verification_amd import _lib
-        _lib.LIB_PATH = os.environ["SVK_TOOL_LIB"]
-        lib = _lib.C.CDLL(_lib.LIB_PATH)
-        _lib.VERSION = lib.svk_version()
-        _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(lib, k)}
-    from speaker_verification_amd import _lib, evaluation
+    _lib, lib = T.load_lib()
+    from speaker_verification_amd import evaluation
     from speaker_verification_amd.engine import get_engine
     eng = get_engine(0)
     reps = int(os.environ.get("SVK_ROC_REPS", "10"))
@@ -60,13 +37,7 @@ def main():
     labels[torch.arange(NT, device=eng.device), true.long()] = 1
     n = NT * NS
     sc, lb = scores.reshape(-1), labels.reshape(-1)
-    res = {"lib": _lib.LIB_PATH, "version": int(_lib.load().svk_version()), "n_pairs": n, "ms": {}, "bytes": {}, "tb_s": {}}
-
-    def put(name, ms, nbytes=None):
-        res["ms"][name] = round(ms, 4)
-        if nbytes:
-            res["bytes"][name] = int(nbytes)
-            res["tb_s"][name] = round(nbytes / (ms * 1e-3) / 1e12, 3)
+    res = T.header(_lib, lib, sha=False, n_pairs=n, ms={}, bytes={}, tb_s={})
 
     # passes the sort runs on these scores: a digit that is the same for every key is skipped
     keys = sc.view(torch.int32).cpu().numpy().view(np.uint32)
@@ -75,21 +46,21 @@ def main():
     passes = sum(int(np.unique((keys >> (8 * p)) & 255).size > 1) for p in range(4)) or 1
     res["sort_passes"] = passes
     point_bytes = n * (5 + 5 + 8)        # (label, key) twice -- part and emit pass -- and the points written
-    put("roc_eer", timed(torch, lambda: eng.roc_eer(sc, lb), reps), sort_bytes(n, passes) + point_bytes)
-    if hasattr(_lib.load(), "svk_roc_k"):
+    T.put("roc_eer", T.timed(torch, lambda: eng.roc_eer(sc, lb), reps), sort_bytes(n, passes) + point_bytes)
+    if hasattr(lib, "svk_roc_k"):
         for k in (1, 10):
             for curve in (False, True):
                 extra = n * 8 * 2 if curve else n * 8   # the curve: points read by the count and the emit pass
-                put(f"roc_k{k}{'_curve' if curve else ''}", timed(torch, lambda: eng.roc_k(sc, lb, k=k, curve=curve), reps),
-                    sort_bytes(n, passes) + point_bytes + extra)
-        put("top1", timed(torch, lambda: eng.top1(scores, true), reps), n * 4 + NT * 8)
-        put("top1_labels", timed(torch, lambda: eng.top1(scores, true, want_labels=True), reps), n * 5 + NT * 8)
+                T.put(f"roc_k{k}{'_curve' if curve else ''}", T.timed(torch, lambda: eng.roc_k(sc, lb, k=k, curve=curve), reps),
+                      sort_bytes(n, passes) + point_bytes + extra)
+        T.put("top1", T.timed(torch, lambda: eng.top1(scores, true), reps), n * 4 + NT * 8)
+        T.put("top1_labels", T.timed(torch, lambda: eng.top1(scores, true, want_labels=True), reps), n * 5 + NT * 8)
     else:
         res["missing"] = ["svk_roc_k", "svk_top1"]
-    put("torch_sort", timed(torch, lambda: torch.sort(sc, descending=True), reps))
+    T.put("torch_sort", T.timed(torch, lambda: torch.sort(sc, descending=True), reps))
 
     # end to end on in-memory embeddings: cosine scores -> top-1 -> labels -> ROC (host: sklearn on float64 copies)
-    if hasattr(_lib.load(), "svk_roc_k") and not os.environ.get("SVK_ROC_SKIP_E2E"):
+    if hasattr(lib, "svk_roc_k") and not os.environ.get("SVK_ROC_SKIP_E2E"):
         speaker_ids = [f"id{j:05d}" for j in range(NS)]
         test_ids = [speaker_ids[j] for j in true.cpu().numpy()]
 
@@ -105,11 +76,11 @@ def main():
         import io
         import time
         with contextlib.redirect_stdout(io.StringIO()):
-            put("evaluate_device", timed(torch, lambda: end_to_end(True), 3, warmup=1))
+            T.put("evaluate_device", T.timed(torch, lambda: end_to_end(True), 3, warmup=1))
             t0 = time.perf_counter()
             end_to_end(False)
             res["ms"]["evaluate_host"] = round((time.perf_counter() - t0) * 1e3, 1)
-    res["hbm_peak_tb_s"] = HBM_PEAK / 1e12
+    res["hbm_peak_tb_s"] = T.HBM_PEAK / 1e12
     print(json.dumps(res))
 
 

@@ -10,34 +10,8 @@ product's 2 n_query n_gallery dim flops as well.  Medians of --reps calls after 
 SVK_TOOL_LIB=path/to/libsvk.so times another build.  One JSON line on stdout."""
 import argparse
 import json
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-HBM_PEAK = 8.0e12          # MI355X HBM3E, spec (6.3 TB/s is the measured copy rate)
-
-
-def one(torch, fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
-def alternated(torch, fns, reps, warmup):
-    """{name: sorted times in ms}: the functions take turns, call by call, so that clocks and cache state drift for all alike"""
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in fns}
-    for _ in range(reps):
-        for name, fn in fns.items():
-            times[name].append(one(torch, fn))
-    return {name: sorted(v) for name, v in times.items()}
+import _timing as T          # (puts the repository on sys.path)
 
 
 def main():
@@ -50,31 +24,13 @@ def main():
     ap.add_argument("--matrix-limit-gb", type=float, default=64.0, help="largest score matrix the existing route is timed with")
     args = ap.parse_args()
     import torch
-    if os.environ.get("SVK_TOOL_LIB"):      # A/B: time another build of the library in the same process layout
-        from speaker_verification_amd import _lib
-        _lib.LIB_PATH = os.environ["SVK_TOOL_LIB"]
-        lib = _lib.C.CDLL(_lib.LIB_PATH)
-        _lib.VERSION = lib.svk_version()
-        _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(lib, k)}
-    from speaker_verification_amd import _lib
+    _lib, lib = T.load_lib()
     from speaker_verification_amd.engine import get_engine
     eng = get_engine(0)
-    lib = _lib.load()
-    res = {"lib": _lib.LIB_PATH, "version": int(lib.svk_version()), "csrc_sha": _lib.provenance()["csrc_sha"], "dim": args.dim,
-           "reps": args.reps, "ms": {}, "spread_ms": {}, "bytes": {}, "tb_s": {}, "tf_s": {}, "ratio": {}, "missing": []}
+    res = T.header(_lib, lib, dim=args.dim, reps=args.reps, ms={}, spread_ms={}, bytes={}, tb_s={}, tf_s={}, ratio={},
+                   missing=[])
     if not hasattr(lib, "svk_cosine_topk"):
         res["missing"].append("svk_cosine_topk")
-
-    def put(name, times, nbytes=None, flops=None):
-        med = times[len(times) // 2]
-        res["ms"][name] = round(med, 4)
-        res["spread_ms"][name] = [round(times[0], 4), round(times[-1], 4)]
-        if nbytes:
-            res["bytes"][name] = int(nbytes)
-            res["tb_s"][name] = round(nbytes / (med * 1e-3) / 1e12, 3)
-        if flops:
-            res["tf_s"][name] = round(flops / (med * 1e-3) / 1e12, 2)
-        return med
 
     g = torch.Generator(device=eng.device).manual_seed(1)
     made = {}
@@ -106,19 +62,19 @@ def main():
                     scores.fill_diagonal_(float("-inf"))
                 return eng.top1(scores, true) if k == 1 else torch.topk(scores, k, dim=1)
             fns["matrix"] = matrix_route
-        times = alternated(torch, fns, args.reps, args.warmup)
+        times = T.alternated(torch, fns, args.reps, args.warmup)
         ours = None
         if "topk" in times:
-            ours = put("topk_" + tag, times["topk"], 4 * args.dim * (nq + (0 if own else ng)) + 12 * nq * k, flops)
+            ours = T.put("topk_" + tag, times["topk"], 4 * args.dim * (nq + (0 if own else ng)) + 12 * nq * k, flops)
         if "matrix" in times:
-            ref = put("matrix_" + tag, times["matrix"], None, flops)
+            ref = T.put("matrix_" + tag, times["matrix"], None, flops)
             if ours:
                 res["ratio"]["matrix/topk_" + tag] = round(ref / ours, 3)
         else:
             res["ms"]["matrix_" + tag] = None                      # the matrix does not fit
         if not own:
             del gallery
-    res["hbm_peak_tb_s"] = HBM_PEAK / 1e12
+    res["hbm_peak_tb_s"] = T.HBM_PEAK / 1e12
     print(json.dumps(res))
 
 
