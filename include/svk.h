@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_calibration_stats, svk_calibration_stats_workspace_bytes, svk_calibration_apply (score calibration and fusion: the statistics of a prior-weighted logistic regression in one pass, and the affine map); earlier under the same number: + svk_plda_scores, svk_plda_scores_workspace_bytes, svk_plda_pair_scores (PLDA log-likelihood ratios: the score matrix on the f32 matrix pipe, trial lists in float64); earlier under the same number: svk_c3d2_stage2 runs as one kernel and no longer touches d_act2, which may be NULL (same results, bit for bit); earlier under the same number: + svk_class_scatter, svk_class_scatter_workspace_bytes, svk_embedding_project (the embedding back end: class statistics in float64 and centre / project / length-normalise in one pass); earlier additions under the same number: + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
+#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_cohort_moments, svk_score_norm, svk_score_norm_pairs (adaptive score normalisation: the top-K cohort moments of every row by an exact radix select, and Z- / T- / S-norm from them); earlier under the same number: + svk_calibration_stats, svk_calibration_stats_workspace_bytes, svk_calibration_apply (score calibration and fusion: the statistics of a prior-weighted logistic regression in one pass, and the affine map); earlier under the same number: + svk_plda_scores, svk_plda_scores_workspace_bytes, svk_plda_pair_scores (PLDA log-likelihood ratios: the score matrix on the f32 matrix pipe, trial lists in float64); earlier under the same number: svk_c3d2_stage2 runs as one kernel and no longer touches d_act2, which may be NULL (same results, bit for bit); earlier under the same number: + svk_class_scatter, svk_class_scatter_workspace_bytes, svk_embedding_project (the embedding back end: class statistics in float64 and centre / project / length-normalise in one pass); earlier additions under the same number: + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
 
 typedef enum svk_status {
   SVK_OK = 0,
@@ -575,6 +575,77 @@ int svk_calibration_stats(svk_ctx* ctx, const float* d_scores, int32_t n_sys, in
  * weight. */
 int svk_calibration_apply(svk_ctx* ctx, const float* d_scores, int32_t n_sys, int64_t plane_stride, int64_t n,
                           const double* h_weights, float* d_out);
+
+/* ---- score normalisation (csrc/snorm.hip) -------------------------------------------------------
+ * The step between the raw score and the calibration: the shift and scale of a row's (an utterance's, a model's) impostor
+ * scores, estimated on a cohort, are taken out of its trial scores (Z-, T-, S-norm; adaptive with top_k).  The reference has
+ * no score normalisation.  All three entries are asynchronous on the context's stream and take no workspace.
+ *
+ * svk_cohort_moments: d_scores f32 [n_rows][row_stride], 4-byte aligned, the first n_cohort values of a row being that row's
+ * scores against the cohort (svk_cosine_scores or svk_plda_scores: the caller's choice).  For every row:
+ *   candidates    the finite scores; NaN and +-inf never are.  -0.0 counts as +0.0 and enters the sums as +0.0
+ *   selection     m = min(top_k, candidates), top_k == 0 meaning all.  With v* the m-th largest candidate, the selected MULTISET
+ *                 is every candidate strictly above v* and as many copies of v* as it takes to reach m: equal values are
+ *                 interchangeable, no index order exists and none influences a bit.  v* is found exactly, by a radix select on
+ *                 the order-preserving 32-bit key of the scores (four 8-bit digits over an LDS histogram); nothing is sorted
+ *   d_moments     float64 [n_rows][2] = {mean, std}: mean = S / m, std = sqrt(sum (x - mean)^2 / m) (population form, two-pass,
+ *                 from the centred values).  m == 0 gives {NaN, NaN}.  When all m selected values are equal (nothing lies
+ *                 above v*) the mean is v* exactly and std is +0.0 exactly: a case of its own, no arithmetic runs
+ *   d_used        int32 [n_rows] = m, or NULL;   d_kth  f32 [n_rows] = v* (NaN when m == 0), or NULL
+ *   team          ONE team of T threads per row: T = 64 (a wave; four rows share a workgroup) for n_cohort <= 2048, T = 256 above
+ *   order of additions   a function of n_cohort alone, the same for S and for the centred squares: lane l of the team adds,
+ *                 from 0.0, the selected values above v* among its columns l, l + T, l + 2 T, .. in column order (a column
+ *                 that is not selected contributes nothing: ceil(n_cohort / T) additions at most); a 64-lane xor butterfly (32,
+ *                 16, .., 1: 6 additions); for T = 256 the 4 wave sums from 0.0 in wave order (4); then ONE term for the c
+ *                 copies of v*, (double) c * v* (for the squares (double) c * ((v* - mean) * (v* - mean))).  Every product,
+ *                 difference and sum is float64 and rounded on its own.  It does not depend on n_rows, the row's position, top_k
+ *                 or the launch geometry; no floating-point atomics: a row computed alone gives the bits it gives inside a
+ *                 batch, runs are bit-identical, and any top_k >= n_cohort gives the bits of top_k == 0
+ *   residency     a row of up to 16 384 columns (ROW_LDS_MAX) is read from memory ONCE and kept in LDS (as keys, 64 KiB at
+ *                 most: two workgroups to a CU) for the four select passes and the two moment passes; a longer row passes
+ *                 through the same LDS buffer 16 384 columns at a time in each of the six passes (re-read through L2).  16-byte
+ *                 loads when row_stride % 4 == 0 and d_scores is 16-byte aligned, 4-byte loads otherwise.  A lane owns the
+ *                 same columns in the same order on every path: the same bits
+ *   accuracy      with x the m selected values, d = x - (their exact mean), ref and ref_var their exact mean and variance, and
+ *                 A = ceil(n_cohort / T) + 6 + (T == 256 ? 4 : 0) + 1 the additions on the longest path:
+ *                   |mean - ref|      <= dm = (A + 2) 2^-52 sum |x| / m                 (+ 2: the product c v* and the division)
+ *                   |std^2 - ref_var| <= (A + 4) 2^-52 sum d^2 / m + 2 dm sum |d| / m + dm^2 + 2^-51 ref_var
+ *                 (+ 4: the difference, the square, the product with c and the division; the terms in dm: the centre is the
+ *                 computed mean, not the exact one; 2^-51 ref_var: the square root, squared again by whoever compares.
+ *                 tests/test_cohort_moments.py holds every row to it)
+ * 1 <= n_cohort < 2^31; element offsets are 64-bit (n_rows * row_stride passes 2^31 at corpus size).  n_rows == 0 launches
+ * nothing.  SVK_ERR_BAD_ARG: NULL context or buffer, negative n_rows, n_cohort < 1, top_k < 0, row_stride < n_cohort,
+ * misalignment (f32 / int32: 4 bytes; float64: 8). */
+int svk_cohort_moments(svk_ctx* ctx, const float* d_scores, int64_t n_rows, int32_t n_cohort, int64_t row_stride,
+                       int32_t top_k, double* d_moments, int32_t* d_used, float* d_kth);
+
+/* Z-, T- and S-norm of a score matrix from ONE expression.  d_scores f32 [n_rows][row_stride], n_cols scores per row; d_out f32
+ * [n_rows][out_stride]; d_row_moments float64 [n_rows][2], d_col_moments float64 [n_cols][2] = {mean, std} as svk_cohort_moments
+ * writes them, either may be NULL:
+ *   both given    out = f32(0.5 * ((s - mu_r) / sd_r + (s - mu_c) / sd_c))                       (S-norm)
+ *   one given     out = f32((s - mu) / sd) with that table: rows -> T-norm (the test side), columns -> Z-norm (the enrolled side)
+ *   both NULL     SVK_ERR_BAD_ARG
+ * All arithmetic is float64; each difference, quotient, sum and the product with 0.5 is rounded on its own, in the order
+ * written, and the result is rounded to f32 once:  |out - ref| <= 2^-24 |ref| + 4 * 2^-52 (|t_r| + |t_c|), t the quotients.
+ * A zero or NaN std and a non-finite score give what IEEE arithmetic gives; nothing is clamped, nothing is counted.
+ * d_out may be d_scores itself, in place; out_stride must then equal row_stride (anything else is SVK_ERR_BAD_ARG).  16-byte loads and stores when both matrices are
+ * 16-byte aligned and both strides are multiples of 4, 4-byte otherwise: the same bits.  n_rows == 0 or n_cols == 0 launches
+ * nothing.  SVK_ERR_BAD_ARG: NULL context or buffer, negative size, n_cols >= 2^31, a stride below n_cols, misalignment (f32: 4
+ * bytes; float64: 8). */
+int svk_score_norm(svk_ctx* ctx, const float* d_scores, int64_t n_rows, int64_t n_cols, int64_t row_stride,
+                   const double* d_row_moments, const double* d_col_moments, float* d_out, int64_t out_stride);
+
+/* The same expression for a TRIAL LIST: d_out[p] is svk_score_norm's entry for the score d_scores[p] with the row moments
+ * d_mom_a[d_idx_a[p]] and the column moments d_mom_b[d_idx_b[p]], bit for bit; the tables (float64 [n_a][2], [n_b][2]) are
+ * indexed as svk_pair_scores indexes its matrices.  A table may be NULL (that side is left out, and only then may its index
+ * list be NULL too); both NULL is SVK_ERR_BAD_ARG.  An index outside its table is the caller's error: nothing is read, that
+ * trial's output is NaN and *d_bad_count (int32, may be NULL, the caller zeroes it) goes up by one.  d_out may be d_scores.
+ * 16-byte loads and stores of the scores when d_scores and d_out are 16-byte aligned, 4-byte otherwise: the same bits.
+ * n == 0 launches nothing.  SVK_ERR_BAD_ARG: NULL context or buffer, negative size, misalignment (f32 / int32: 4 bytes;
+ * float64 / int64: 8). */
+int svk_score_norm_pairs(svk_ctx* ctx, const float* d_scores, int64_t n, const double* d_mom_a, int64_t n_a,
+                         const double* d_mom_b, int64_t n_b, const int64_t* d_idx_a, const int64_t* d_idx_b,
+                         float* d_out, int32_t* d_bad_count);
 
 /* ---- the first block of the embedding network ----------------------------------------------------
  * model.py:110-117 + :141-150 (C3D2): cube (utils.py:351-379) -> conv1_1 (1 -> 16, kernel (3,1,5)) -> BN -> PReLU

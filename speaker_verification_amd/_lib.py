@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsvk.so")
 
 SVK_OK = 0
-VERSION = 114                      # include/svk.h SVK_VERSION (0.1.12: + svk_calibration_stats, svk_calibration_apply, number unchanged; + svk_plda_scores, svk_plda_pair_scores, number unchanged; + svk_class_scatter, svk_embedding_project, number unchanged; + svk_cosine_topk, number unchanged; + svk_pair_scores, svk_roc_dcf, svk_decision_counts, number unchanged; + svk_c3d2_head; + the svk_delta_* entries, the *_multi first block and svk_embedding_pool, number unchanged)
+VERSION = 114                      # include/svk.h SVK_VERSION (0.1.12: + svk_cohort_moments, svk_score_norm, svk_score_norm_pairs, number unchanged; + svk_calibration_stats, svk_calibration_apply, number unchanged; + svk_plda_scores, svk_plda_pair_scores, number unchanged; + svk_class_scatter, svk_embedding_project, number unchanged; + svk_cosine_topk, number unchanged; + svk_pair_scores, svk_roc_dcf, svk_decision_counts, number unchanged; + svk_c3d2_head; + the svk_delta_* entries, the *_multi first block and svk_embedding_pool, number unchanged)
 SVK_ERR_BAD_ARG, SVK_ERR_UNSUPPORTED, SVK_ERR_HIP, SVK_ERR_NO_DEVICE, SVK_ERR_OOM, SVK_ERR_RCCL = -1, -2, -3, -4, -5, -6
 OUT_MFE, OUT_LMFE, OUT_MFCC = 0, 1, 2
 PCM_I16, PCM_F32 = 0, 1
@@ -87,6 +87,9 @@ SIGNATURES = {
     "svk_calibration_stats": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _i64, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double),
                                         _i32, _vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(_i64)]),
     "svk_calibration_apply": (C.c_int, [_vp, _vp, _i32, _i64, _i64, C.POINTER(C.c_double), _vp]),
+    "svk_cohort_moments": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp]),
+    "svk_score_norm": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64]),
+    "svk_score_norm_pairs": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "svk_top1": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, C.POINTER(_i64)]),
     "svk_l2_dist": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "svk_pair_scores": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _vp]),

@@ -871,6 +871,94 @@ class Engine:
                                              self._ptr(out)), self.ctx)
         return out.reshape(-1)
 
+    def _score_rows(self, scores, who):
+        """A score matrix as the normalisation entries read it -> f32 [n_rows, n_cols] on the device with unit stride along a
+        row.  A device f32 view whose rows are row_stride >= n_cols apart is taken as it is (no copy)."""
+        torch = _torch()
+        if not (isinstance(scores, torch.Tensor) and scores.device == self.device and scores.dtype == torch.float32
+                and scores.dim() == 2 and (scores.shape[1] <= 1 or scores.stride(1) == 1)
+                and (scores.shape[0] <= 1 or scores.stride(0) >= scores.shape[1])):
+            scores = self.to_device(scores, torch.float32)
+        if scores.dim() != 2:
+            raise ValueError("%s wants a [n_rows, n_cols] score matrix, got %s" % (who, tuple(scores.shape)))
+        return scores, (int(scores.stride(0)) if scores.shape[0] > 1 else int(scores.shape[1]))
+
+    def _moments(self, moments, n, name):
+        """An optional {mean, std} table as float64 [n, 2] on the device."""
+        if moments is None:
+            return None
+        mom = self.to_device(moments, _torch().float64)
+        if tuple(mom.shape) != (n, 2):
+            raise ValueError("%s wants float64 [%d, 2] (mean, std), got %s" % (name, n, tuple(mom.shape)))
+        return mom
+
+    def cohort_moments(self, scores, top_k=0, want_used=False, want_kth=False):
+        """svk_cohort_moments: the mean and population standard deviation of the top_k largest finite scores of every row of
+        scores [n_rows, n_cohort] (top_k = 0: of all of them) -> float64 [n_rows, 2] on the device; a row without a finite
+        score gives NaN, NaN.  With want_used or want_kth the result is (moments, used, kth): used int32 [n_rows] = the values
+        that entered, kth float32 [n_rows] = the smallest of them (None for the one not asked for)."""
+        torch = _torch()
+        sc, stride = self._score_rows(scores, "cohort_moments")
+        n_rows, n_cohort = int(sc.shape[0]), int(sc.shape[1])
+        mom = torch.empty((n_rows, 2), dtype=torch.float64, device=self.device)
+        used = torch.empty((n_rows,), dtype=torch.int32, device=self.device) if want_used else None
+        kth = torch.empty((n_rows,), dtype=torch.float32, device=self.device) if want_kth else None
+        self._stream()
+        check(self.lib.svk_cohort_moments(self.ctx, self._ptr(sc), n_rows, n_cohort, stride, int(top_k), self._ptr(mom),
+                                          self._ptr(used), self._ptr(kth)), self.ctx)
+        return (mom, used, kth) if (want_used or want_kth) else mom
+
+    def score_norm(self, scores, row_moments=None, col_moments=None, out=None):
+        """svk_score_norm: scores [n_rows, n_cols] normalised by the rows' moments (T-norm), the columns' (Z-norm) or both
+        (S-norm, the mean of the two) -> float32 [n_rows, n_cols] on the device, float64 arithmetic.  The tables are float64
+        [n_rows, 2] and [n_cols, 2] as `cohort_moments` returns them.  out: the tensor to write; it may be the scores
+        themselves (in place)."""
+        torch = _torch()
+        sc, stride = self._score_rows(scores, "score_norm")
+        n_rows, n_cols = int(sc.shape[0]), int(sc.shape[1])
+        rm, cm = self._moments(row_moments, n_rows, "row_moments"), self._moments(col_moments, n_cols, "col_moments")
+        if out is None:
+            out, out_stride = torch.empty((n_rows, n_cols), dtype=torch.float32, device=self.device), n_cols
+        else:
+            if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == (n_rows, n_cols)):
+                raise ValueError("out wants a float32 device tensor of shape %s" % ((n_rows, n_cols),))
+            kept, out_stride = self._score_rows(out, "score_norm")
+            if kept.data_ptr() != out.data_ptr():
+                raise ValueError("out wants rows of unit stride on this device")
+        self._stream()
+        check(self.lib.svk_score_norm(self.ctx, self._ptr(sc), n_rows, n_cols, stride, self._ptr(rm), self._ptr(cm),
+                                      self._ptr(out), out_stride), self.ctx)
+        return out
+
+    def score_norm_pairs(self, scores, mom_a, idx_a, mom_b, idx_b, out=None, bad_count=None):
+        """svk_score_norm_pairs: `score_norm` for a trial list -> float32 [n] on the device: trial p takes the row moments
+        mom_a[idx_a[p]] and the column moments mom_b[idx_b[p]].  A table (and then its indices) may be None.  An index outside
+        its table gives NaN at that trial and counts in bad_count (an int32 [1] device tensor the caller zeroes), if given.
+        out: the tensor to write; it may be the scores themselves."""
+        torch = _torch()
+        sc = self.to_device(scores, torch.float32).reshape(-1)
+        n = sc.numel()
+        i64 = torch.int64
+        ma = None if mom_a is None else self.to_device(mom_a, torch.float64)
+        mb = None if mom_b is None else self.to_device(mom_b, torch.float64)
+        for mom, name in ((ma, "mom_a"), (mb, "mom_b")):
+            if mom is not None and (mom.dim() != 2 or mom.shape[1] != 2):
+                raise ValueError("%s wants float64 [n, 2] (mean, std), got %s" % (name, tuple(mom.shape)))
+        ia = None if ma is None else self.to_device(idx_a, i64).reshape(-1)
+        ib = None if mb is None else self.to_device(idx_b, i64).reshape(-1)
+        if any(ix is not None and ix.numel() != n for ix in (ia, ib)):
+            raise ValueError("one index per trial and table")
+        bad_count = self._counter(bad_count, "bad_count")
+        if out is None:
+            out = torch.empty((n,), dtype=torch.float32, device=self.device)
+        else:
+            self._given_out(out, n, torch.float32, "out wants a contiguous float32 device tensor of %d elements" % n)
+        self._stream()
+        check(self.lib.svk_score_norm_pairs(self.ctx, self._ptr(sc), n, self._ptr(ma), 0 if ma is None else ma.shape[0],
+                                            self._ptr(mb), 0 if mb is None else mb.shape[0], self._ptr(ia), self._ptr(ib),
+                                            self._ptr(out), self._ptr(bad_count)), self.ctx)
+        return out.reshape(-1)
+
     def roc_k(self, scores, labels, k=1, curve=False):
         """svk_roc_k: per split of `split_step(n, k)` consecutive pairs (evaluation.py:11-33), (eer, auc), or with
         curve=True (eer, auc, fpr, tpr): sklearn's roc_curve(drop_intermediate=True) as float64 NumPy arrays, fps / fps[-1]

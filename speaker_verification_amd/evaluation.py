@@ -157,7 +157,7 @@ def make_trials(speaker_ids, n_target, n_nontarget, seed):
 
 
 def evaluate_trials(embeddings, labels, idx_a, idx_b, metric="cosine", operating_points=DEFAULT_OPERATING_POINTS, device=True,
-                    backend=None, plda=None, calibration=None):
+                    backend=None, plda=None, calibration=None, score_norm=None):
     """Verification over a trial list: trial p compares embeddings[idx_a[p]] with embeddings[idx_b[p]] (`svk_pair_scores`,
     metric "cosine" or "l2"), labels[p] = 1 for the same speaker.  Returns a dict: eer, auc, eer_threshold, and per operating
     point (p_target, c_miss, c_fa) the lists min_dcf, threshold, p_miss, p_fa; scores = the float32 trial scores on the device.
@@ -168,14 +168,17 @@ def evaluate_trials(embeddings, labels, idx_a, idx_b, metric="cosine", operating
     log-likelihood ratios (`svk_plda_pair_scores`, idx_a the test side); metric must then be left at its default.
     calibration: a fitted one-system `calibration.Calibration`: the trial scores go through it before the metrics (scores = the
     calibrated LLRs) and the dict gains cllr and the list act_dcf, the cost of deciding at each operating point's Bayes
-    threshold (`svk_decision_counts`; min_dcf <= act_dcf, the gap is the calibration loss).  None (the default) changes nothing."""
+    threshold (`svk_decision_counts`; min_dcf <= act_dcf, the gap is the calibration loss).  None (the default) changes nothing.
+    score_norm: a `score_norm.ScoreNorm` fitted on a cohort for the same back end and PLDA: the trial scores are normalised
+    (between the raw score and the calibration) before the metrics, and scores = the normalised scores.  None (the default)
+    changes nothing."""
     from .pipeline import trial_scores
     eng = get_engine()
     if calibration is not None and calibration.n_sys != 1:
         raise ValueError("evaluate_trials scores one system: the calibration must be fitted on one, not %r" % (calibration.n_sys,))
     bad = torch.zeros((1,), dtype=torch.int32, device=eng.device)
     emb = eng.to_device(embeddings, torch.float32)
-    scores = trial_scores(eng, emb, idx_a, idx_b, None, metric, backend, plda, calibration, bad)
+    scores = trial_scores(eng, emb, idx_a, idx_b, None, metric, backend, plda, calibration, bad, score_norm=score_norm)
     if int(bad.item()):
         raise ValueError("evaluate_trials: %d trials index outside the %d embeddings" % (int(bad.item()), emb.shape[0]))
     labels = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1)

@@ -115,7 +115,7 @@ class VerificationPipeline:
     def __init__(self, model, use_vad=True, vad_threshold=c.VAD_ENERGY_THRESHOLD, normalize=c.NORMALIZE,
                  crop_seed=12345, micro_batch=1024, preemph_cof=None, crop_rng="reference", overlap_front=False,
                  pcm_scale=1.0 / 32768.0, cubes_per_clip=1, pool="mean", backend=None, plda=None,
-                 calibration=None):
+                 calibration=None, score_norm=None):
         """model: a `model.C3D2` with one channel, or with three (static, delta, delta-delta features: utils.py:325-348,
         :382-397; every method then carries [n, 3, T, 40] feature rows and [n, 3, 20, 80, 40] cubes): its inference form is
         `model.fused_inference()`, seven libsvk kernels.  Any other channel count raises ValueError.
@@ -147,7 +147,11 @@ class VerificationPipeline:
         calibration: a fitted one-system `calibration.Calibration` (fitted on the scores this pipeline produces: cosines, or
         with `plda` its LLRs), or None.  With one, `score` and `score_trials` return calibrated log-likelihood ratios
         (svk_calibration_apply, in place on the fresh scores) and `decide` thresholds them; `search` raises ValueError.  None
-        (the default) changes no code path."""
+        (the default) changes no code path.
+        score_norm: a `score_norm.ScoreNorm` fitted on a cohort with this pipeline's `backend` and `plda`, or None.  With one,
+        `score` and `score_trials` normalise between the raw score and the calibration (svk_cohort_moments of both sides
+        against the cohort, then svk_score_norm / svk_score_norm_pairs in place on the fresh scores; a calibration is then one
+        fitted on normalised scores); `search` raises ValueError.  None (the default) changes no code path."""
         self.channels = int(getattr(model, "num_channels", 0))
         if self.channels not in (1, 3):
             raise ValueError("VerificationPipeline runs C3D2 models with 1 or 3 input channels, got num_channels = %r"
@@ -169,6 +173,9 @@ class VerificationPipeline:
         if calibration is not None and calibration.n_sys != 1:
             raise ValueError("the pipeline scores one system: its calibration must be fitted on one, not %r" % (calibration.n_sys,))
         self.calibration = calibration
+        if score_norm is not None:
+            score_norm.check_scorer(backend, plda)
+        self.score_norm = score_norm
         # model front end: lmfe(signal, 16000, 0.025, 0.01, 40, 1024)  (load_data.py:64-70, Q14)
         self.spec = spec_from_seconds(c.SAMPLE_RATE, c.FRAME_LEN, c.FRAME_STEP, c.NUM_FFT, c.NUM_COEF, c.NUM_COEF,
                                       _lib.OUT_LMFE, preemph=preemph_cof is not None,
@@ -770,6 +777,8 @@ class VerificationPipeline:
         test_emb, enroll_emb = self.project(test_emb), self.project(enroll_emb)
         scores = self.eng.cosine_scores(test_emb, enroll_emb) if self.plda is None else \
             self.plda.score(test_emb, enroll_emb, counts=counts, engine=self.eng)
+        if self.score_norm is not None:       # between the raw score and the calibration, in place
+            self.score_norm.normalize(scores, *self.score_norm.side_moments(test_emb, enroll_emb, counts), out=scores)
         if self.calibration is not None:      # in place on the fresh scores
             self.calibration.apply(scores.reshape(-1), engine=self.eng, out=scores.reshape(-1))
         return scores
@@ -793,6 +802,8 @@ class VerificationPipeline:
             raise ValueError("search ranks by cosine score: top-k by PLDA log-likelihood ratio is not built (use score)")
         if self.calibration is not None:
             raise ValueError("search ranks by raw cosine score: calibrated top-k is not built (use score)")
+        if self.score_norm is not None:
+            raise ValueError("search ranks by raw cosine score: top-k on normalised scores is not built (use score)")
         eng = self.eng
         n_gallery, dim = int(enroll_emb.shape[0]), int(enroll_emb.shape[1])
         query = self.project(eng.to_device(test_emb, torch.float32))
@@ -820,8 +831,10 @@ class VerificationPipeline:
         `svk_pair_scores` -> float32 [n_trials] on the device: a VoxCeleb-style trial list instead of the whole matrix of
         `score`.  On several GPUs call it on the all-gathered embeddings (`distributed.all_gather_embeddings`); every rank
         then holds the whole list's scores (the trial list itself is not sharded).  With `plda`: log-likelihood ratios through
-        `svk_plda_pair_scores`, emb_a the test side and emb_b the enrolled side (one utterance each); `metric` must be left alone."""
-        return trial_scores(self.eng, emb_a, idx_a, idx_b, emb_b, metric, self.backend, self.plda, self.calibration)
+        `svk_plda_pair_scores`, emb_a the test side and emb_b the enrolled side (one utterance each); `metric` must be left alone.
+        With `score_norm`: emb_a's rows take the test side's cohort moments, emb_b's the enrolled side's."""
+        return trial_scores(self.eng, emb_a, idx_a, idx_b, emb_b, metric, self.backend, self.plda, self.calibration,
+                            score_norm=self.score_norm)
 
 
 def project_rows(eng, emb, backend, plda):
@@ -831,18 +844,29 @@ def project_rows(eng, emb, backend, plda):
     return emb if plda is None else plda.project(emb, engine=eng)
 
 
-def trial_scores(eng, emb_a, idx_a, idx_b, emb_b=None, metric="cosine", backend=None, plda=None, calibration=None, bad_count=None):
+def trial_scores(eng, emb_a, idx_a, idx_b, emb_b=None, metric="cosine", backend=None, plda=None, calibration=None, bad_count=None,
+                 score_norm=None):
     """The scoring chain of a trial list (`VerificationPipeline.score_trials`, `evaluation.evaluate_trials`): both sides through
-    `project_rows`, PLDA log-likelihood ratios or `svk_pair_scores`, the calibration in place -> float32 [n_trials] on the
-    device.  emb_b None: both indices address emb_a.  bad_count: an int32 device counter of the indices outside their matrix."""
+    `project_rows`, PLDA log-likelihood ratios or `svk_pair_scores`, the score normalisation and the calibration in place ->
+    float32 [n_trials] on the device.  emb_b None: both indices address emb_a.  bad_count: an int32 device counter of the
+    indices outside their matrix.  score_norm: a fitted `score_norm.ScoreNorm` (for the same back end and PLDA; cosine metric):
+    the cohort moments of every row of the a side as test rows and of the b side as enrolled rows, then svk_score_norm_pairs
+    (every row of both sides, referenced by a trial or not; with emb_b None and the cosine, one table serves both sides)."""
     if plda is not None and metric != "cosine":
         raise ValueError("PLDA scores are log-likelihood ratios: metric does not apply")
+    if score_norm is not None:
+        score_norm.check_scorer(backend, plda)
+        if metric != "cosine":
+            raise ValueError("the cohort is scored by cosine or PLDA: metric %r cannot be normalised on it" % (metric,))
     u_a = project_rows(eng, emb_a, backend, plda)
     u_b = u_a if emb_b is None else project_rows(eng, emb_b, backend, plda)
     if plda is not None:
         scores = plda.score_trials(u_a, idx_a, idx_b, u_b=u_b, bad_count=bad_count, engine=eng)
     else:
         scores = eng.pair_scores(u_a, u_b, idx_a, idx_b, metric=metric, bad_count=bad_count)
+    if score_norm is not None:
+        test_moments, enroll_moments = score_norm.side_moments(u_a, u_b)
+        score_norm.normalize_trials(scores, test_moments, idx_a, enroll_moments, idx_b, out=scores)
     if calibration is not None:
         calibration.apply(scores, engine=eng, out=scores)
     return scores
