@@ -473,7 +473,10 @@ __global__ __launch_bounds__(Spec::MAX_THREADS) void frontend_kernel(const Front
       // the first and drops the result: one code path.
       constexpr int FR_PER_FFT = SPLIT1024 ? 1 : 2;
       const bool pre = RAW16 && c_preemph != 0;
-      auto load = [&](int f, cplx (&v)[8], float& ea, float& eb) __attribute__((always_inline)) {
+      // za / zb: the first / second frame of a packed pair (nfft 512) is all zeros.  The untangling separates the two spectra
+      // only to rounding: a silent frame would inherit ~1e-14 of its partner's power where SpeechPy has an exact 0 (-> eps,
+      // feature.py:217), so its power bins are written as 0.  (nfft 1024 transforms one frame: no partner.)
+      auto load = [&](int f, cplx (&v)[8], float& ea, float& eb, bool& za, bool& zb) __attribute__((always_inline)) {
         const bool hasb = !SPLIT1024 && f + 1 < nvalid;
         const FrameReader<SPLIT1024, RAW16> rd{sig, sigh, f * c_stride, (hasb ? f + 1 : f) * c_stride, c_flen_eff,
                                                p.pre_cof, hasb, lane};
@@ -483,6 +486,17 @@ __global__ __launch_bounds__(Spec::MAX_THREADS) void frontend_kernel(const Front
         } else {
           if (pre) rd.template read_steps<true, false>(c_n_steps, v);
           else rd.template read_steps<false, false>(c_n_steps, v);
+        }
+        za = false, zb = false;
+        if constexpr (!SPLIT1024) {
+          bool nza = false, nzb = false;
+#pragma unroll
+          for (int a = 0; a < 8; ++a) {
+            nza |= v[a].x != 0.f;
+            nzb |= v[a].y != 0.f;
+          }
+          za = __builtin_amdgcn_ballot_w64(nza) == 0;  // wave-uniform
+          zb = __builtin_amdgcn_ballot_w64(nzb) == 0;
         }
         // Frame energy = sum over ALL nfft/2+1 power bins (feature.py:202).  By Parseval that is
         // sum(x^2)/2 + (X[0]^2 + X[nfft/2]^2) / (2 nfft), so only the bins the mel filters read
@@ -501,14 +515,14 @@ __global__ __launch_bounds__(Spec::MAX_THREADS) void frontend_kernel(const Front
       // hold[0..4] / hold[5..9] (first / second frame of the FFT, one float per 64-bin step) and hold[10], hold[11]
       // (their energy partials): see ALIAS_SCR.  Step j = 4 (bins 256..287) exists only when the bank reaches
       // bin 256 = nfft/4 of a 1024-point transform (kp = 288: SpeechPy's bank at any rate but 16 kHz, Q2).
-      auto finish = [&](int f, cplx (&v)[8], float ea, float eb, float (&hold)[12], auto defer) __attribute__((always_inline)) {
+      auto finish = [&](int f, cplx (&v)[8], float ea, float eb, bool za, bool zb, float (&hold)[12], auto defer) __attribute__((always_inline)) {
         constexpr bool DEFER = decltype(defer)::value;
         if (lane0 && c_need_energy) {
           if (SPLIT1024) {  // X[0] = Re + Im, X[512] = Re - Im of Z[0]
             ea += (v[0].x * v[0].x + v[0].y * v[0].y) * (1.0f / 1024.0f);
           } else {          // X1[0], X1[256] = Re Z[0], Re Z[256];  X2: the imaginary parts
-            ea += (v[0].x * v[0].x + v[4].x * v[4].x) * (1.0f / 1024.0f);
-            eb += (v[0].y * v[0].y + v[4].y * v[4].y) * (1.0f / 1024.0f);
+            ea += za ? 0.f : (v[0].x * v[0].x + v[4].x * v[4].x) * (1.0f / 1024.0f);
+            eb += zb ? 0.f : (v[0].y * v[0].y + v[4].y * v[4].y) * (1.0f / 1024.0f);
           }
         }
         float* rowa = ptile + f * prow;
@@ -536,7 +550,7 @@ __global__ __launch_bounds__(Spec::MAX_THREADS) void frontend_kernel(const Front
               cplx xa = add_conj(zk, zn), xb = swap_add_conj(zk, zn);
               xa *= xa;
               xb *= xb;
-              const float pa = xa.x + xa.y, pb = xb.x + xb.y;  // 4 nfft |X[k]|^2
+              const float pa = za ? 0.f : xa.x + xa.y, pb = zb ? 0.f : xb.x + xb.y;  // 4 nfft |X[k]|^2
               if constexpr (DEFER) {
                 hold[j] = pa;
                 hold[5 + j] = pb;
@@ -577,15 +591,16 @@ __global__ __launch_bounds__(Spec::MAX_THREADS) void frontend_kernel(const Front
             const int fb = two ? fa + FR_PER_FFT : fa;
             cplx va[8], vb[8];
             float eaa, eba, eab, ebb;
-            load(fa, va, eaa, eba);
-            load(fb, vb, eab, ebb);
+            bool zaa, zba, zab, zbb;
+            load(fa, va, eaa, eba, zaa, zba);
+            load(fb, vb, eab, ebb, zab, zbb);
             fft512_wave_x2<(Spec::N_STEPS > 0 ? Spec::N_STEPS : 8)>(va, vb, scr, lane, t1, t2);
             if (t < DIRECT) {
-              finish(fa, va, eaa, eba, unused, std::false_type{});
-              if (two) finish(fb, vb, eab, ebb, unused, std::false_type{});
+              finish(fa, va, eaa, eba, zaa, zba, unused, std::false_type{});
+              if (two) finish(fb, vb, eab, ebb, zab, zbb, unused, std::false_type{});
             } else {
-              finish(fa, va, eaa, eba, held[2 * (t - DIRECT)], std::true_type{});
-              if (two) finish(fb, vb, eab, ebb, held[2 * (t - DIRECT) + 1], std::true_type{});
+              finish(fa, va, eaa, eba, zaa, zba, held[2 * (t - DIRECT)], std::true_type{});
+              if (two) finish(fb, vb, eab, ebb, zab, zbb, held[2 * (t - DIRECT) + 1], std::true_type{});
             }
           }
         }
@@ -616,12 +631,13 @@ __global__ __launch_bounds__(Spec::MAX_THREADS) void frontend_kernel(const Front
           const int fb = two ? fa + FR_PER_FFT : fa;
           cplx va[8], vb[8];
           float eaa, eba, eab, ebb;
-          load(fa, va, eaa, eba);
-          load(fb, vb, eab, ebb);
+          bool zaa, zba, zab, zbb;
+          load(fa, va, eaa, eba, zaa, zba);
+          load(fb, vb, eab, ebb, zab, zbb);
           fft512_wave_x2<(Spec::N_STEPS > 0 ? Spec::N_STEPS : 8)>(va, vb, scr, lane, t1, t2);
           float unused[12];
-          finish(fa, va, eaa, eba, unused, std::false_type{});
-          if (two) finish(fb, vb, eab, ebb, unused, std::false_type{});
+          finish(fa, va, eaa, eba, zaa, zba, unused, std::false_type{});
+          if (two) finish(fb, vb, eab, ebb, zab, zbb, unused, std::false_type{});
         }
       }
       wave_sync();
