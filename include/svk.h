@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_cohort_moments, svk_score_norm, svk_score_norm_pairs (adaptive score normalisation: the top-K cohort moments of every row by an exact radix select, and Z- / T- / S-norm from them); earlier under the same number: + svk_calibration_stats, svk_calibration_stats_workspace_bytes, svk_calibration_apply (score calibration and fusion: the statistics of a prior-weighted logistic regression in one pass, and the affine map); earlier under the same number: + svk_plda_scores, svk_plda_scores_workspace_bytes, svk_plda_pair_scores (PLDA log-likelihood ratios: the score matrix on the f32 matrix pipe, trial lists in float64); earlier under the same number: svk_c3d2_stage2 runs as one kernel and no longer touches d_act2, which may be NULL (same results, bit for bit); earlier under the same number: + svk_class_scatter, svk_class_scatter_workspace_bytes, svk_embedding_project (the embedding back end: class statistics in float64 and centre / project / length-normalise in one pass); earlier additions under the same number: + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
+#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_window_crops, svk_segment_affinity, svk_ahc, svk_ahc_limits, svk_ahc_workspace_bytes (speaker diarization: sliding-window crop tables, the window-against-window cosines of every recording and average-linkage clustering, one workgroup per recording); earlier under the same number: + svk_cohort_moments, svk_score_norm, svk_score_norm_pairs (adaptive score normalisation: the top-K cohort moments of every row by an exact radix select, and Z- / T- / S-norm from them); earlier under the same number: + svk_calibration_stats, svk_calibration_stats_workspace_bytes, svk_calibration_apply (score calibration and fusion: the statistics of a prior-weighted logistic regression in one pass, and the affine map); earlier under the same number: + svk_plda_scores, svk_plda_scores_workspace_bytes, svk_plda_pair_scores (PLDA log-likelihood ratios: the score matrix on the f32 matrix pipe, trial lists in float64); earlier under the same number: svk_c3d2_stage2 runs as one kernel and no longer touches d_act2, which may be NULL (same results, bit for bit); earlier under the same number: + svk_class_scatter, svk_class_scatter_workspace_bytes, svk_embedding_project (the embedding back end: class statistics in float64 and centre / project / length-normalise in one pass); earlier additions under the same number: + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
 
 typedef enum svk_status {
   SVK_OK = 0,
@@ -463,6 +463,89 @@ size_t svk_cosine_topk_workspace_bytes(int32_t n_query, int32_t n_gallery, int32
 int svk_cosine_topk(svk_ctx* ctx, const float* d_query, int32_t n_query, const float* d_gallery, int32_t n_gallery,
                     int32_t dim, int32_t k, int64_t index_base, const int64_t* d_exclude, int32_t flags,
                     void* d_workspace, size_t workspace_bytes, float* d_top_score, int64_t* d_top_index);
+
+/* ---- speaker diarization (csrc/cluster.hip) ---------------------------------------------------
+ * "Who spoke when" in recordings with several speakers: sliding windows over a recording's feature rows, one embedding per
+ * window (svk_c3d2_stage1_multi with K = max_windows), the cosine of every pair of windows of a recording, and agglomerative
+ * clustering of each recording's windows.  All three entries are asynchronous on the context's stream, make no host round trip,
+ * use no floating-point atomics and let no workgroup wait for another; every device loop has a trip count fixed by its
+ * arguments.  PADDED layout throughout: recording r owns slot r of every array, and d_n_seg[r] (d_n_windows[r]) of its
+ * seg_stride (max_windows) rows are live.  n_rec == 0 launches nothing and looks at no pointer.
+ *
+ * svk_window_crops: per-recording frame counts -> the crop table svk_c3d2_stage1_multi takes.  Integer arithmetic only.  For a
+ * recording of T = d_n_frames[r] frames (a negative count reads as 0):
+ *   windows       T < crop_frames: none;  T < win_frames: one window [0, T);  else windows of win_frames frames starting at
+ *                 w * hop_frames for w = 0 .. (T - win_frames) / hop_frames, and, when (T - win_frames) % hop_frames != 0, a last
+ *                 window [T - win_frames, T)
+ *   crops         crop c of a window [w0, w0 + len) starts at w0 + (c * (len - crop_frames)) / max(n_crops - 1, 1)
+ *   d_crop_idx    int32 [n_rec][max_windows][n_crops]; -1 in unused windows (the first block reads zero rows there)
+ *   d_n_windows   int32 [n_rec]: windows written, at most max_windows
+ *   d_window_span NULL, or int32 [n_rec][max_windows][2]: (first frame, length) of every window, (-1, 0) in unused ones
+ *   d_bad_count   a recording that needs more than max_windows windows keeps its first max_windows and adds 1 to *d_bad_count
+ *                 (int32, may be NULL; the caller zeroes it)
+ * SVK_ERR_BAD_ARG: NULL context or buffer, negative size, crop_frames < 1, win_frames < crop_frames, hop_frames < 1,
+ * n_crops < 1, max_windows < 1, max_windows * n_crops or n_crops * win_frames at or above 2^31, misalignment. */
+int svk_window_crops(svk_ctx* ctx, const int32_t* d_n_frames, int32_t n_rec, int32_t win_frames, int32_t hop_frames,
+                     int32_t crop_frames, int32_t n_crops, int32_t max_windows, int32_t* d_crop_idx, int32_t* d_n_windows,
+                     int32_t* d_window_span, int32_t* d_bad_count);
+
+/* The cosine of every pair of live rows of every recording: the block-diagonal part of the corpus-wide matrix
+ * svk_cosine_scores would write.
+ *   d_emb         f32 [n_rec][seg_stride][dim], 4-byte aligned, 1 <= dim <= 512
+ *   d_n_seg       int32 [n_rec]: live rows of each recording; a value outside [0, seg_stride] is clamped into it
+ *   d_aff         f32 [n_rec][seg_stride][seg_stride]; entries with i or j >= d_n_seg[r] are NOT written
+ * Arithmetic as svk_pair_scores' cosine: products, sums, square roots and the division in float64, a zero norm divides by 1 (a
+ * zero row scores exactly 0), the result (float)(x.y / (||x|| ||y||)) rounded once.  The dot products run on
+ * v_mfma_f64_16x16x4_f64, one wave per 16 x 16 tile of the upper triangle; k runs in super-steps of 16, inside one the
+ * k = 16 S + 4 g + e in the order (e, g); the squared norms are summed per lane over its columns in order, then over g.  Since
+ * sum |x_k y_k| <= ||x|| ||y||, the float64 value lies within (dim + 8) 2^-53 of the exact cosine: the output is float32(exact)
+ * or, within that distance of a rounding boundary, its neighbour (tests/test_segment_affinity.py).
+ *   symmetry      only entries with i <= j are computed; each is written to [i][j] and [j][i]: symmetric bit for bit
+ *   bits          an entry depends on its two rows and dim alone -- not on n_rec, the slot, seg_stride, d_n_seg or the launch
+ *                 geometry; runs are bit-identical.  16-byte loads (dim % 4 == 0 and a 16-byte aligned d_emb) and 4-byte loads
+ *                 fill the same registers: the same bits
+ *   NaN           a NaN (or Inf) row makes its own row and column NaN and touches nothing else
+ * SVK_ERR_BAD_ARG: NULL context or buffer, negative size, dim outside [1, 512], misalignment, more tiles than one launch holds. */
+int svk_segment_affinity(svk_ctx* ctx, const float* d_emb, int32_t n_rec, int32_t seg_stride, int32_t dim,
+                         const int32_t* d_n_seg, float* d_aff);
+
+/* Average-linkage agglomerative clustering of every recording on its SIMILARITY matrix (larger = closer: the cosines above, or
+ * LLRs a caller writes there).  One workgroup per recording.  Definition (tests/ahc_f64_ref.py states it in NumPy and the kernel
+ * reproduces it bit for bit), n = d_n_seg[r]:
+ *   W             float64 [n][n], W[i][j] = W[j][i] = (double)d_aff[r][i][j] for i < j: only entries ABOVE the diagonal of live
+ *                 rows are read; cluster sizes s = 1, k = n live clusters
+ *   step          the live pair i < j with the largest W[i][j]; ties go to the lowest i, then the lowest j.  The step is taken
+ *                 if k > max_clusters, or if k > min_clusters and W[i][j] >= threshold; otherwise clustering stops
+ *   merge         j into i: for every other live m, W[m][i] = W[i][m] = (s_i W[m][i] + s_j W[m][j]) / (s_i + s_j) -- two products,
+ *                 one sum, one quotient, each rounded once in float64, no fused multiply-add; then s_i += s_j, j is retired
+ *   d_target      NULL, or int32 [n_rec]: a value >= 1 replaces BOTH min_clusters and max_clusters for that recording (a known
+ *                 number of speakers); a target above n merges nothing
+ *   d_labels      int32 [n_rec][seg_stride]: clusters numbered 0, 1, ... in the order of their lowest member; dead rows are not
+ *                 written
+ *   d_n_clusters  int32 [n_rec]
+ *   d_merge_pair  NULL, or int32 [n_rec][seg_stride][2]: step t of a recording in slot t as (i, j); unused slots hold -1
+ *   d_merge_sim   NULL, or float64 [n_rec][seg_stride]: W[i][j] of step t in slot t; unused slots hold NaN
+ *   special       n == 0: 0 clusters;  n == 1: one cluster.  A recording with a non-finite live entry above the diagonal, or with
+ *                 d_n_seg[r] outside [0, seg_stride], is NOT clustered: its labels are -1 (the live rows'; all seg_stride of
+ *                 them when the count is out of range), its cluster count is -1, its merge slots are unused, and it adds 1 to
+ *                 *d_bad_count (int32, may be NULL; the caller zeroes it).  Non-finite values below the diagonal or in dead
+ *                 rows are never read
+ *   instances     n <= svk_ahc_limits()[0] keeps W in LDS (128 rows, 129 float64 apart: 129 KiB of the 160); a larger recording works in
+ *                 its slot of d_workspace.  Both run the same statements in the same order: the same bits
+ *   d_workspace   svk_ahc_workspace_bytes(n_rec, seg_stride) bytes, 16-byte aligned: 0 (d_workspace may be NULL) when
+ *                 seg_stride <= limits[0], else 8 seg_stride^2 bytes per recording; 0 for arguments the call rejects
+ * The search keeps every row's best partner j > i and the global step is a reduction over rows: average linkage is reducible, so
+ * a merge elsewhere changes a row's best only through the merged column, which is compared on the spot; the total order above
+ * (ties included) is reproduced exactly.  The bits depend on the recording's matrix and the stop arguments alone: a recording
+ * clustered alone gives the bits it gives in a batch, and runs are bit-identical.  At most n - 1 steps; no spin-waits.
+ * svk_ahc_limits: out[0] = the largest n_seg that runs on the LDS instance, out[1] = the largest supported seg_stride (2 048).
+ * SVK_ERR_BAD_ARG: NULL context or buffer, negative size, seg_stride above limits[1], min_clusters < 1, max_clusters <
+ * min_clusters, a NaN threshold (+-infinity is allowed), misalignment, a short workspace. */
+int svk_ahc_limits(int32_t out[2]);
+size_t svk_ahc_workspace_bytes(int32_t n_rec, int32_t seg_stride);
+int svk_ahc(svk_ctx* ctx, const float* d_aff, int32_t n_rec, int32_t seg_stride, const int32_t* d_n_seg, double threshold,
+            int32_t min_clusters, int32_t max_clusters, const int32_t* d_target, void* d_workspace, size_t workspace_bytes,
+            int32_t* d_labels, int32_t* d_n_clusters, int32_t* d_merge_pair, double* d_merge_sim, int32_t* d_bad_count);
 
 /* ---- ROC / EER / AUC on the device ------------------------------------------------------------
  * evaluation.py:47-52 (sklearn roc_curve + roc_auc_score + brentq on interp1d) for pair sets too

@@ -1033,6 +1033,92 @@ class Engine:
               self.ctx)
         return out
 
+    def window_crops(self, n_frames, max_windows, win_frames=150, hop_frames=75, crop_frames=80, n_crops=20, bad_count=None,
+                     want_spans=True):
+        """svk_window_crops: frame counts [n_rec] i32 -> (crop_idx [n_rec, max_windows, n_crops] i32 with -1 in unused windows,
+        n_windows [n_rec] i32, spans [n_rec, max_windows, 2] i32 = (first frame, length), or None without want_spans), all on the
+        device.  A recording of T frames has no window below crop_frames, the one window [0, T) below win_frames, else windows of
+        win_frames every hop_frames and a last one flush with the end; crop c of a window spreads evenly over it.  A recording
+        that needs more than max_windows keeps the first ones and counts in bad_count (int32 [1] device tensor, caller zeroes)."""
+        torch = _torch()
+        nf = self.to_device(n_frames, torch.int32).reshape(-1)
+        n_rec, K, nc = nf.numel(), int(max_windows), int(n_crops)
+        self._counter(bad_count, "bad_count")
+        idx = torch.empty((n_rec, max(K, 0), max(nc, 0)), dtype=torch.int32, device=self.device)
+        nwin = torch.empty((n_rec,), dtype=torch.int32, device=self.device)
+        spans = torch.empty((n_rec, max(K, 0), 2), dtype=torch.int32, device=self.device) if want_spans else None
+        self._stream()
+        check(self.lib.svk_window_crops(self.ctx, self._ptr(nf), n_rec, int(win_frames), int(hop_frames), int(crop_frames), nc, K,
+                                        self._ptr(idx), self._ptr(nwin), self._ptr(spans), self._ptr(bad_count)), self.ctx)
+        return idx, nwin, spans
+
+    def _n_seg(self, n_seg, n_rec):
+        """The live-row counts of a padded batch as int32 [n_rec] on the device."""
+        ns = self.to_device(n_seg, _torch().int32).reshape(-1)
+        if ns.numel() != n_rec:
+            raise ValueError("n_seg holds one count per recording")
+        return ns
+
+    def segment_affinity(self, emb, n_seg, out=None):
+        """svk_segment_affinity: emb [n_rec, seg_stride, dim] f32 + n_seg [n_rec] i32 -> the cosines of every pair of live rows
+        of every recording, float32 [n_rec, seg_stride, seg_stride] on the device (float64 arithmetic, symmetric bit for bit).
+        Entries of dead rows are NOT written: `out` (a float32 device tensor of that shape) keeps what it held there; without
+        `out` they are zeros."""
+        torch = _torch()
+        x = self.to_device(emb, torch.float32)
+        if x.dim() != 3:
+            raise ValueError("segment_affinity wants rows (n_rec, seg_stride, dim)")
+        n_rec, stride, dim = (int(v) for v in x.shape)
+        ns = self._n_seg(n_seg, n_rec)
+        if out is None:
+            out = torch.zeros((n_rec, stride, stride), dtype=torch.float32, device=self.device)
+        else:
+            self._given_out(out, (n_rec, stride, stride), torch.float32, "out must be a contiguous float32 device tensor [n_rec, seg_stride, seg_stride]")
+        self._stream()
+        check(self.lib.svk_segment_affinity(self.ctx, self._ptr(x), n_rec, stride, dim, self._ptr(ns), self._ptr(out)), self.ctx)
+        return out
+
+    def ahc_limits(self):
+        """svk_ahc_limits: (the largest n_seg clustered in LDS, the largest seg_stride svk_ahc takes)."""
+        out = (C.c_int32 * 2)()
+        check(self.lib.svk_ahc_limits(out))
+        return int(out[0]), int(out[1])
+
+    def ahc(self, aff, n_seg, threshold=None, min_clusters=1, max_clusters=None, target=None, want_merges=False,
+            bad_count=None, labels_out=None):
+        """svk_ahc: average-linkage agglomerative clustering of every recording of aff [n_rec, seg_stride, seg_stride] f32
+        (similarities, only the entries above the diagonal of the n_seg[r] live rows are read) -> (labels [n_rec, seg_stride]
+        i32, n_clusters [n_rec] i32) on the device; with want_merges also merge_pair [n_rec, seg_stride, 2] i32 and merge_sim
+        [n_rec, seg_stride] f64.  A step merges the most similar pair while more than max_clusters clusters are left, or while
+        more than min_clusters are left and the pair reaches `threshold` (None: nothing does).  target: int32 [n_rec], a value
+        >= 1 fixes that recording's cluster count.  Labels of dead rows are -1 here (the library leaves them alone: a given
+        labels_out, int32 [n_rec, seg_stride] on the device, keeps what it held there); a recording
+        with a non-finite entry or a count out of range gets labels -1, count -1 and counts in bad_count."""
+        torch = _torch()
+        a = self.to_device(aff, torch.float32)
+        if a.dim() != 3 or a.shape[1] != a.shape[2]:
+            raise ValueError("ahc wants matrices (n_rec, seg_stride, seg_stride)")
+        n_rec, stride = int(a.shape[0]), int(a.shape[1])
+        ns = self._n_seg(n_seg, n_rec)
+        tg = self._n_seg(target, n_rec) if target is not None else None
+        self._counter(bad_count, "bad_count")
+        thr = float("inf") if threshold is None else float(threshold)
+        max_c = 0x7fffffff if max_clusters is None else int(max_clusters)
+        work = self._workspace(self.lib.svk_ahc_workspace_bytes(n_rec, stride))
+        if labels_out is None:
+            labels = torch.full((n_rec, stride), -1, dtype=torch.int32, device=self.device)
+        else:
+            labels = labels_out
+            self._given_out(labels, (n_rec, stride), torch.int32, "labels_out must be a contiguous int32 device tensor [n_rec, seg_stride]")
+        count = torch.empty((n_rec,), dtype=torch.int32, device=self.device)
+        pair = torch.empty((n_rec, stride, 2), dtype=torch.int32, device=self.device) if want_merges else None
+        sim = torch.empty((n_rec, stride), dtype=torch.float64, device=self.device) if want_merges else None
+        self._stream()
+        check(self.lib.svk_ahc(self.ctx, self._ptr(a), n_rec, stride, self._ptr(ns), thr, int(min_clusters), max_c, self._ptr(tg),
+                               self._ptr(work), work.numel(), self._ptr(labels), self._ptr(count), self._ptr(pair), self._ptr(sim),
+                               self._ptr(bad_count)), self.ctx)
+        return (labels, count, pair, sim) if want_merges else (labels, count)
+
     def class_scatter(self, emb, seg_start, row_index=None, l2_rows=False):
         """svk_class_scatter: the float64 class means [n_class, dim] and the within-class scatter S_w [dim, dim] (two-pass, on
         the centred rows) of emb [n_rows, dim] f32 -> two float64 device tensors.  Class c is rows

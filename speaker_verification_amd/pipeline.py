@@ -826,6 +826,15 @@ class VerificationPipeline:
             into = out
         return into
 
+    def diarize(self, pcm, **kw):
+        """"Who spoke when": int16 PCM [n_rec, samples] of recordings with several speakers -> one list of
+        `diarization.Turn(start_s, end_s, speaker)` per recording (`diarization.Diarizer.diarize`, which lists the keywords:
+        `threshold` or `num_speakers` must be given).  The Diarizer (1.5 s windows every 0.75 s) is made on first use."""
+        if getattr(self, "_diarizer", None) is None:
+            from .diarization import Diarizer
+            self._diarizer = Diarizer(self)
+        return self._diarizer.diarize(pcm, **kw)
+
     def score_trials(self, emb_a, idx_a, idx_b, emb_b=None, metric="cosine"):
         """One score per trial (emb_a[idx_a[p]] against emb_b[idx_b[p]], emb_b = emb_a when not given) through
         `svk_pair_scores` -> float32 [n_trials] on the device: a VoxCeleb-style trial list instead of the whole matrix of
