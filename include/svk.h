@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_window_crops, svk_segment_affinity, svk_ahc, svk_ahc_limits, svk_ahc_workspace_bytes (speaker diarization: sliding-window crop tables, the window-against-window cosines of every recording and average-linkage clustering, one workgroup per recording); earlier under the same number: + svk_cohort_moments, svk_score_norm, svk_score_norm_pairs (adaptive score normalisation: the top-K cohort moments of every row by an exact radix select, and Z- / T- / S-norm from them); earlier under the same number: + svk_calibration_stats, svk_calibration_stats_workspace_bytes, svk_calibration_apply (score calibration and fusion: the statistics of a prior-weighted logistic regression in one pass, and the affine map); earlier under the same number: + svk_plda_scores, svk_plda_scores_workspace_bytes, svk_plda_pair_scores (PLDA log-likelihood ratios: the score matrix on the f32 matrix pipe, trial lists in float64); earlier under the same number: svk_c3d2_stage2 runs as one kernel and no longer touches d_act2, which may be NULL (same results, bit for bit); earlier under the same number: + svk_class_scatter, svk_class_scatter_workspace_bytes, svk_embedding_project (the embedding back end: class statistics in float64 and centre / project / length-normalise in one pass); earlier additions under the same number: + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
+#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_spectral_embed, svk_spectral_limits, svk_spectral_workspace_bytes (spectral clustering for diarization: batched Jacobi eigendecompositions of graph Laplacians, the speaker count from the eigengap, the neighbour count by the normalised maximum eigengap); earlier under the same number: + svk_window_crops, svk_segment_affinity, svk_ahc, svk_ahc_limits, svk_ahc_workspace_bytes (speaker diarization: sliding-window crop tables, the window-against-window cosines of every recording and average-linkage clustering, one workgroup per recording); earlier under the same number: + svk_cohort_moments, svk_score_norm, svk_score_norm_pairs (adaptive score normalisation: the top-K cohort moments of every row by an exact radix select, and Z- / T- / S-norm from them); earlier under the same number: + svk_calibration_stats, svk_calibration_stats_workspace_bytes, svk_calibration_apply (score calibration and fusion: the statistics of a prior-weighted logistic regression in one pass, and the affine map); earlier under the same number: + svk_plda_scores, svk_plda_scores_workspace_bytes, svk_plda_pair_scores (PLDA log-likelihood ratios: the score matrix on the f32 matrix pipe, trial lists in float64); earlier under the same number: svk_c3d2_stage2 runs as one kernel and no longer touches d_act2, which may be NULL (same results, bit for bit); earlier under the same number: + svk_class_scatter, svk_class_scatter_workspace_bytes, svk_embedding_project (the embedding back end: class statistics in float64 and centre / project / length-normalise in one pass); earlier additions under the same number: + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
 
 typedef enum svk_status {
   SVK_OK = 0,
@@ -546,6 +546,74 @@ size_t svk_ahc_workspace_bytes(int32_t n_rec, int32_t seg_stride);
 int svk_ahc(svk_ctx* ctx, const float* d_aff, int32_t n_rec, int32_t seg_stride, const int32_t* d_n_seg, double threshold,
             int32_t min_clusters, int32_t max_clusters, const int32_t* d_target, void* d_workspace, size_t workspace_bytes,
             int32_t* d_labels, int32_t* d_n_clusters, int32_t* d_merge_pair, double* d_merge_sim, int32_t* d_bad_count);
+
+/* Spectral embedding of every recording with the speaker count read off the eigengap (Ng-Jordan-Weiss; the neighbour count of
+ * the graph chosen by the normalised maximum eigengap, Park et al. 2020) (csrc/spectral.hip).  svk_ahc on the cosines of the
+ * embedding rows, with d_n_speakers as its target, gives the labels; svk_ahc's labels may also come first, as d_group, to reduce
+ * a long recording to at most limits[0] nodes.  One workgroup per recording; asynchronous on the context's stream, no host round
+ * trip, no floating-point atomics, no workgroup waits for another, every loop's trip count is bounded by the arguments.
+ * Definition (tests/spectral_f64_ref.py states it in NumPy), n = d_n_seg[r]:
+ *   nodes         d_group == NULL: node a is window a, m = n, M[a][b] = (double)d_aff[r][min(a, b)][max(a, b)].  Otherwise
+ *                 d_group is int32 [n_rec][seg_stride] (svk_ahc's labels), m = 1 + the largest label of the live rows, and
+ *                 M[a][b] = (sum over i in a, j in b of (double)d_aff[r][min(i, j)][max(i, j)]) / (double)(|a| |b|) for a != b
+ *                 (the mean pairwise cosine: what average linkage holds).  ORDER OF ADDITIONS: one float64 accumulator from 0,
+ *                 i over a's members ascending, inside it j over b's members ascending; one division.  Only entries ABOVE
+ *                 the diagonal that join two live rows of DIFFERENT nodes are read; the diagonal of M is not used
+ *   graph(p)      p clamped to m - 1.  Row a keeps its p largest M[a][b], b != a, ties to the lower b: B[a][b] = 1 there, else 0.
+ *                 S = (B + B^T) / 2, D = diag(S 1), L = D - S: every entry a multiple of 1/2, exact in float64
+ *   spectrum      all m eigenvalues of L by cyclic Jacobi, sorted ascending (equal values in the order of their index).
+ *                 M2 = m rounded up to even (an index >= m is padding and pairs as an identity), H = M2 / 2.  A sweep is the
+ *                 M2 - 1 rounds r = 0 .. M2 - 2 of the round-robin: pair 0 = {M2 - 1, r}, pair k = {(r + k) mod (M2 - 1),
+ *                 (r - k) mod (M2 - 1)} for k = 1 .. H - 1, each written p < q.  A round takes every rotation from the matrix
+ *                 as the round finds it: a_pq == 0 gives c = 1, s = 0, else theta = (a_qq - a_pp) / (2 a_pq),
+ *                 t = copysign(1, theta) / (|theta| + sqrt(theta^2 + 1)), c = 1 / sqrt(t^2 + 1), s = t c; then A <- J^T A J for
+ *                 the product J of the round's rotations: x'_p = c x_p - s x_q, x'_q = s x_p + c x_q along columns, then along
+ *                 rows, a pair's own a_pq (which the rotation annihilates) then set to zero outright; an entry and its
+ *                 mirror image get the same bits.  Products may contract into fused multiply-adds.  Before every
+ *                 sweep the largest off-diagonal magnitude is compared with 2^-52 ||L||_F: at or below it the diagonal is
+ *                 the spectrum.  At most 30 sweeps, then one last comparison; a recording that fails it is bad
+ *   count         g_i = lambda_(i+1) - lambda_i, i = 1 .. min(max_speakers, m - 1) (lambda_1 the smallest); k = the first i with
+ *                 the largest g_i, raised to min_speakers, capped at m.  d_target: NULL, or int32 [n_rec]; a value >= 1
+ *                 replaces k, capped at m and at max_speakers (the columns of d_embed); the ratio below is unaffected
+ *   neighbours    candidates p_c = nb_lo + c nb_step, c = 0 .. nb_count - 1, clamped to m - 1; a candidate that clamps to the
+ *                 p of the one before it is skipped (and so are all after it).  r(p) = p lambda_max / max_i g_i in float64,
+ *                 +infinity when the largest gap is not positive; the smallest r wins, the first among equals.  Candidates
+ *                 are solved for eigenvalues only; the winner again with vectors (the same eigenvalue bits)
+ *   d_embed       f32 [n_rec][node_stride][max_speakers]: row a < m = (float)v_1[a] .. (float)v_k[a], then zeros; v_j is the
+ *                 eigenvector of lambda_j of the chosen graph, its sign such that the entry of largest magnitude (the lowest
+ *                 index among equals) is positive.  Rows a >= m are NOT written
+ *   d_n_nodes, d_n_speakers, d_neighbours   int32 [n_rec]: m, k, the chosen (clamped) p
+ *   d_eigval      NULL, or f64 [n_rec][node_stride]: the m eigenvalues of the chosen graph, ascending
+ *   d_eigvec      NULL, or f64 [n_rec][max_speakers][node_stride]: v_1 .. v_k in float64 (rows j < k, entries a < m)
+ *   d_graph       NULL, or u8 [n_rec][node_stride][node_stride]: 2 S of the chosen graph (the m x m block)
+ *   d_ratio       NULL, or f64 [n_rec][nb_count]: r(p_c); NaN where the candidate was skipped
+ *   special       m == 0: 0 nodes, 0 speakers, 0 neighbours.  m == 1: 1 node, 1 speaker, 0 neighbours, embedding row (1, 0, ...),
+ *                 eigenvalue 0, eigenvector (1), graph (0).  Both leave d_ratio NaN
+ *   bad           a non-finite affinity among the entries read; d_n_seg[r] outside [0, seg_stride]; a group label of a live row
+ *                 outside [0, node_stride); a node below the largest label without a member; no convergence.  A bad recording
+ *                 gets d_n_nodes = d_n_speakers = d_neighbours = -1, zeros in all node_stride rows of its d_embed slot, NaN in
+ *                 its d_ratio slot, and adds 1 to *d_bad_count (int32, may be NULL; the caller zeroes it).  It touches no
+ *                 other recording
+ *   d_workspace   svk_spectral_workspace_bytes(n_rec, seg_stride, node_stride) bytes, 16-byte aligned: per recording 8 c^2 +
+ *                 4 * (seg_stride rounded up to 4) bytes with c = max(2, node_stride rounded up to even) -- the eigenvectors
+ *                 (transposed) and the member lists; 0 for arguments the call rejects
+ *   LDS           sized by node_stride: L with c rows, c + 1 float64 apart, one byte per entry of the neighbour ranks and a few
+ *                 vectors (150 KiB at 128 nodes, 39 KiB at 64)
+ * The only rounding is inside the eigensolver.  The bits depend on the recording's live entries, its groups and the scalar
+ * arguments alone -- not on n_rec, the slot or the launch geometry; a recording processed alone gives the bits it gives in a
+ * batch, and runs are bit-identical.
+ * svk_spectral_limits: out[0] = the largest node_stride (128), out[1] = the largest seg_stride (2 048), out[2] = the largest
+ * max_speakers (16).
+ * SVK_ERR_BAD_ARG: NULL context or required buffer, negative size, node_stride or seg_stride above the limits, d_group == NULL
+ * with seg_stride > node_stride, nb_lo, nb_step or nb_count < 1, min_speakers < 1, max_speakers outside [min_speakers,
+ * limits[2]], misalignment, a short workspace.  n_rec == 0 launches nothing and looks at no pointer. */
+int svk_spectral_limits(int32_t out[3]);
+size_t svk_spectral_workspace_bytes(int32_t n_rec, int32_t seg_stride, int32_t node_stride);
+int svk_spectral_embed(svk_ctx* ctx, const float* d_aff, int32_t n_rec, int32_t seg_stride, const int32_t* d_n_seg,
+                       const int32_t* d_group, int32_t node_stride, int32_t nb_lo, int32_t nb_step, int32_t nb_count,
+                       int32_t min_speakers, int32_t max_speakers, const int32_t* d_target, void* d_workspace,
+                       size_t workspace_bytes, float* d_embed, int32_t* d_n_nodes, int32_t* d_n_speakers, int32_t* d_neighbours,
+                       double* d_eigval, double* d_eigvec, uint8_t* d_graph, double* d_ratio, int32_t* d_bad_count);
 
 /* ---- ROC / EER / AUC on the device ------------------------------------------------------------
  * evaluation.py:47-52 (sklearn roc_curve + roc_auc_score + brentq on interp1d) for pair sets too

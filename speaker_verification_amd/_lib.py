@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsvk.so")
 
 SVK_OK = 0
-VERSION = 114                      # include/svk.h SVK_VERSION (0.1.12: + svk_window_crops, svk_segment_affinity, svk_ahc, number unchanged; + svk_cohort_moments, svk_score_norm, svk_score_norm_pairs, number unchanged; + svk_calibration_stats, svk_calibration_apply, number unchanged; + svk_plda_scores, svk_plda_pair_scores, number unchanged; + svk_class_scatter, svk_embedding_project, number unchanged; + svk_cosine_topk, number unchanged; + svk_pair_scores, svk_roc_dcf, svk_decision_counts, number unchanged; + svk_c3d2_head; + the svk_delta_* entries, the *_multi first block and svk_embedding_pool, number unchanged)
+VERSION = 114                      # include/svk.h SVK_VERSION (0.1.12: + svk_spectral_embed, svk_spectral_limits, svk_spectral_workspace_bytes, number unchanged; + svk_window_crops, svk_segment_affinity, svk_ahc, number unchanged; + svk_cohort_moments, svk_score_norm, svk_score_norm_pairs, number unchanged; + svk_calibration_stats, svk_calibration_apply, number unchanged; + svk_plda_scores, svk_plda_pair_scores, number unchanged; + svk_class_scatter, svk_embedding_project, number unchanged; + svk_cosine_topk, number unchanged; + svk_pair_scores, svk_roc_dcf, svk_decision_counts, number unchanged; + svk_c3d2_head; + the svk_delta_* entries, the *_multi first block and svk_embedding_pool, number unchanged)
 SVK_ERR_BAD_ARG, SVK_ERR_UNSUPPORTED, SVK_ERR_HIP, SVK_ERR_NO_DEVICE, SVK_ERR_OOM, SVK_ERR_RCCL = -1, -2, -3, -4, -5, -6
 OUT_MFE, OUT_LMFE, OUT_MFCC = 0, 1, 2
 PCM_I16, PCM_F32 = 0, 1
@@ -107,6 +107,10 @@ SIGNATURES = {
     "svk_ahc_limits": (C.c_int, [C.POINTER(_i32)]),
     "svk_ahc_workspace_bytes": (C.c_size_t, [_i32, _i32]),
     "svk_ahc": (C.c_int, [_vp, _vp, _i32, _i32, _vp, C.c_double, _i32, _i32, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp]),
+    "svk_spectral_limits": (C.c_int, [C.POINTER(_i32)]),
+    "svk_spectral_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32]),
+    "svk_spectral_embed": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, C.c_size_t, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "svk_c3d2_stage1_lds_bytes": (C.c_size_t, []),
     "svk_c3d2_stage1": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "svk_c3d2_stage1_c3_lds_bytes": (C.c_size_t, []),

@@ -5,6 +5,8 @@ around the multi-cube embedding call:
 
     pipeline.vad -> pipeline.features -> svk_window_crops -> embedder.embed_features(feat, crops[n, K, 20], pool=None)
     [-> pipeline.project with a back end] -> svk_segment_affinity -> svk_ahc
+    or, with method="spectral" (INTEGRATION 11), which counts the speakers itself:
+    ... -> svk_segment_affinity [-> svk_ahc down to 128 nodes] -> svk_spectral_embed -> svk_segment_affinity -> svk_ahc
 
 One D2H then fetches labels, window spans and the VAD frame map, and the timeline -- a few hundred integers per recording -- is
 built on the host.  The host helpers (window rule, timeline, RTTM, DER) need no GPU."""
@@ -233,15 +235,54 @@ class Diarizer:
         win = self._windows(pcm, lengths)
         return self.pipeline.eng.segment_affinity(win["emb"], win["n_windows"]), win["n_windows"]
 
-    def diarize(self, pcm, lengths=None, threshold=None, num_speakers=None, min_speakers=1, max_speakers=None,
-                return_device=False):
-        """pcm int16 [n_rec, samples] -> one list of Turn(start_s, end_s, speaker) per recording, in original time.  Either
-        `threshold` (merging stops when no pair of clusters reaches this cosine; it has NO default: tune it on a development
-        set with `affinity`) or `num_speakers` (an int, or one per recording) must be given.  min_speakers / max_speakers bound
-        the cluster count under a threshold.  return_device: also the dict of device tensors behind the result."""
-        if threshold is None and num_speakers is None:
+    METHODS = ("ahc", "spectral")
+    NEIGHBOURS = (2, 32, 2)      # a SEARCH RANGE (lo, hi, step) for the neighbour count, not a tuned value
+    MAX_SPEAKERS = 8             # how far the eigengap is looked for under `spectral` when the caller sets no bound
+
+    @staticmethod
+    def _arguments(method, threshold, num_speakers):
+        """The argument rules of `diarize` that need no engine."""
+        if method not in Diarizer.METHODS:
+            raise ValueError("unknown method %r: diarize clusters with %s" % (method, " or ".join(map(repr, Diarizer.METHODS))))
+        if method == "spectral":
+            if threshold is not None:
+                raise ValueError("`threshold` stops agglomerative merging: method='spectral' counts the speakers from the "
+                                 "eigengap and takes none")
+        elif threshold is None and num_speakers is None:
             raise ValueError("diarize needs `threshold` or `num_speakers`: no affinity threshold has been measured for any "
-                             "checkpoint, and none is assumed")
+                             "checkpoint, and none is assumed (method='spectral' needs neither)")
+
+    def _spectral(self, eng, aff, n_win, target, min_speakers, max_speakers, neighbours):
+        """affinities -> (window labels, speaker counts, the tensors behind them): svk_ahc down to the node limit where the
+        window stride exceeds it, svk_spectral_embed, the cosines of the embedding rows, svk_ahc to the counted speakers, and
+        the node labels gathered through the groups."""
+        limit = eng.spectral_limits()[0]
+        group = None
+        if int(aff.shape[1]) > limit:
+            group, _ = eng.ahc(aff, n_win, threshold=None, max_clusters=limit)
+        embed, n_nodes, n_spk, chosen = eng.spectral_embed(aff, n_win, group=group, neighbours=neighbours, min_speakers=min_speakers,
+                                                           max_speakers=max_speakers, target=target)
+        node_labels, count = eng.ahc(eng.segment_affinity(embed, n_nodes), n_nodes, target=n_spk)
+        labels = node_labels
+        if group is not None:
+            # rows move, nothing is computed: window -> its node's label (dead windows, group -1, stay -1)
+            import torch
+            labels = torch.gather(node_labels, 1, group.clamp(min=0).long()).masked_fill(group < 0, -1)
+        return labels, count, {"group": group, "embedding": embed, "n_nodes": n_nodes, "neighbours": chosen, "node_labels": node_labels}
+
+    def diarize(self, pcm, lengths=None, threshold=None, num_speakers=None, min_speakers=1, max_speakers=None,
+                return_device=False, method="ahc", neighbours=None):
+        """pcm int16 [n_rec, samples] -> one list of Turn(start_s, end_s, speaker) per recording, in original time.
+        method="ahc" (the default): either `threshold` (merging stops when no pair of clusters reaches this cosine; it has NO
+        default: tune it on a development set with `affinity`) or `num_speakers` (an int, or one per recording) must be given;
+        min_speakers / max_speakers bound the cluster count under a threshold.
+        method="spectral": neither is needed.  The speakers are counted from the largest eigengap of a nearest-neighbour
+        graph of the windows, between min_speakers and max_speakers (default 8); `neighbours` is the graph's neighbour count,
+        an int or a (lo, hi, step) range searched by the normalised maximum eigengap -- the default (2, 32, 2) is a search
+        range, not a tuned value.  num_speakers, where given, replaces the count; `threshold` is refused.  Recordings with more
+        windows than svk_spectral_limits()[0] are first merged down to that many nodes by svk_ahc.
+        return_device: also the dict of device tensors behind the result."""
+        self._arguments(method, threshold, num_speakers)
         import torch
         eng = self.pipeline.eng
         win = self._windows(pcm, lengths)
@@ -252,8 +293,14 @@ class Diarizer:
             if (target < 1).any():
                 raise ValueError("num_speakers must be at least 1")
         aff = eng.segment_affinity(win["emb"], win["n_windows"])
-        labels, count = eng.ahc(aff, win["n_windows"], threshold=threshold, min_clusters=min_speakers, max_clusters=max_speakers,
-                                target=target)
+        extra = {}
+        if method == "spectral":
+            labels, count, extra = self._spectral(eng, aff, win["n_windows"], target, min_speakers,
+                                                  self.MAX_SPEAKERS if max_speakers is None else max_speakers,
+                                                  self.NEIGHBOURS if neighbours is None else neighbours)
+        else:
+            labels, count = eng.ahc(aff, win["n_windows"], threshold=threshold, min_clusters=min_speakers, max_clusters=max_speakers,
+                                    target=target)
         # ONE D2H: labels, spans, counts and the VAD frame map as one int32 row per recording
         cols = [labels, win["spans"].reshape(n_rec, 2 * K), win["n_windows"][:, None], win["n_frames"][:, None],
                 win["packed"][:, None], count[:, None]]
@@ -269,6 +316,6 @@ class Diarizer:
             src = row[3 * K + 4:] if win["src_frame"] is not None else None
             out.append(timeline(fl, stride, packed, src, win["frame_samples"]))
         if return_device:
-            win.update(affinity=aff, labels=labels, n_clusters=count)
+            win.update(affinity=aff, labels=labels, n_clusters=count, **extra)
             return out, win
         return out

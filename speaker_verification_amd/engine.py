@@ -1119,6 +1119,71 @@ class Engine:
                                self._ptr(bad_count)), self.ctx)
         return (labels, count, pair, sim) if want_merges else (labels, count)
 
+    def spectral_limits(self):
+        """svk_spectral_limits: (the most nodes per recording, the largest seg_stride, the largest max_speakers)."""
+        out = (C.c_int32 * 3)()
+        check(self.lib.svk_spectral_limits(out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    @staticmethod
+    def _neighbour_sweep(neighbours):
+        """An int p, or (lo, hi, step): the candidates lo, lo + step, ... up to hi -> (lo, step, count)."""
+        if isinstance(neighbours, (int, np.integer)):
+            return int(neighbours), 1, 1
+        lo, hi, step = (int(v) for v in neighbours)
+        if lo < 1 or step < 1 or hi < lo:
+            raise ValueError("neighbours is an int >= 1 or (lo, hi, step) with 1 <= lo <= hi and step >= 1")
+        return lo, step, (hi - lo) // step + 1
+
+    def spectral_embed(self, aff, n_seg, group=None, neighbours=(2, 32, 2), min_speakers=1, max_speakers=8, target=None,
+                       want_spectrum=False, want_graph=False, bad_count=None):
+        """svk_spectral_embed: the spectral embedding of every recording of aff [n_rec, seg_stride, seg_stride] f32 (only the
+        entries above the diagonal of the n_seg[r] live rows are read), the speaker count from the largest eigengap and the
+        graph's neighbour count from the normalised maximum eigengap -> (embed [n_rec, node_stride, max_speakers] f32,
+        n_nodes, n_speakers, neighbours, each [n_rec] i32) on the device; with want_spectrum also eigval [n_rec, node_stride]
+        f64 and eigvec [n_rec, max_speakers, node_stride] f64, with want_graph also graph [n_rec, node_stride, node_stride]
+        u8 (twice the symmetrised adjacency) and ratio [n_rec, candidates] f64.  group: None (every window is a node;
+        node_stride = seg_stride), or svk_ahc's labels int32 [n_rec, seg_stride] (node_stride = spectral_limits()[0]).
+        neighbours: an int, or a (lo, hi, step) search range.  target: int32 [n_rec], a value >= 1 fixes that recording's
+        count.  What the library leaves alone (dead rows, unused vectors) is zero here.  A bad recording (non-finite entry,
+        counts or labels out of range, no convergence) reads -1 in the three counts and counts in bad_count."""
+        torch = _torch()
+        a = self.to_device(aff, torch.float32)
+        if a.dim() != 3 or a.shape[1] != a.shape[2]:
+            raise ValueError("spectral_embed wants matrices (n_rec, seg_stride, seg_stride)")
+        n_rec, stride = int(a.shape[0]), int(a.shape[1])
+        ns = self._n_seg(n_seg, n_rec)
+        tg = self._n_seg(target, n_rec) if target is not None else None
+        self._counter(bad_count, "bad_count")
+        grp, nodes = None, stride
+        if group is not None:
+            grp = self.to_device(group, torch.int32)
+            if tuple(grp.shape) != (n_rec, stride):
+                raise ValueError("group holds one label per window: int32 [n_rec, seg_stride]")
+            nodes = self.spectral_limits()[0]
+        lo, step, count = self._neighbour_sweep(neighbours)
+        K = int(max_speakers)
+        work = self._workspace(self.lib.svk_spectral_workspace_bytes(n_rec, stride, nodes))
+        dev = self.device
+        embed = torch.zeros((n_rec, nodes, max(K, 0)), dtype=torch.float32, device=dev)
+        n_nodes, n_spk, chosen = (torch.empty((n_rec,), dtype=torch.int32, device=dev) for _ in range(3))
+        eigval = torch.zeros((n_rec, nodes), dtype=torch.float64, device=dev) if want_spectrum else None
+        eigvec = torch.zeros((n_rec, max(K, 0), nodes), dtype=torch.float64, device=dev) if want_spectrum else None
+        graph = torch.zeros((n_rec, nodes, nodes), dtype=torch.uint8, device=dev) if want_graph else None
+        ratio = torch.empty((n_rec, count), dtype=torch.float64, device=dev) if want_graph else None
+        self._stream()
+        check(self.lib.svk_spectral_embed(self.ctx, self._ptr(a), n_rec, stride, self._ptr(ns), self._ptr(grp), nodes, lo, step,
+                                          count, int(min_speakers), K, self._ptr(tg), self._ptr(work), work.numel(),
+                                          self._ptr(embed), self._ptr(n_nodes), self._ptr(n_spk), self._ptr(chosen),
+                                          self._ptr(eigval), self._ptr(eigvec), self._ptr(graph), self._ptr(ratio),
+                                          self._ptr(bad_count)), self.ctx)
+        out = (embed, n_nodes, n_spk, chosen)
+        if want_spectrum:
+            out += (eigval, eigvec)
+        if want_graph:
+            out += (graph, ratio)
+        return out
+
     def class_scatter(self, emb, seg_start, row_index=None, l2_rows=False):
         """svk_class_scatter: the float64 class means [n_class, dim] and the within-class scatter S_w [dim, dim] (two-pass, on
         the centred rows) of emb [n_rows, dim] f32 -> two float64 device tensors.  Class c is rows

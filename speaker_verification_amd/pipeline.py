@@ -829,7 +829,8 @@ class VerificationPipeline:
     def diarize(self, pcm, **kw):
         """"Who spoke when": int16 PCM [n_rec, samples] of recordings with several speakers -> one list of
         `diarization.Turn(start_s, end_s, speaker)` per recording (`diarization.Diarizer.diarize`, which lists the keywords:
-        `threshold` or `num_speakers` must be given).  The Diarizer (1.5 s windows every 0.75 s) is made on first use."""
+        `threshold` or `num_speakers` must be given under the default method="ahc"; method="spectral" counts the speakers from
+        the eigengap and needs neither).  The Diarizer (1.5 s windows every 0.75 s) is made on first use."""
         if getattr(self, "_diarizer", None) is None:
             from .diarization import Diarizer
             self._diarizer = Diarizer(self)
