@@ -250,7 +250,8 @@ int svk_cube_draw_crops(svk_ctx* ctx, const int32_t* d_n_frames, int32_t n_utt, 
  * d_taps   : [n_taps] float32 (odd count; the host builds them, see ingest.py)
  * d_out    : [n_utt][out_stride] float32 in [-1, 1) (SVK_PCM_F32) or int16 rounded back to the
  *            16-bit grid, saturating (SVK_PCM_I16); samples past a clip's end are written as 0
- * d_out_len: [n_utt] int32 = min(ceil(n_in * up / down), clip_out), or NULL          */
+ * d_out_len: [n_utt] int32 = min(ceil(n_in * up / down), clip_out), or NULL; written for every
+ *            clip also when clip_out == 0 (a batch without frames: all zero, nothing else is touched) */
 int svk_ingest_resample(svk_ctx* ctx, const int16_t* d_pcm, int32_t n_ch, int64_t in_stride,
                         const int32_t* d_in_len, int32_t clip_in, int32_t n_utt, const float* d_taps,
                         int32_t n_taps, int32_t up, int32_t down, void* d_out, int32_t out_dtype,

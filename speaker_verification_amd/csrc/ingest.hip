@@ -185,7 +185,11 @@ int svk_ingest_resample(svk_ctx* ctx, const int16_t* d_pcm, int32_t n_ch, int64_
                         int32_t clip_in, int32_t n_utt, const float* d_taps, int32_t n_taps, int32_t up, int32_t down,
                         void* d_out, int32_t out_dtype, int64_t out_stride, int32_t clip_out, int32_t* d_out_len) {
   SVK_REQUIRE(ctx, ctx != nullptr, "ctx");
-  if (n_utt == 0 || clip_out == 0) return SVK_OK;
+  if (n_utt == 0) return SVK_OK;
+  if (clip_out == 0) {  // nothing to launch (a batch without frames), but the lengths are an output all the same: min(.., 0)
+    if (n_utt > 0 && d_out_len) SVK_HIP(ctx, hipMemsetAsync(d_out_len, 0, sizeof(int32_t) * (size_t)n_utt, ctx->stream));
+    return SVK_OK;
+  }
   SVK_REQUIRE(ctx, d_pcm && d_taps && d_out, "null buffer");
   SVK_REQUIRE(ctx, n_utt > 0 && n_ch >= 1 && n_ch <= 8 && clip_in >= 0 && clip_out > 0, "shape");
   SVK_REQUIRE(ctx, in_stride >= clip_in && out_stride >= clip_out, "strides shorter than the clips");
