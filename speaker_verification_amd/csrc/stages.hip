@@ -102,6 +102,20 @@ __global__ __launch_bounds__(64 * SPEC_WAVES) void spectrum_fft_kernel(const flo
         v[a].y = (nn < feff && hasb) ? sb[nn] : 0.f;
       }
     }
+    // The untangling separates the two frames of a pair only to rounding: a silent frame would inherit ~1e-14 of its
+    // partner's power where SpeechPy has an exact 0, so its bins are written as 0 (as frontend.hip does).  nfft 1024
+    // transforms one frame: no partner, no flag.
+    bool za = false, zb = false;  // wave-uniform
+    if (!SPLIT1024) {
+      bool nza = false, nzb = false;
+#pragma unroll
+      for (int a = 0; a < 8; ++a) {
+        nza |= v[a].x != 0.f;
+        nzb |= v[a].y != 0.f;
+      }
+      za = __builtin_amdgcn_ballot_w64(nza) == 0;
+      zb = __builtin_amdgcn_ballot_w64(nzb) == 0;
+    }
     fft512_wave(v, scr, lane, t1, t2);
     cplx s7 = shfl2(v[7], mirror), s6 = shfl2(v[6], mirror), s5 = shfl2(v[5], mirror), s4 = shfl2(v[4], mirror);
     cplx zm[5] = {lane0 ? v[0] : s7, lane0 ? s7 : s6, lane0 ? s6 : s5, lane0 ? s5 : s4, v[4]};
@@ -131,8 +145,8 @@ __global__ __launch_bounds__(64 * SPEC_WAVES) void spectrum_fft_kernel(const flo
           pa = sqrtf(pa);
           pb = sqrtf(pb);
         }
-        oa[k] = pa;
-        if (hasb) ob[k] = pb;
+        oa[k] = za ? 0.f : pa;
+        if (hasb) ob[k] = zb ? 0.f : pb;
       }
     }
   }
@@ -458,6 +472,10 @@ __global__ __launch_bounds__(256) void cmvn_apply_kernel(float* __restrict__ fea
 // staged power chunks of the first filter block.  (log) mel energies of the tile stay in LDS; the DCT-II
 // (ortho) rows come from a table built once per call (dct_table_kernel).
 constexpr int MEL_FR = 16, MEL_CH = 64;
+// log of a mel / frame energy, correctly rounded: the float32 library logarithm is up to ~2.2 ulp off the true value (measured
+// on [0.5, 2] and on mel energies around e^14), more than the 2 ulp the stage is held to; one float64 log per output is noise
+// beside the bank product.
+__device__ __forceinline__ float log_rn(float v) { return (float)log((double)v); }
 __global__ __launch_bounds__(256) void mel_features_kernel(const float* __restrict__ power, int nframes, int nbins,
                                                            const float* __restrict__ bank, int nf, int out_kind,
                                                            int ncep, int dc_elim, const float* __restrict__ dct,
@@ -504,7 +522,7 @@ __global__ __launch_bounds__(256) void mel_features_kernel(const float* __restri
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         float m = acc[q] == 0.f ? EPS : acc[q];  // feature.py:217
-        lmel[(fg * 4 + q) * nf + fb + fi] = out_kind == SVK_OUT_MFE ? m : logf(m);
+        lmel[(fg * 4 + q) * nf + fb + fi] = out_kind == SVK_OUT_MFE ? m : log_rn(m);
       }
     }
   }
@@ -523,7 +541,7 @@ __global__ __launch_bounds__(256) void mel_features_kernel(const float* __restri
     if (out_kind != SVK_OUT_MFCC) {
       v = lmel[r * nf + cc];
     } else if (cc == 0 && dc_elim) {
-      v = logf(etot[r]);                             // feature.py:151-152
+      v = log_rn(etot[r]);                             // feature.py:151-152
     } else {
       const float* d = dct + (int64_t)cc * nf;
       const float* lm = lmel + r * nf;
@@ -637,7 +655,7 @@ __global__ __launch_bounds__(256) void mel_features_mfma_kernel(const float* __r
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float m = acc[fbi][nt][r] == 0.f ? EPS : acc[fbi][nt][r];  // feature.py:217
-          lmel[(16 * wave + 4 * kk + r) * nf + 64 * fbi + 16 * nt + i] = out_kind == SVK_OUT_MFE ? m : logf(m);
+          lmel[(16 * wave + 4 * kk + r) * nf + 64 * fbi + 16 * nt + i] = out_kind == SVK_OUT_MFE ? m : log_rn(m);
         }
       }
   esum += __shfl_xor(esum, 2, 64);
@@ -652,7 +670,7 @@ __global__ __launch_bounds__(256) void mel_features_mfma_kernel(const float* __r
     if (out_kind != SVK_OUT_MFCC) {
       v = lmel[r * nf + cc];
     } else if (cc == 0 && dc_elim) {
-      v = logf(etot[r]);                             // feature.py:151-152
+      v = log_rn(etot[r]);                             // feature.py:151-152
     } else {
       const float* d = dct + (int64_t)cc * nf;
       const float* lm = lmel + r * nf;

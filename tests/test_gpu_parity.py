@@ -718,7 +718,8 @@ def test_utils_transforms(eng, golden, monkeypatch):
 
 def test_general_fft_lengths(sp):
     """fft lengths / filter counts outside the fused kernel go through the stage kernels
-    (framing -> direct-DFT spectrum -> svk_mel_features) and still match the reference."""
+    (framing -> svk_spectrum -> svk_mel_features) and still match the reference: nfft 256 and 2048 run the
+    Stockham kernel (spectrum_pow2_kernel), nfft 400 the direct DFT (spectrum_dft_kernel)."""
     sig8k = synth.noise_clip(21, 8000)
     np.testing.assert_allclose(sp.feature.mfcc(sig8k, 8000, fft_length=256),
                                ref.mfcc(sig8k, 8000, fft_length=256), **FEAT_TOL)
