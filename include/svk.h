@@ -18,6 +18,14 @@
  *   - launches go to the stream set by svk_set_stream (default: the null stream)
  *     and are asynchronous w.r.t. the host; svk_sync waits for that stream.
  *   - a context is bound to one device and is not thread-safe.
+ *   - the memory contract (tests/memory_contract.py, tests/test_memory_contract_*.py hold the scoring, back-end, evaluation
+ *     and diarization entries to it on guarded buffers):
+ *       a call writes only the buffers it documents as outputs, and only the elements it documents -- nothing in front of a
+ *       buffer, behind it, in the padding between strided rows or in elements an entry calls "not written";
+ *       the contents of workspaces and outputs on entry change no result (a workspace of exactly svk_*_workspace_bytes
+ *       bytes is enough, whatever it holds; lists an accumulate flag reads and counters "the caller zeroes" are inputs);
+ *       bytes beyond an input's documented extent -- behind its last element, in stride padding, in rows or entries an
+ *       entry calls "not read" -- change no result.
  */
 #ifndef SVK_H
 #define SVK_H
@@ -588,6 +596,8 @@ int svk_ahc(svk_ctx* ctx, const float* d_aff, int32_t n_rec, int32_t seg_stride,
  *   d_eigvec      NULL, or f64 [n_rec][max_speakers][node_stride]: v_1 .. v_k in float64 (rows j < k, entries a < m)
  *   d_graph       NULL, or u8 [n_rec][node_stride][node_stride]: 2 S of the chosen graph (the m x m block)
  *   d_ratio       NULL, or f64 [n_rec][nb_count]: r(p_c); NaN where the candidate was skipped
+ *                 Of d_eigval, d_eigvec and d_graph only the elements named above are written (nothing past entry m, past
+ *                 vector k or outside the m x m block, and nothing at all for a bad recording)
  *   special       m == 0: 0 nodes, 0 speakers, 0 neighbours.  m == 1: 1 node, 1 speaker, 0 neighbours, embedding row (1, 0, ...),
  *                 eigenvalue 0, eigenvector (1), graph (0).  Both leave d_ratio NaN
  *   bad           a non-finite affinity among the entries read; d_n_seg[r] outside [0, seg_stride]; a group label of a live row
@@ -633,10 +643,12 @@ int svk_roc_eer(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, in
  * plus roc_curve(drop_intermediate=True) in counts: the distinct-score points, then (more than two of
  * them) only the first, the last and those where a second difference of fps or tps is non-zero, then the
  * prepended origin.  d_curve: NULL, or uint32 [2][k][step + 1] -- the fps plane, then the tps plane; fpr =
- * fps / fps[-1], tpr = tps / tps[-1] in float64 is sklearn's own arithmetic.  h_out (HOST) [k][4] = {eer, auc,
- * positives, curve points}.  SVK_ERR_BAD_ARG (the message names the split) for a split with one class or a
- * non-finite score, and for k < 1 or step < 2.  d_workspace: svk_roc_k_workspace_bytes(n, k) bytes (0 for
- * arguments svk_roc_k rejects); the splits run one after another through it.  Synchronises the stream. */
+ * fps / fps[-1], tpr = tps / tps[-1] in float64 is sklearn's own arithmetic; entries of a split's rows at and
+ * past its curve points are not written.  h_out (HOST) [k][4] = {eer, auc, positives, curve points}.
+ * SVK_ERR_BAD_ARG (the message names the split) for a split with one class or a non-finite score, and for
+ * k < 1 or step < 2.
+ * d_workspace: svk_roc_k_workspace_bytes(n, k) bytes (0 for arguments svk_roc_k rejects); the splits run one
+ * after another through it.  Synchronises the stream. */
 size_t svk_roc_k_workspace_bytes(int64_t n, int32_t k);
 int svk_roc_k(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, int64_t n, int32_t k, void* d_workspace,
               size_t workspace_bytes, uint32_t* d_curve, double* h_out);

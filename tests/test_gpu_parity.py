@@ -843,6 +843,26 @@ def test_overlapped_front_end_gives_the_same_embeddings(eng):
         assert torch.equal(got, want)
 
 
+def test_overlapped_front_end_behind_a_busy_main_stream(eng):
+    """The same with the main stream busy when the call starts: every launch of the call is then queued before the first one
+    runs, and the side stream gets as far ahead as its dependencies let it.  It may run one micro-batch ahead of the network
+    and no further (while nothing held it back, the last micro-batch missed the one-stream bits in most such calls)."""
+    from speaker_verification_amd.model import seeded_model
+    from speaker_verification_amd.pipeline import VerificationPipeline
+    pcm, _ = synth.corpus_device(96, eng.device)
+    model = seeded_model(2, n_labels=8).to(eng.device).eval()
+    kw = dict(crop_rng="device", crop_seed=7, micro_batch=24, preemph_cof=0.98)
+    want = VerificationPipeline(model, **kw).embed(pcm)
+    both = VerificationPipeline(model, overlap_front=True, **kw)
+    busy = torch.randn((4096, 4096), device=eng.device)
+    for _ in range(6):
+        for _ in range(4):
+            busy = (busy @ busy).clamp_(-1, 1)
+        got = both.embed(pcm)
+        torch.cuda.synchronize()
+        assert torch.equal(got, want)
+
+
 def test_load_wav_resamples_on_device(tmp_path):
     """load_data.load_wav (utils.py:170-173 drop-in) on a stereo 44.1 kHz file and on a mono 16 kHz one."""
     import wave
