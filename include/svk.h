@@ -18,8 +18,9 @@
  *   - launches go to the stream set by svk_set_stream (default: the null stream)
  *     and are asynchronous w.r.t. the host; svk_sync waits for that stream.
  *   - a context is bound to one device and is not thread-safe.
- *   - the memory contract (tests/memory_contract.py, tests/test_memory_contract_*.py hold the scoring, back-end, evaluation
- *     and diarization entries to it on guarded buffers):
+ *   - the memory contract (tests/memory_contract.py; tests/test_memory_contract_{scoring,backend,evaluation,diarization,
+ *     frontend,stages,ingest,network}.py hold every entry that touches device memory to it on guarded buffers, and
+ *     tests/test_memory_contract_helper.py walks the sources so that none is left out):
  *       a call writes only the buffers it documents as outputs, and only the elements it documents -- nothing in front of a
  *       buffer, behind it, in the padding between strided rows or in elements an entry calls "not written";
  *       the contents of workspaces and outputs on entry change no result (a workspace of exactly svk_*_workspace_bytes
@@ -106,18 +107,22 @@ int64_t svk_frontend_num_frames(const svk_frontend_cfg* cfg, int64_t n_samples);
 /* columns of the feature matrix: num_filters (MFE/LMFE) or num_ceps (MFCC) */
 int svk_frontend_num_cols(const svk_frontend_cfg* cfg);
 
-/* d_pcm      : concatenated clips, int16 or float32 (pcm_dtype)
- * d_offsets  : [n_utt] int64 first sample of each clip in d_pcm, or NULL = i * clip_stride
+/* d_pcm      : concatenated clips, int16 or float32 (pcm_dtype); only the samples [offset, offset + length) of each clip are
+ *              read (pre-emphasis is circular over the clip: the neighbour of its first sample is its last), never the gaps
+ *              between clips or what lies behind the last one
+ * d_offsets  : [n_utt] int64 first sample of each clip in d_pcm, or NULL = i * clip_stride; any offset is allowed (a clip
+ *              that starts on a 16-byte boundary is staged with 16-byte loads, any other sample by sample: same bits)
  * d_lengths  : [n_utt] int32 samples per clip, or NULL = clip_len for all
  * max_frames : row stride of the outputs (>= frames of the longest clip)
  * d_feat     : [n_utt][max_frames][num_cols] float32; rows >= n_frames are zeroed
- * d_energy   : [n_utt][max_frames] float32 frame energies (after zero handling), or NULL
+ * d_energy   : [n_utt][max_frames] float32 frame energies (after zero handling), rows >= n_frames are zeroed; or NULL
  * d_n_frames : [n_utt] int32 frames produced per clip, or NULL
  * d_src_chunk: NULL, or GATHERED input (int16 PCM): clip u's signal is then the concatenation of chunks of chunk_samples
  *              samples of its PCM, chunk q = PCM chunk d_src_chunk[u * chunk_stride + q], d_lengths[u] samples of it in
  *              all (required) -- svk_vad_energy's d_src_frame with chunk_samples = frame_samples: the voiced frames of
  *              vad.py:135-168 feed the front end where they lie, without the pass that copies them to the front of a
- *              second buffer (same samples, bit-identical features).  chunk_samples a multiple of 8.
+ *              second buffer (same samples, bit-identical features).  chunk_samples a multiple of 8.  Of a clip's row of the
+ *              table only the first ceil(d_lengths[u] / chunk_samples) entries are read, and of its PCM only the chunks they name.
  */
 int svk_frontend_run(svk_ctx* ctx, const svk_frontend_plan* plan, const void* d_pcm, int pcm_dtype,
                      const int64_t* d_offsets, const int32_t* d_lengths, int64_t clip_stride,
@@ -128,7 +133,7 @@ int svk_frontend_run(svk_ctx* ctx, const svk_frontend_plan* plan, const void* d_
 /* processing.py:45-58.  d_in int16/float32 [n]; d_out float32 [n]; circular. */
 int svk_preemphasis(svk_ctx* ctx, const void* d_in, int pcm_dtype, int64_t n, int32_t shift, float cof,
                     float* d_out);
-/* processing.py:61-139.  frame t = d_sig[t*stride .. +frame_len) (zeros past n) times d_window
+/* processing.py:61-139.  frame t = d_sig[t*stride .. +frame_len) (zeros past n: nothing is read there) times d_window
  * (NULL = rectangular).  d_out float32 [n_frames][frame_len].                 */
 int svk_stack_frames(svk_ctx* ctx, const float* d_sig, int64_t n, int32_t frame_len, int32_t stride,
                      int32_t n_frames, const float* d_window, float* d_out);
@@ -138,7 +143,9 @@ int svk_stack_frames(svk_ctx* ctx, const float* d_sig, int64_t n, int32_t frame_
 int svk_spectrum(svk_ctx* ctx, const float* d_frames, int32_t n_frames, int32_t frame_len, int32_t nfft,
                  int32_t power, float* d_out);
 /* processing.py:239-271 per clip: d_feat [n_utt][max_frames][n_cols], rows < n_frames[u]
- * (NULL = max_frames) are normalised in place; variance != 0 divides by (std + 2^-30). */
+ * (NULL = max_frames) are normalised in place; variance != 0 divides by (std + 2^-30).  Rows >= n_frames[u] are neither
+ * read nor written (nor read by svk_cmvn_stats, svk_delta_cmvn_stats, svk_cmvnw and svk_delta_planes: what they hold reaches
+ * no statistic). */
 int svk_cmvn(svk_ctx* ctx, float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
              const int32_t* d_n_frames, int32_t variance);
 /* The same statistics WITHOUT applying them: d_stats float64 [n_utt][2][n_cols], [u][0][c] = mean, [u][1][c] =
@@ -159,8 +166,9 @@ int svk_mel_features(svk_ctx* ctx, const float* d_power, int32_t n_frames, int32
 /* processing.py:274-327 (cmvnw, Q10) per clip: sliding window of `win` (odd) rows, 'symmetric'
  * padding of (win-1)/2 rows; out = x - window mean; with variance != 0 a second pass divides by
  * (population std of the window over the MEAN-SUBTRACTED rows, padded the same way, + 2^-30).
- * d_in / d_out / d_tmp: [n_utt][max_frames][n_cols] float32, all distinct; d_tmp is only needed
- * (and only written) when variance != 0.  Rows >= n_frames[u] are left untouched in d_out. */
+ * d_in / d_out / d_tmp: [n_utt][max_frames][n_cols] float32, all distinct; d_tmp is a workspace, only needed
+ * (and only written, in rows < n_frames[u] at most) when variance != 0: with variance == 0 it may be NULL and is left
+ * untouched.  Rows >= n_frames[u] are left untouched in d_out. */
 int svk_cmvnw(svk_ctx* ctx, const float* d_in, int32_t n_utt, int32_t max_frames, int32_t n_cols,
               const int32_t* d_n_frames, int32_t win, int32_t variance, float* d_tmp, float* d_out);
 /* processing.py:201-236 (derivative_extraction) exactly as the reference computes it, Q11 included:
@@ -177,8 +185,10 @@ int svk_log_power(svk_ctx* ctx, float* d_power, int64_t n, int32_t normalize);
  * webrtcvad (vad.py:90).  ring_len = int(padding_ms / frame_ms); ring_thresh =
  * floor(0.9 * ring_len) (trigger when voiced > ring_thresh, release when unvoiced >
  * ring_thresh).
- * d_keep       : [n_utt][max_vad_frames] uint8, 1 = frame is in some yielded segment
- * d_seg        : [n_utt][max_vad_frames] int32 segment ordinal or -1, or NULL
+ * A clip of L samples has (2 L - 1) / (2 frame_samples) whole frames (vad.py:54); the samples of the partial frame behind
+ * them are not read.
+ * d_keep       : [n_utt][max_vad_frames] uint8, 1 = frame is in some yielded segment; 0 from the clip's frame count on
+ * d_seg        : [n_utt][max_vad_frames] int32 segment ordinal or -1 (also from the clip's frame count on), or NULL
  * d_n_vad_frames: [n_utt] int32, or NULL
  * d_voiced     : int16, same offsets as d_pcm: kept frames packed to the front (the rest of a
  *                clip's slot is left untouched), or NULL
@@ -195,7 +205,9 @@ int svk_vad_energy(svk_ctx* ctx, const int16_t* d_pcm, const int64_t* d_offsets,
 
 /* ---- feature cube ------------------------------------------------------------
  * utils.py:351-379 (FeatureCube): out[u][0][c][r][:] = feat[u][crop[u][c] + r][:].
- * d_out float32 [n_utt][1][n_crops][crop_frames][n_cols] (a torch tensor's data_ptr()). */
+ * d_out float32 [n_utt][1][n_crops][crop_frames][n_cols] (a torch tensor's data_ptr()).  A negative start or one at / past
+ * max_frames gives a zero crop, a crop that runs past max_frames zero rows from there; rows of d_feat that no crop covers
+ * are not read (the same for svk_cube_gather_cmvn and svk_cube_gather_delta). */
 int svk_cube_gather(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
                     const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, float* d_out);
 /* utils.py:382-397 + :351-379 in one pass: the cube of svk_cmvn-normalised features from the RAW features and svk_cmvn_stats'
@@ -254,7 +266,8 @@ int svk_cube_draw_crops(svk_ctx* ctx, const int32_t* d_n_frames, int32_t n_utt, 
  * polyphase windowed-sinc scheme of scipy.signal.resample_poly (zero-padded edges):
  *     y[m] = sum_j x[j] * taps[m * down + half - j * up],   half = (n_taps - 1) / 2
  * d_pcm    : [n_utt][in_stride][n_ch] interleaved int16 frames (vad.py:10-22 reads them)
- * d_in_len : [n_utt] int32 frames per clip, or NULL = clip_in
+ * d_in_len : [n_utt] int32 frames per clip, or NULL = clip_in; frames at or past a clip's count and the padding of in_stride
+ *            are not read, the padding of out_stride is not written
  * d_taps   : [n_taps] float32 (odd count; the host builds them, see ingest.py)
  * d_out    : [n_utt][out_stride] float32 in [-1, 1) (SVK_PCM_F32) or int16 rounded back to the
  *            16-bit grid, saturating (SVK_PCM_I16); samples past a clip's end are written as 0
@@ -811,7 +824,13 @@ int svk_score_norm_pairs(svk_ctx* ctx, const float* d_scores, int64_t n, const d
                          const double* d_mom_b, int64_t n_b, const int64_t* d_idx_a, const int64_t* d_idx_b,
                          float* d_out, int32_t* d_bad_count);
 
-/* ---- the first block of the embedding network ----------------------------------------------------
+/* ---- the embedding network --------------------------------------------------------------------------
+ * Every entry of this section (svk_c3d2_stage1 .. svk_c3d2_fc5) writes its whole d_out and, beside it, only its workspace where
+ * it has one: svk_c3d2_fc5's d_work, and svk_c3d2_stage2's d_act2 under SVK_C3D2_STAGE2_TWO_KERNELS.  The work-item counters
+ * the persistent kernels draw tickets from live in the handle and are zeroed by every call: a result does not depend on what
+ * ran on the handle before.
+ *
+ * ---- the first block ------------------------------------------------------------------------------
  * model.py:110-117 + :141-150 (C3D2): cube (utils.py:351-379) -> conv1_1 (1 -> 16, kernel (3,1,5)) -> BN -> PReLU
  * -> conv1_2 (16 -> 16, kernel (3,9,1), stride (1,2,1)) -> BN -> PReLU -> MaxPool3d((1,1,2)), eval mode, as ONE
  * kernel: conv1_1's output (3.3 MB per cube) lives only in LDS.  Since 0.1.8 on v_mfma_f32_16x16x32_f16 through TWO-PIECE
@@ -834,7 +853,8 @@ int svk_score_norm_pairs(svk_ctx* ctx, const float* d_scores, int64_t n, const d
  * the host fixes every channel's scale before it splits them (model.FusedEmbedder: activations of channel c are carried times
  * the power of two nearest 1 / (|gamma_c| + |beta_c|) of its BatchNorm, the next layer's weights take the inverse: exact, and
  * the tables no longer depend on how a checkpoint distributes a channel's scale between one layer and the next).
- * d_feat [n_utt][max_frames][40] f32, d_crop_idx [n_utt][20] as for svk_cube_gather (a start outside the clip -> zero rows).
+ * d_feat [n_utt][max_frames][40] f32, d_crop_idx [n_utt][20] as for svk_cube_gather (a start outside the clip -> zero rows, a
+ * crop that runs off the clip -> zero rows from max_frames on; feature rows that no crop names are not read).
  * d_out: the activation after the pool, float32, channels last: [n_utt][16 d][36 h][18 w][16 c]
  * flags bit 1 (value 2) = the caller asserts every PReLU slope lies in [0, 1] (then prelu(v) = max(v, slope v): two
  * instructions per value instead of four); every other bit must be 0.

@@ -1,6 +1,6 @@
 """Guard memory for the memory contract of include/svk.h (Conventions): a call writes only the elements it documents as
 outputs, what its workspaces and outputs hold on entry changes no result, and bytes beyond an input's documented extent change
-no result.  tests/test_memory_contract_*.py hold the scoring, back-end, evaluation and diarization entries to it.
+no result.  tests/test_memory_contract_*.py hold every entry point of the library that touches device memory to it.
 
 An `Arena` is ONE allocation laid out  guard | payload | guard.  Each guard is GUARD = 64 KiB -- a condition, not a
 measurement: more than any single tile row or vector tail of the kernels can overrun, so that a stray store lands in memory the
@@ -236,12 +236,41 @@ def keeps_prefill(arena, region, what):
         what, arena.env, bad.size, region.size, bad[0])
 
 
-# Every svk_* entry point defined in the eleven files the contract tests cover is either exercised by a case (CASES: entry ->
-# the test module that holds it) or exempt with a reason.  tests/test_memory_contract_helper.py walks _lib.SIGNATURES and the
-# sources against the two, so that a later entry point cannot be left out silently.
+# Every svk_* entry point defined in the library's sources (every *.hip of csrc/) is either exercised by a case (CASES: entry ->
+# the test module that holds it) or exempt with a reason.  tests/test_memory_contract_helper.py walks _lib.SIGNATURES, the
+# sources and the directory listing against the three, so that a later entry point or source file cannot be left out silently.
 CONTRACT_SOURCES = ("scoring.hip", "search.hip", "plda.hip", "backend.hip", "pool.hip", "snorm.hip", "calibration.hip", "roc.hip",
-                    "head.hip", "cluster.hip", "spectral.hip")
+                    "head.hip", "cluster.hip", "spectral.hip", "frontend.hip", "stages.hip", "vad.hip", "ingest.hip", "c3d2.hip",
+                    "c3d2_tail.hip", "context.hip", "comm.hip")
 CASES = {
+    "svk_frontend_run": "test_memory_contract_frontend",
+    "svk_preemphasis": "test_memory_contract_stages",
+    "svk_stack_frames": "test_memory_contract_stages",
+    "svk_spectrum": "test_memory_contract_stages",
+    "svk_mel_features": "test_memory_contract_stages",
+    "svk_cmvn": "test_memory_contract_stages",
+    "svk_cmvn_stats": "test_memory_contract_stages",
+    "svk_delta_cmvn_stats": "test_memory_contract_stages",
+    "svk_cmvnw": "test_memory_contract_stages",
+    "svk_derivative": "test_memory_contract_stages",
+    "svk_log_power": "test_memory_contract_stages",
+    "svk_delta_planes": "test_memory_contract_stages",
+    "svk_cube_gather": "test_memory_contract_stages",
+    "svk_cube_gather_cmvn": "test_memory_contract_stages",
+    "svk_cube_gather_delta": "test_memory_contract_stages",
+    "svk_cube_draw_crops": "test_memory_contract_stages",
+    "svk_vad_energy": "test_memory_contract_ingest",
+    "svk_ingest_resample": "test_memory_contract_ingest",
+    "svk_c3d2_stage1": "test_memory_contract_network",
+    "svk_c3d2_stage1_c3": "test_memory_contract_network",
+    "svk_c3d2_stage1_multi": "test_memory_contract_network",
+    "svk_c3d2_stage1_c3_multi": "test_memory_contract_network",
+    "svk_c3d2_stage2": "test_memory_contract_network",
+    "svk_c3d2_conv31": "test_memory_contract_network",
+    "svk_c3d2_conv32t": "test_memory_contract_network",
+    "svk_c3d2_conv41": "test_memory_contract_network",
+    "svk_c3d2_conv42": "test_memory_contract_network",
+    "svk_c3d2_fc5": "test_memory_contract_network",
     "svk_cosine_scores": "test_memory_contract_scoring",
     "svk_l2_dist": "test_memory_contract_scoring",
     "svk_pair_scores": "test_memory_contract_scoring",
@@ -268,7 +297,35 @@ CASES = {
     "svk_spectral_embed": "test_memory_contract_diarization",
 }
 _SIZE_ONLY = "host arithmetic on its arguments: touches no device memory (the cases pass its value as the workspace's exact length)"
+_HOST_ONLY = "reads or writes host memory only: no device memory the caller owns"
+_HANDLE = "makes, frees or configures what the library owns (the handle, a plan, the stream): no device memory the caller owns"
+_RCCL = "RCCL, one process per GPU: not reachable from a single-process test"
+_RUNTIME = "a thin wrapper of one HIP runtime call (hipMalloc, hipFree, hipMemcpy, hipMemset): no kernel of the library runs"
 EXEMPT = {
+    "svk_version": _HOST_ONLY,
+    "svk_last_error": _HOST_ONLY,
+    "svk_device_info": _HOST_ONLY,
+    "svk_create": _HANDLE,
+    "svk_destroy": _HANDLE,
+    "svk_set_stream": _HANDLE,
+    "svk_sync": _HANDLE,
+    "svk_frontend_plan_create": _HANDLE,
+    "svk_frontend_plan_destroy": _HANDLE,
+    "svk_frontend_num_frames": _SIZE_ONLY,
+    "svk_frontend_num_cols": _SIZE_ONLY,
+    "svk_c3d2_stage1_lds_bytes": _SIZE_ONLY,
+    "svk_c3d2_stage1_c3_lds_bytes": _SIZE_ONLY,
+    "svk_c3d2_fc5_workspace_floats": _SIZE_ONLY,
+    "svk_malloc": _RUNTIME,
+    "svk_free": _RUNTIME,
+    "svk_memcpy_h2d": _RUNTIME,
+    "svk_memcpy_d2h": _RUNTIME,
+    "svk_memset": _RUNTIME,
+    "svk_comm_unique_id": _RCCL,
+    "svk_comm_init": _RCCL,
+    "svk_allgather_f32": _RCCL,
+    "svk_comm_destroy": _RCCL,
+    "svk_comm_info": _RCCL,
     "svk_plda_scores_workspace_bytes": _SIZE_ONLY,
     "svk_cosine_topk_workspace_bytes": _SIZE_ONLY,
     "svk_class_scatter_workspace_bytes": _SIZE_ONLY,

@@ -1,5 +1,5 @@
-"""tests/memory_contract.py proves itself on CPU tensors, and the coverage walk: every svk_* entry point defined in the eleven
-source files the memory contract covers has a case in tests/test_memory_contract_*.py or a stated exemption."""
+"""tests/memory_contract.py proves itself on CPU tensors, and the coverage walk: every svk_* entry point defined in a source
+file of the library (every *.hip of csrc/) has a case in tests/test_memory_contract_*.py or a stated exemption."""
 import math
 import os
 import re
@@ -133,9 +133,13 @@ def _defined_entries():
 
 
 def test_every_entry_point_has_a_case_or_an_exemption():
+    listing = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
+    assert sorted(M.CONTRACT_SOURCES) == listing and len(set(M.CONTRACT_SOURCES)) == len(M.CONTRACT_SOURCES), \
+        "CONTRACT_SOURCES is not the library's source files: %s" % sorted(set(listing) ^ set(M.CONTRACT_SOURCES))
+    from speaker_verification_amd import _lib
     defined = _defined_entries()
-    assert len(defined) >= 30 and set(M.CONTRACT_SOURCES) == set(defined.values()), \
-        "the walk no longer finds the entry points: %s" % sorted(defined)
+    assert len(defined) == len(_lib.SIGNATURES) == 87 and set(M.CONTRACT_SOURCES) == set(defined.values()), \
+        "the walk no longer finds the entry points: %s" % sorted(set(_lib.SIGNATURES) - set(defined))
     missing = sorted(fn for fn in defined if fn not in M.CASES and fn not in M.EXEMPT)
     assert not missing, "entry points without a memory-contract case or an exemption: %s" % missing
     assert not set(M.CASES) & set(M.EXEMPT)
