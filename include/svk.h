@@ -202,6 +202,7 @@ int svk_vad_energy(svk_ctx* ctx, const int16_t* d_pcm, const int64_t* d_offsets,
                    int32_t ring_len, int32_t ring_thresh, int64_t threshold, int32_t max_vad_frames,
                    uint8_t* d_keep, int32_t* d_seg, int32_t* d_n_vad_frames, int16_t* d_voiced,
                    int32_t* d_voiced_len, int32_t* d_src_frame);
+/* svk_vad.h declares svk_vad_adaptive: the same framer, hysteresis and outputs with a threshold derived per clip from its levels. */
 
 /* ---- feature cube ------------------------------------------------------------
  * utils.py:351-379 (FeatureCube): out[u][0][c][r][:] = feat[u][crop[u][c] + r][:].

@@ -10,9 +10,14 @@
 //     records keep / segment / packed position per frame.
 // Phase 3 (all waves): kept frames are copied to the front of the clip's output slot.
 // HBM-bound: 2 bytes read per sample (+2 written when compacting).
+//
+// svk_vad_adaptive (include/svk_vad.h) is the same framer, walk and compaction with a threshold derived per clip from two
+// order statistics of the clip's frame energies; its kernels are at the end of the namespace and share the ones above them.
+#include <cstdint>
 #include <cstdlib>
 
 #include "svk_internal.h"
+#include "../../include/svk_vad.h"
 
 namespace {
 
@@ -21,12 +26,54 @@ constexpr int VAD_THREADS = 256;
 
 typedef short i16x8 __attribute__((ext_vector_type(8)));
 
+// The level-adaptive rule's parameters and its two optional outputs, as the kernels carry them (svk_vad.h has the definition).
+struct VadAdaptive {
+  int floor_q16, peak_q16;
+  long long above_floor_q16, below_peak_q16, min_threshold;
+  long long* levels;   // [n_utt][3] = {E_lo, E_hi, T}, or nullptr
+  long long* energy;   // [n_utt][max_vf] E_f, or nullptr
+};
+
+// rank(q) = (q (nf - 1)) >> 16 of a clip of nf >= 1 frames: q <= 2^16 and nf <= 2^13 keep the product below 2^29
+__device__ __forceinline__ int vad_rank(int q16, int nf) { return (int)(((long long)q16 * (nf - 1)) >> 16); }
+
+// T = max(min((E_lo above) >> 16, (E_hi below) >> 16), min_threshold fsamp).  E < 2^47 and above <= 2^40: the first product
+// needs 87 bits, so both are formed in 128 and the smaller one is taken before narrowing; it is at most (E_hi 2^16) >> 16, and
+// the host has checked that min_threshold fsamp fits 63 bits.
+__device__ __forceinline__ long long vad_adaptive_threshold(unsigned long long e_lo, unsigned long long e_hi, const VadAdaptive& r,
+                                                            int fsamp) {
+  const unsigned __int128 a = ((unsigned __int128)e_lo * (unsigned long long)r.above_floor_q16) >> 16;
+  const unsigned __int128 b = ((unsigned __int128)e_hi * (unsigned long long)r.below_peak_q16) >> 16;
+  const long long m = (long long)(unsigned long long)(a < b ? a : b);
+  return max(m, r.min_threshold * (long long)fsamp);
+}
+
+// sum(x^2) of one frame of any length at any alignment, by one wave; every lane gets it
+__device__ __forceinline__ long long vad_frame_energy(const int16_t* __restrict__ fr, int fsamp, int lane) {
+  long long acc = 0;
+  const bool aligned = (reinterpret_cast<uintptr_t>(fr) & 15) == 0;
+  if (aligned) {
+    const int nvec = fsamp >> 3;
+    for (int i = lane; i < nvec; i += 64) {
+      const i16x8 v = *reinterpret_cast<const i16x8*>(fr + 8 * i);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc += (long long)((int)v[e] * (int)v[e]);
+    }
+    for (int i = (nvec << 3) + lane; i < fsamp; i += 64) acc += (long long)((int)fr[i] * (int)fr[i]);
+  } else {
+    for (int i = lane; i < fsamp; i += 64) acc += (long long)((int)fr[i] * (int)fr[i]);
+  }
+  return wave_sum(acc);
+}
+
+template <bool FROM_FLAGS>   // true: the per-frame decisions come from flag_g (svk_vad_adaptive's general route), phase 1 is a copy
 __global__ __launch_bounds__(VAD_THREADS) void vad_kernel(const int16_t* __restrict__ pcm, const int64_t* __restrict__ offsets,
                                                   const int32_t* __restrict__ lengths, int64_t clip_stride,
                                                   int clip_len, int fsamp, int ring_len, int ring_thresh,
                                                   long long threshold, int max_vf, uint8_t* __restrict__ keep_out,
                                                   int32_t* __restrict__ seg_out, int32_t* __restrict__ nvf_out,
-                                                  int16_t* __restrict__ voiced, int32_t* __restrict__ voiced_len, int32_t* __restrict__ src_frame) {
+                                                  int16_t* __restrict__ voiced, int32_t* __restrict__ voiced_len, int32_t* __restrict__ src_frame,
+                                                  const uint8_t* __restrict__ flag_g) {
   __shared__ uint8_t flag[MAX_VAD_FRAMES];
   __shared__ int32_t pos[MAX_VAD_FRAMES];  // packed frame index of a kept frame, or -1
   const int utt = blockIdx.x;
@@ -45,7 +92,9 @@ __global__ __launch_bounds__(VAD_THREADS) void vad_kernel(const int16_t* __restr
   const int nvec_f = fsamp >> 3;
   const bool one_vec = (fsamp & 7) == 0 && nvec_f <= 64 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   constexpr int VU = 8;
-  for (int f0 = wave; one_vec && f0 < nf; f0 += NW * VU) {
+  if constexpr (FROM_FLAGS)
+    for (int f = threadIdx.x; f < nf; f += VAD_THREADS) flag[f] = flag_g[(int64_t)utt * max_vf + f];
+  for (int f0 = wave; !FROM_FLAGS && one_vec && f0 < nf; f0 += NW * VU) {
     i16x8 v[VU];
 #pragma unroll
     for (int u = 0; u < VU; ++u) {
@@ -66,22 +115,8 @@ __global__ __launch_bounds__(VAD_THREADS) void vad_kernel(const int16_t* __restr
       if (lane == 0) flag[f] = acc > threshold * (long long)fsamp ? 1 : 0;
     }
   }
-  for (int f = wave; !one_vec && f < nf; f += NW) {
-    const int16_t* fr = x + (int64_t)f * fsamp;
-    long long acc = 0;
-    const bool aligned = (reinterpret_cast<uintptr_t>(fr) & 15) == 0;
-    if (aligned) {
-      const int nvec = fsamp >> 3;
-      for (int i = lane; i < nvec; i += 64) {
-        const i16x8 v = *reinterpret_cast<const i16x8*>(fr + 8 * i);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc += (long long)((int)v[e] * (int)v[e]);
-      }
-      for (int i = (nvec << 3) + lane; i < fsamp; i += 64) acc += (long long)((int)fr[i] * (int)fr[i]);
-    } else {
-      for (int i = lane; i < fsamp; i += 64) acc += (long long)((int)fr[i] * (int)fr[i]);
-    }
-    acc = wave_sum(acc);
+  for (int f = wave; !FROM_FLAGS && !one_vec && f < nf; f += NW) {
+    const long long acc = vad_frame_energy(x + (int64_t)f * fsamp, fsamp, lane);
     if (lane == 0) flag[f] = acc > threshold * (long long)fsamp ? 1 : 0;
   }
   __syncthreads();
@@ -212,20 +247,12 @@ __global__ __launch_bounds__(VAD_THREADS) void vad_kernel(const int16_t* __restr
 // same integer rule, the same walk. ----
 constexpr int VAD_CHUNK = 32;   // frames per workgroup: 4 waves x 8 frames in flight
 
-__global__ __launch_bounds__(VAD_THREADS) void vad_flags_kernel(const int16_t* __restrict__ pcm, const int64_t* __restrict__ offsets,
-                                                                const int32_t* __restrict__ lengths, int64_t clip_stride, int clip_len,
-                                                                int fsamp, long long threshold, int max_vf, uint8_t* __restrict__ flag_g) {
-  const int utt = blockIdx.y;
-  const int64_t off = offsets ? offsets[utt] : (int64_t)utt * clip_stride;
-  const int len = lengths ? lengths[utt] : clip_len;
-  int nf = len > 0 ? (int)((2LL * len - 1) / (2LL * fsamp)) : 0;
-  if (nf > max_vf) nf = max_vf;
-  const int f_lo = blockIdx.x * VAD_CHUNK;
-  if (f_lo >= nf) return;
-  const int16_t* x = pcm + off;
+// The frames [f_lo, min(nf, f_lo + VAD_CHUNK)) of the clip at x, usual geometry, by one workgroup: lane 0 of the wave that summed
+// frame f hands its sum(x^2) to sink(f, sum).
+template <class Sink>
+__device__ __forceinline__ void vad_chunk_energies(const int16_t* __restrict__ x, int nf, int f_lo, int fsamp, Sink sink) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nvec_f = fsamp >> 3;
-  uint8_t* fl = flag_g + (int64_t)utt * max_vf;
   if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) {
     i16x8 v[8];
 #pragma unroll
@@ -244,7 +271,7 @@ __global__ __launch_bounds__(VAD_THREADS) void vad_flags_kernel(const int16_t* _
       for (int e = 0; e < 8; e += 2)
         acc += (long long)((unsigned)((int)v[u][e] * (int)v[u][e]) + (unsigned)((int)v[u][e + 1] * (int)v[u][e + 1]));
       acc = wave_sum(acc);
-      if (lane == 0) fl[f] = acc > threshold * (long long)fsamp ? 1 : 0;
+      if (lane == 0) sink(f, acc);
     }
   } else {   // a clip that does not start on a 16-byte boundary: element loads
     for (int f = f_lo + wave; f < min(nf, f_lo + VAD_CHUNK); f += 4) {
@@ -252,9 +279,23 @@ __global__ __launch_bounds__(VAD_THREADS) void vad_flags_kernel(const int16_t* _
       long long acc = 0;
       for (int i = lane; i < fsamp; i += 64) acc += (long long)((int)fr[i] * (int)fr[i]);
       acc = wave_sum(acc);
-      if (lane == 0) fl[f] = acc > threshold * (long long)fsamp ? 1 : 0;
+      if (lane == 0) sink(f, acc);
     }
   }
+}
+
+__global__ __launch_bounds__(VAD_THREADS) void vad_flags_kernel(const int16_t* __restrict__ pcm, const int64_t* __restrict__ offsets,
+                                                                const int32_t* __restrict__ lengths, int64_t clip_stride, int clip_len,
+                                                                int fsamp, long long threshold, int max_vf, uint8_t* __restrict__ flag_g) {
+  const int utt = blockIdx.y;
+  const int64_t off = offsets ? offsets[utt] : (int64_t)utt * clip_stride;
+  const int len = lengths ? lengths[utt] : clip_len;
+  int nf = len > 0 ? (int)((2LL * len - 1) / (2LL * fsamp)) : 0;
+  if (nf > max_vf) nf = max_vf;
+  const int f_lo = blockIdx.x * VAD_CHUNK;
+  if (f_lo >= nf) return;
+  uint8_t* fl = flag_g + (int64_t)utt * max_vf;
+  vad_chunk_energies(pcm + off, nf, f_lo, fsamp, [&](int f, long long acc) { fl[f] = acc > threshold * (long long)fsamp ? 1 : 0; });
 }
 
 // The hysteresis of vad.py:60-129 for one clip by one wave, WITHOUT walking the frames one by one.  Between two events the
@@ -363,13 +404,20 @@ __global__ __launch_bounds__(64) void vad_walk_kernel(const int32_t* __restrict_
 // phases 1 and 3 with the wave-parallel walk in between and 6 KB of LDS instead of 40 (more workgroups per CU).
 constexpr int VAD_SMALL = 512;
 
+// ADAPTIVE (svk_vad_adaptive's short-clip route): phase 1 keeps the frame energies in LDS (4 KB) instead of comparing them on the
+// spot; the two order statistics come from rank counting (at most 512 x 512 broadcast LDS reads per clip, two frames per thread),
+// then the clip's threshold and the flags, and the walk and the copy go on unchanged.  `threshold` is then unused.
+template <bool ADAPTIVE>
 __global__ __launch_bounds__(VAD_THREADS) void vad_small_kernel(const int16_t* __restrict__ pcm, const int64_t* __restrict__ offsets,
                                                                 const int32_t* __restrict__ lengths, int64_t clip_stride,
                                                                 int clip_len, int fsamp, int ring_len, int ring_thresh,
                                                                 long long threshold, int max_vf, uint8_t* __restrict__ keep_out,
                                                                 int32_t* __restrict__ seg_out, int32_t* __restrict__ nvf_out,
-                                                                int16_t* __restrict__ voiced, int32_t* __restrict__ voiced_len, int32_t* __restrict__ src_frame) {
+                                                                int16_t* __restrict__ voiced, int32_t* __restrict__ voiced_len, int32_t* __restrict__ src_frame,
+                                                                VadAdaptive rule) {
   __shared__ uint8_t flag[VAD_SMALL];
+  __shared__ long long E[ADAPTIVE ? VAD_SMALL : 1];
+  __shared__ long long sel[2];
   __shared__ int32_t P[VAD_SMALL + 1];
   __shared__ int16_t segm[VAD_SMALL];
   __shared__ int16_t pos[VAD_SMALL];
@@ -384,6 +432,14 @@ __global__ __launch_bounds__(VAD_THREADS) void vad_small_kernel(const int16_t* _
   const int nvec_f = fsamp >> 3;                      // usual geometry only (the host checks): a frame = one vector per lane
   const bool aligned = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   constexpr int VU = 8;
+  auto put = [&](int f, long long acc) {
+    if constexpr (ADAPTIVE) {
+      E[f] = acc;
+      if (rule.energy) rule.energy[(int64_t)utt * max_vf + f] = acc;
+    } else {
+      flag[f] = acc > threshold * (long long)fsamp ? 1 : 0;
+    }
+  };
   for (int f0 = wave; aligned && f0 < nf; f0 += NW * VU) {
     i16x8 v[VU];
 #pragma unroll
@@ -402,7 +458,7 @@ __global__ __launch_bounds__(VAD_THREADS) void vad_small_kernel(const int16_t* _
       for (int e = 0; e < 8; e += 2)
         acc += (long long)((unsigned)((int)v[u][e] * (int)v[u][e]) + (unsigned)((int)v[u][e + 1] * (int)v[u][e + 1]));
       acc = wave_sum(acc);
-      if (lane == 0) flag[f] = acc > threshold * (long long)fsamp ? 1 : 0;
+      if (lane == 0) put(f, acc);
     }
   }
   for (int f = wave; !aligned && f < nf; f += NW) {
@@ -410,9 +466,35 @@ __global__ __launch_bounds__(VAD_THREADS) void vad_small_kernel(const int16_t* _
     long long acc = 0;
     for (int i = lane; i < fsamp; i += 64) acc += (long long)((int)fr[i] * (int)fr[i]);
     acc = wave_sum(acc);
-    if (lane == 0) flag[f] = acc > threshold * (long long)fsamp ? 1 : 0;
+    if (lane == 0) put(f, acc);
   }
   __syncthreads();
+  if constexpr (ADAPTIVE) {
+    // the frame whose energy has `less` smaller ones and `eq` equal ones (itself included) holds the ranks [less, less + eq)
+    const int r_lo = nf > 0 ? vad_rank(rule.floor_q16, nf) : 0, r_hi = nf > 0 ? vad_rank(rule.peak_q16, nf) : 0;
+    if (threadIdx.x < 2) sel[threadIdx.x] = 0;     // (nf == 0: the levels are {0, 0, min_threshold fsamp})
+    __syncthreads();
+    for (int f = threadIdx.x; f < nf; f += VAD_THREADS) {
+      const long long e = E[f];
+      int less = 0, eq = 0;
+      for (int g = 0; g < nf; ++g) {
+        const long long o = E[g];
+        less += o < e;
+        eq += o == e;
+      }
+      if (less <= r_lo && r_lo < less + eq) sel[0] = e;   // ties store the same value
+      if (less <= r_hi && r_hi < less + eq) sel[1] = e;
+    }
+    __syncthreads();
+    const long long t = vad_adaptive_threshold((unsigned long long)sel[0], (unsigned long long)sel[1], rule, fsamp);
+    for (int f = threadIdx.x; f < nf; f += VAD_THREADS) flag[f] = E[f] > t ? 1 : 0;
+    if (threadIdx.x == 0 && rule.levels) {
+      rule.levels[3 * (int64_t)utt] = sel[0];
+      rule.levels[3 * (int64_t)utt + 1] = sel[1];
+      rule.levels[3 * (int64_t)utt + 2] = t;
+    }
+    __syncthreads();
+  }
   if (wave == 0) {
     vad_walk_wave(nf, ring_len, ring_thresh, lane, [&](int f) { return flag[f] != 0; }, P, segm);
     int kept = 0;
@@ -496,6 +578,123 @@ __global__ __launch_bounds__(VAD_THREADS) void vad_copy_kernel(const int16_t* __
   }
 }
 
+// ---- svk_vad_adaptive beyond the short-clip route: the frame energies go to HBM (8 bytes per frame: the caller's d_energy, or the
+// workspace), one workgroup per clip selects the two order statistics and writes the flags, and the walk and the copy above
+// take over: vad_walk_kernel + vad_copy_kernel (long clips, usual geometry) or vad_kernel<true> (any geometry). ----
+
+// E_f of VAD_CHUNK frames per workgroup; grid (clips, chunks).  usual: one 16-byte vector per lane and eight frames in flight
+// (vad_flags_kernel's loop); otherwise a wave per frame at any length and alignment.
+__global__ __launch_bounds__(VAD_THREADS) void vad_energy_kernel(const int16_t* __restrict__ pcm, const int64_t* __restrict__ offsets,
+                                                                 const int32_t* __restrict__ lengths, int64_t clip_stride, int clip_len,
+                                                                 int fsamp, int max_vf, int usual, long long* __restrict__ energy_g) {
+  const int utt = blockIdx.x;
+  const int64_t off = offsets ? offsets[utt] : (int64_t)utt * clip_stride;
+  const int len = lengths ? lengths[utt] : clip_len;
+  int nf = len > 0 ? (int)((2LL * len - 1) / (2LL * fsamp)) : 0;
+  if (nf > max_vf) nf = max_vf;
+  const int f_lo = blockIdx.y * VAD_CHUNK;
+  if (f_lo >= nf) return;
+  const int16_t* x = pcm + off;
+  long long* en = energy_g + (int64_t)utt * max_vf;
+  if (usual) {
+    vad_chunk_energies(x, nf, f_lo, fsamp, [&](int f, long long acc) { en[f] = acc; });
+    return;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int f = f_lo + wave; f < min(nf, f_lo + VAD_CHUNK); f += VAD_THREADS / 64) {
+    const long long acc = vad_frame_energy(x + (int64_t)f * fsamp, fsamp, lane);
+    if (lane == 0) en[f] = acc;
+  }
+}
+
+// The rank(floor_q16)-th and rank(peak_q16)-th smallest of a clip's nf <= 8192 frame energies, EXACTLY, by a radix select over
+// the six 8-bit digits of the 48-bit key (E <= 2^46), most significant first: per pass one LDS histogram per statistic of the
+// digit among the keys that share the prefix found so far; wave k scans histogram k (four bins per lane, a wave prefix sum),
+// the lane whose bins hold the rank appends its digit to the prefix and rebases the rank.  The energies are streamed from HBM /
+// L2 once per pass (at 8192 frames they are 64 KB per clip: all of the static LDS a workgroup can have).  Then the clip's
+// threshold, its levels and its flags.  One workgroup per clip.
+__global__ __launch_bounds__(VAD_THREADS) void vad_select_kernel(const int32_t* __restrict__ lengths, int clip_len, int fsamp, int max_vf,
+                                                                 VadAdaptive rule, const long long* __restrict__ energy_g,
+                                                                 uint8_t* __restrict__ flag_g) {
+  __shared__ unsigned hist[2][256];
+  __shared__ unsigned long long prefix[2];
+  __shared__ int rank[2];
+  static_assert(VAD_THREADS == 256, "one thread per histogram bin");
+  const int utt = blockIdx.x;
+  const int len = lengths ? lengths[utt] : clip_len;
+  int nf = len > 0 ? (int)((2LL * len - 1) / (2LL * fsamp)) : 0;
+  if (nf > max_vf) nf = max_vf;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long* en = reinterpret_cast<const unsigned long long*>(energy_g) + (int64_t)utt * max_vf;
+  if (threadIdx.x < 2) {
+    prefix[threadIdx.x] = 0;
+    rank[threadIdx.x] = nf > 0 ? vad_rank(threadIdx.x ? rule.peak_q16 : rule.floor_q16, nf) : 0;
+  }
+  for (int shift = 40; nf > 0 && shift >= 0; shift -= 8) {   // (nf is uniform over the workgroup: so is every barrier)
+    hist[0][threadIdx.x] = 0;
+    hist[1][threadIdx.x] = 0;
+    __syncthreads();
+    const unsigned long long p0 = prefix[0] >> (shift + 8), p1 = prefix[1] >> (shift + 8);
+    for (int f = threadIdx.x; f < nf; f += VAD_THREADS) {
+      const unsigned long long k = en[f];
+      const unsigned digit = (unsigned)(k >> shift) & 255u;
+      if ((k >> (shift + 8)) == p0) atomicAdd(&hist[0][digit], 1u);
+      if ((k >> (shift + 8)) == p1) atomicAdd(&hist[1][digit], 1u);
+    }
+    __syncthreads();
+    if (wave < 2) {
+      // the keys that share the prefix hold the rank (true at the start: rank < nf; kept by every pass)
+      const unsigned r = (unsigned)rank[wave];
+      unsigned h[4], sum = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        h[i] = hist[wave][4 * lane + i];
+        sum += h[i];
+      }
+      unsigned incl = sum;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+      }
+      unsigned below = incl - sum;
+      if (below <= r && r < incl) {   // exactly one lane
+        int d = 4 * lane;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+          if (r >= below + h[i] && d == 4 * lane + i) {
+            below += h[i];
+            ++d;
+          }
+        prefix[wave] = (wave ? p1 : p0) << (shift + 8) | (unsigned long long)d << shift;
+        rank[wave] = (int)(r - below);
+      }
+    }
+    __syncthreads();
+  }
+  __syncthreads();
+  const unsigned long long e_lo = prefix[0], e_hi = prefix[1];
+  const long long t = vad_adaptive_threshold(e_lo, e_hi, rule, fsamp);
+  for (int f = threadIdx.x; f < nf; f += VAD_THREADS) flag_g[(int64_t)utt * max_vf + f] = (long long)en[f] > t ? 1 : 0;
+  if (threadIdx.x == 0 && rule.levels) {
+    rule.levels[3 * (int64_t)utt] = (long long)e_lo;
+    rule.levels[3 * (int64_t)utt + 1] = (long long)e_hi;
+    rule.levels[3 * (int64_t)utt + 2] = t;
+  }
+}
+
+// Which kernels serve a call (both entries).  Long clips: the phases as separate kernels cut into frame chunks (see
+// vad_flags_kernel); SVK_VAD_SPLIT=0 / 1 forces or forbids that route, 2 forces the general one-kernel path.
+enum VadRoute { VAD_ROUTE_SMALL, VAD_ROUTE_SPLIT, VAD_ROUTE_GENERAL };
+VadRoute vad_route(int n_utt, int frame_samples, int max_vad_frames) {
+  const char* force = getenv("SVK_VAD_SPLIT");
+  const bool usual = (frame_samples & 7) == 0 && (frame_samples >> 3) <= 64;
+  const bool split = usual && n_utt <= 65535 && (force ? force[0] == '1' : max_vad_frames > 512);
+  if (split && max_vad_frames > 0) return VAD_ROUTE_SPLIT;
+  if (usual && max_vad_frames <= VAD_SMALL && !(force && force[0] == '2')) return VAD_ROUTE_SMALL;
+  return VAD_ROUTE_GENERAL;
+}
+
 }  // namespace
 
 extern "C" int svk_vad_energy(svk_ctx* ctx, const int16_t* d_pcm, const int64_t* d_offsets, const int32_t* d_lengths,
@@ -514,11 +713,8 @@ extern "C" int svk_vad_energy(svk_ctx* ctx, const int16_t* d_pcm, const int64_t*
   if (max_vad_frames > MAX_VAD_FRAMES)
     return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "at most %d VAD frames per clip, got %d", MAX_VAD_FRAMES,
                     max_vad_frames);
-  // long clips: the three phases as three kernels cut into frame chunks (see vad_flags_kernel); SVK_VAD_SPLIT=0 / 1 forces a path
-  const char* force = getenv("SVK_VAD_SPLIT");
-  const bool usual = (frame_samples & 7) == 0 && (frame_samples >> 3) <= 64;
-  const bool split = usual && n_utt <= 65535 && (force ? force[0] == '1' : max_vad_frames > 512);
-  if (split && max_vad_frames > 0) {
+  const VadRoute route = vad_route(n_utt, frame_samples, max_vad_frames);
+  if (route == VAD_ROUTE_SPLIT) {
     const size_t flag_bytes = ((size_t)n_utt * max_vad_frames + 15) & ~(size_t)15;
     const size_t pos_bytes = d_voiced ? sizeof(int32_t) * (size_t)n_utt * max_vad_frames : 0;   // positions: only the copy reads them
     const int rc = svk_ensure_work(ctx, flag_bytes + pos_bytes);
@@ -539,16 +735,91 @@ extern "C" int svk_vad_energy(svk_ctx* ctx, const int16_t* d_pcm, const int64_t*
     }
     return SVK_OK;
   }
-  if (usual && max_vad_frames <= VAD_SMALL && !(force && force[0] == '2')) {   // (SVK_VAD_SPLIT=2 forces the general one-kernel path)
-    hipLaunchKernelGGL(vad_small_kernel, dim3(n_utt), dim3(VAD_THREADS), 0, ctx->stream, d_pcm, d_offsets, d_lengths, clip_stride,
+  if (route == VAD_ROUTE_SMALL) {
+    hipLaunchKernelGGL(vad_small_kernel<false>, dim3(n_utt), dim3(VAD_THREADS), 0, ctx->stream, d_pcm, d_offsets, d_lengths, clip_stride,
                        clip_len, frame_samples, ring_len, ring_thresh, (long long)threshold, max_vad_frames, d_keep, d_seg,
-                       d_n_vad_frames, d_voiced, d_voiced_len, d_src_frame);
+                       d_n_vad_frames, d_voiced, d_voiced_len, d_src_frame, VadAdaptive{});
     SVK_LAUNCH_CHECK(ctx);
     return SVK_OK;
   }
-  hipLaunchKernelGGL(vad_kernel, dim3(n_utt), dim3(VAD_THREADS), 0, ctx->stream, d_pcm, d_offsets, d_lengths, clip_stride,
+  hipLaunchKernelGGL(vad_kernel<false>, dim3(n_utt), dim3(VAD_THREADS), 0, ctx->stream, d_pcm, d_offsets, d_lengths, clip_stride,
                      clip_len, frame_samples, ring_len, ring_thresh, (long long)threshold, max_vad_frames, d_keep,
-                     d_seg, d_n_vad_frames, d_voiced, d_voiced_len, d_src_frame);
+                     d_seg, d_n_vad_frames, d_voiced, d_voiced_len, d_src_frame, (const uint8_t*)nullptr);
   SVK_LAUNCH_CHECK(ctx);
+  return SVK_OK;
+}
+
+extern "C" int svk_vad_adaptive(svk_ctx* ctx, const int16_t* d_pcm, const int64_t* d_offsets, const int32_t* d_lengths,
+                                int64_t clip_stride, int32_t clip_len, int32_t n_utt, int32_t frame_samples,
+                                int32_t ring_len, int32_t ring_thresh, int32_t floor_q16, int32_t peak_q16,
+                                int64_t above_floor_q16, int64_t below_peak_q16, int64_t min_threshold, int32_t max_vad_frames,
+                                uint8_t* d_keep, int32_t* d_seg, int32_t* d_n_vad_frames, int16_t* d_voiced,
+                                int32_t* d_voiced_len, int32_t* d_src_frame, int64_t* d_levels, int64_t* d_energy) {
+  if (!ctx) return SVK_ERR_BAD_ARG;
+  SVK_REQUIRE(ctx, n_utt >= 0 && frame_samples >= 1 && ring_len >= 1 && ring_thresh >= 0 && max_vad_frames >= 0,
+              "negative or zero geometry");
+  SVK_REQUIRE(ctx, floor_q16 >= 0 && floor_q16 <= 65536, "floor_q16 is outside [0, 65536]");
+  SVK_REQUIRE(ctx, peak_q16 >= 0 && peak_q16 <= 65536, "peak_q16 is outside [0, 65536]");
+  SVK_REQUIRE(ctx, floor_q16 <= peak_q16, "floor_q16 exceeds peak_q16");
+  SVK_REQUIRE(ctx, above_floor_q16 >= 65536 && above_floor_q16 <= (1LL << 40), "above_floor_q16 is outside [65536, 2^40]");
+  SVK_REQUIRE(ctx, below_peak_q16 >= 0 && below_peak_q16 <= 65536, "below_peak_q16 is outside [0, 65536]");
+  SVK_REQUIRE(ctx, min_threshold >= 0, "min_threshold is negative");
+  if (frame_samples > 65536)
+    return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "frame_samples of at most 65536 (the frame energies are 48-bit keys), got %d",
+                    frame_samples);
+  SVK_REQUIRE(ctx, min_threshold <= INT64_MAX / frame_samples, "min_threshold * frame_samples does not fit 63 bits");
+  if (n_utt == 0) return SVK_OK;
+  SVK_REQUIRE(ctx, d_pcm && d_keep, "d_pcm / d_keep is NULL");
+  SVK_REQUIRE(ctx, !d_voiced || d_voiced_len, "d_voiced needs d_voiced_len");
+  SVK_REQUIRE(ctx, !d_src_frame || d_voiced_len, "d_src_frame needs d_voiced_len");
+  SVK_REQUIRE(ctx, d_voiced != d_pcm, "d_voiced must not alias d_pcm");
+  if (max_vad_frames > MAX_VAD_FRAMES)
+    return svk_fail(ctx, SVK_ERR_UNSUPPORTED, "at most %d VAD frames per clip, got %d", MAX_VAD_FRAMES,
+                    max_vad_frames);
+  const VadAdaptive rule{floor_q16, peak_q16, (long long)above_floor_q16, (long long)below_peak_q16, (long long)min_threshold,
+                         reinterpret_cast<long long*>(d_levels), reinterpret_cast<long long*>(d_energy)};
+  const VadRoute route = vad_route(n_utt, frame_samples, max_vad_frames);
+  if (route == VAD_ROUTE_SMALL) {
+    hipLaunchKernelGGL(vad_small_kernel<true>, dim3(n_utt), dim3(VAD_THREADS), 0, ctx->stream, d_pcm, d_offsets, d_lengths, clip_stride,
+                       clip_len, frame_samples, ring_len, ring_thresh, 0LL, max_vad_frames, d_keep, d_seg, d_n_vad_frames, d_voiced,
+                       d_voiced_len, d_src_frame, rule);
+    SVK_LAUNCH_CHECK(ctx);
+    return SVK_OK;
+  }
+  // workspace: flags | packed positions (the split route's copy reads them) | frame energies (unless d_energy takes them)
+  const bool split = route == VAD_ROUTE_SPLIT;
+  const size_t cells = (size_t)n_utt * max_vad_frames;
+  const size_t flag_bytes = (cells + 15) & ~(size_t)15;
+  const size_t pos_bytes = split && d_voiced ? (sizeof(int32_t) * cells + 15) & ~(size_t)15 : 0;
+  const size_t energy_bytes = d_energy ? 0 : sizeof(long long) * cells;
+  const int rc = svk_ensure_work(ctx, flag_bytes + pos_bytes + energy_bytes);
+  if (rc != SVK_OK) return rc;
+  uint8_t* flag_g = reinterpret_cast<uint8_t*>(ctx->work);
+  int32_t* pos_g = pos_bytes ? reinterpret_cast<int32_t*>(flag_g + flag_bytes) : nullptr;
+  long long* energy_g = d_energy ? rule.energy : reinterpret_cast<long long*>(flag_g + flag_bytes + pos_bytes);
+  const int chunks = (max_vad_frames + VAD_CHUNK - 1) / VAD_CHUNK;
+  if (chunks > 0) {
+    hipLaunchKernelGGL(vad_energy_kernel, dim3(n_utt, chunks), dim3(VAD_THREADS), 0, ctx->stream, d_pcm, d_offsets, d_lengths,
+                       clip_stride, clip_len, frame_samples, max_vad_frames, split ? 1 : 0, energy_g);
+    SVK_LAUNCH_CHECK(ctx);
+  }
+  hipLaunchKernelGGL(vad_select_kernel, dim3(n_utt), dim3(VAD_THREADS), 0, ctx->stream, d_lengths, clip_len, frame_samples,
+                     max_vad_frames, rule, energy_g, flag_g);
+  SVK_LAUNCH_CHECK(ctx);
+  if (!split) {
+    hipLaunchKernelGGL(vad_kernel<true>, dim3(n_utt), dim3(VAD_THREADS), 0, ctx->stream, d_pcm, d_offsets, d_lengths, clip_stride,
+                       clip_len, frame_samples, ring_len, ring_thresh, 0LL, max_vad_frames, d_keep, d_seg, d_n_vad_frames, d_voiced,
+                       d_voiced_len, d_src_frame, flag_g);
+    SVK_LAUNCH_CHECK(ctx);
+    return SVK_OK;
+  }
+  hipLaunchKernelGGL(vad_walk_kernel, dim3(n_utt), dim3(64), 0, ctx->stream, d_lengths, clip_len, frame_samples, ring_len, ring_thresh,
+                     max_vad_frames, flag_g, pos_g, d_keep, d_seg, d_n_vad_frames, d_voiced_len, d_src_frame);
+  SVK_LAUNCH_CHECK(ctx);
+  if (d_voiced) {
+    hipLaunchKernelGGL(vad_copy_kernel, dim3(chunks, n_utt), dim3(VAD_THREADS), 0, ctx->stream, d_pcm, d_offsets, d_lengths, clip_stride,
+                       clip_len, frame_samples, max_vad_frames, pos_g, d_voiced);
+    SVK_LAUNCH_CHECK(ctx);
+  }
   return SVK_OK;
 }

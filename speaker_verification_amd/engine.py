@@ -479,14 +479,11 @@ class Engine:
         check(self.lib.svk_log_power(self.ctx, self._ptr(power), power.numel(), int(bool(normalize))), self.ctx)
         return power
 
-    def vad_energy(self, pcm, threshold, fs=16000, frame_ms=30, padding_ms=300, lengths=None, compact=True,
-                   want_segments=False, frame_samples=None, ring_len=None, offsets=None, voiced_out=None, longest=None):
-        """pcm [n_utt, L] int16 (or, with `offsets` + `lengths`, a 1-D concatenation of ragged clips) ->
-        dict(keep [n, F] u8, n_vad_frames [n] i32, voiced (same layout as pcm; a clip's samples past its
-        voiced_len are unspecified) i16, voiced_len [n] i32, seg [n, F] i32, src_frame).  compact=True copies the kept
-        frames to the front of `voiced`; compact="index" copies nothing and returns src_frame [n, F] i32 instead (entry q =
-        the q-th kept frame: `features(pcm, ..., lengths=voiced_len, gather=(src_frame, frame_samples))` reads through it).  `longest`: the longest clip in samples when
-        the caller knows it (device-side lengths would otherwise cost a host round trip to size the outputs)."""
+    def _vad_call(self, pcm, fs, frame_ms, padding_ms, lengths, compact, want_segments, frame_samples, ring_len, offsets,
+                  voiced_out, longest):
+        """What the two VAD entries share: geometry, output sizing and allocation.  -> (head, tail, result, max_vf, inputs): the
+        C-ABI arguments in front of the rule's parameters (pcm .. ring_thresh) and behind max_vad_frames (d_keep .. d_src_frame),
+        the dict of outputs, and the device inputs `head` points into (the caller holds them until the launch is queued)."""
         torch = _torch()
         x = self.to_device(pcm)
         if x.dtype != torch.int16:
@@ -531,12 +528,47 @@ class Engine:
             voiced = torch.empty_like(x) if compact else None
         vlen = torch.empty((n_utt,), dtype=torch.int32, device=self.device) if compact else None
         src = torch.empty((n_utt, max_vf), dtype=torch.int32, device=self.device) if index else None
+        head = (self._ptr(x), self._ptr(offs), self._ptr(lens), stride, longest, n_utt, fsamp, ring_len, ring_thresh)
+        tail = (self._ptr(keep), self._ptr(seg), self._ptr(nvf), self._ptr(voiced), self._ptr(vlen), self._ptr(src))
+        res = {"keep": keep, "n_vad_frames": nvf, "voiced": voiced, "voiced_len": vlen, "seg": seg,
+               "frame_samples": fsamp, "src_frame": src}
+        return head, tail, res, max_vf, (x, offs, lens)
+
+    def vad_energy(self, pcm, threshold, fs=16000, frame_ms=30, padding_ms=300, lengths=None, compact=True,
+                   want_segments=False, frame_samples=None, ring_len=None, offsets=None, voiced_out=None, longest=None):
+        """pcm [n_utt, L] int16 (or, with `offsets` + `lengths`, a 1-D concatenation of ragged clips) ->
+        dict(keep [n, F] u8, n_vad_frames [n] i32, voiced (same layout as pcm; a clip's samples past its
+        voiced_len are unspecified) i16, voiced_len [n] i32, seg [n, F] i32, src_frame).  compact=True copies the kept
+        frames to the front of `voiced`; compact="index" copies nothing and returns src_frame [n, F] i32 instead (entry q =
+        the q-th kept frame: `features(pcm, ..., lengths=voiced_len, gather=(src_frame, frame_samples))` reads through it).  `longest`: the longest clip in samples when
+        the caller knows it (device-side lengths would otherwise cost a host round trip to size the outputs)."""
+        head, tail, res, max_vf, _inputs = self._vad_call(pcm, fs, frame_ms, padding_ms, lengths, compact, want_segments,
+                                                          frame_samples, ring_len, offsets, voiced_out, longest)
         self._stream()
-        check(self.lib.svk_vad_energy(self.ctx, self._ptr(x), self._ptr(offs), self._ptr(lens), stride, longest, n_utt,
-                                      fsamp, ring_len, ring_thresh, int(threshold), max_vf, self._ptr(keep),
-                                      self._ptr(seg), self._ptr(nvf), self._ptr(voiced), self._ptr(vlen), self._ptr(src)), self.ctx)
-        return {"keep": keep, "n_vad_frames": nvf, "voiced": voiced, "voiced_len": vlen, "seg": seg,
-                "frame_samples": fsamp, "src_frame": src}
+        check(self.lib.svk_vad_energy(self.ctx, *head, int(threshold), max_vf, *tail), self.ctx)
+        return res
+
+    def vad_adaptive(self, pcm, vad, fs=16000, frame_ms=30, padding_ms=300, lengths=None, compact=True,
+                     want_segments=False, frame_samples=None, ring_len=None, offsets=None, voiced_out=None, longest=None,
+                     want_energy=False):
+        """`vad_energy` under the level-adaptive rule (svk_vad_adaptive, include/svk_vad.h): `vad` is a `vad.AdaptiveEnergyVad`
+        (anything with its five integer attributes floor_q16, peak_q16, above_floor_q16, below_peak_q16, min_threshold).  The
+        same arguments and the same dict, plus levels [n, 3] i64 = (E_lo, E_hi, T) per clip and, with want_energy, energy
+        [n, F] i64 (a clip's entries from its frame count on are unspecified)."""
+        torch = _torch()
+        head, tail, res, max_vf, _inputs = self._vad_call(pcm, fs, frame_ms, padding_ms, lengths, compact, want_segments,
+                                                          frame_samples, ring_len, offsets, voiced_out, longest)
+        n_utt = head[5]
+        levels = torch.empty((n_utt, 3), dtype=torch.int64, device=self.device)
+        energy = torch.empty((n_utt, max_vf), dtype=torch.int64, device=self.device) if want_energy else None
+        self._stream()
+        check(self.lib.svk_vad_adaptive(self.ctx, *head, int(vad.floor_q16), int(vad.peak_q16), int(vad.above_floor_q16),
+                                        int(vad.below_peak_q16), int(vad.min_threshold), max_vf, *tail, self._ptr(levels),
+                                        self._ptr(energy)), self.ctx)
+        res["levels"] = levels
+        if want_energy:
+            res["energy"] = energy
+        return res
 
     def draw_crops(self, n_frames, n_crops=20, crop_frames=80, seed=12345, first_utt=0, bad_count=None,
                    utt_index=None):

@@ -115,7 +115,7 @@ class VerificationPipeline:
     def __init__(self, model, use_vad=True, vad_threshold=c.VAD_ENERGY_THRESHOLD, normalize=c.NORMALIZE,
                  crop_seed=12345, micro_batch=1024, preemph_cof=None, crop_rng="reference", overlap_front=False,
                  pcm_scale=1.0 / 32768.0, cubes_per_clip=1, pool="mean", backend=None, plda=None,
-                 calibration=None, score_norm=None):
+                 calibration=None, score_norm=None, vad=None):
         """model: a `model.C3D2` with one channel, or with three (static, delta, delta-delta features: utils.py:325-348,
         :382-397; every method then carries [n, 3, T, 40] feature rows and [n, 3, 20, 80, 40] cubes): its inference form is
         `model.fused_inference()`, seven libsvk kernels.  Any other channel count raises ValueError.
@@ -151,7 +151,17 @@ class VerificationPipeline:
         score_norm: a `score_norm.ScoreNorm` fitted on a cohort with this pipeline's `backend` and `plda`, or None.  With one,
         `score` and `score_trials` normalise between the raw score and the calibration (svk_cohort_moments of both sides
         against the cohort, then svk_score_norm / svk_score_norm_pairs in place on the fresh scores; a calibration is then one
-        fitted on normalised scores); `search` raises ValueError.  None (the default) changes no code path."""
+        fitted on normalised scores); `search` raises ValueError.  None (the default) changes no code path.
+        vad: a `vad.AdaptiveEnergyVad`, or None.  With one, `voiced` and `vad` -- and so `embed`, the ragged and arena paths and
+        `diarize` -- decide by the level-adaptive rule (svk_vad_adaptive: thresholds from each clip's own frame-energy
+        quantiles) and `vad_threshold` is unused; together with use_vad=False it is a ValueError.  None (the default) is the
+        absolute rule: the same code path and the same bits as before."""
+        if vad is not None and not use_vad:
+            raise ValueError("vad= names the rule the VAD decides by; with use_vad=False there is no VAD to hand it to")
+        if vad is not None and not all(hasattr(vad, k) for k in ("floor_q16", "peak_q16", "above_floor_q16", "below_peak_q16",
+                                                                 "min_threshold")):
+            raise ValueError("vad must be a vad.AdaptiveEnergyVad or None, got %r" % (vad,))
+        self.adaptive_vad = vad
         self.channels = int(getattr(model, "num_channels", 0))
         if self.channels not in (1, 3):
             raise ValueError("VerificationPipeline runs C3D2 models with 1 or 3 input channels, got num_channels = %r"
@@ -222,9 +232,15 @@ class VerificationPipeline:
         """[n, L] int16 -> (packed voiced samples [n, L] int16, voiced_len [n] i32)."""
         if not self.use_vad:
             return pcm, None
-        res = self.eng.vad_energy(pcm, self.vad_threshold, fs=c.SAMPLE_RATE, frame_ms=c.VAD_FRAME_MS,
-                                  padding_ms=c.VAD_PADDING_MS, compact=True)
+        res = self._run_vad(pcm, compact=True)
         return res["voiced"], res["voiced_len"]
+
+    def _run_vad(self, pcm, **kw):
+        """The pipeline's VAD rule on its frame geometry: the absolute threshold, or the `vad=` the pipeline was built with."""
+        kw.update(fs=c.SAMPLE_RATE, frame_ms=c.VAD_FRAME_MS, padding_ms=c.VAD_PADDING_MS)
+        if self.adaptive_vad is not None:
+            return self.eng.vad_adaptive(pcm, self.adaptive_vad, **kw)
+        return self.eng.vad_energy(pcm, self.vad_threshold, **kw)
 
     def vad(self, pcm, lengths=None, offsets=None, longest=None):
         """The energy VAD WITHOUT the compaction copy: (voiced_len [n] i32, gather) where gather = (src_frame, frame_samples)
@@ -232,8 +248,7 @@ class VerificationPipeline:
         pipeline runs without VAD.  `voiced()` is the copying form (packed samples, for callers that want them)."""
         if not self.use_vad:
             return (None if lengths is None else lengths), None
-        res = self.eng.vad_energy(pcm, self.vad_threshold, fs=c.SAMPLE_RATE, frame_ms=c.VAD_FRAME_MS, padding_ms=c.VAD_PADDING_MS,
-                                  lengths=lengths, offsets=offsets, compact="index", longest=longest)
+        res = self._run_vad(pcm, lengths=lengths, offsets=offsets, compact="index", longest=longest)
         return res["voiced_len"], (res["src_frame"], res["frame_samples"])
 
     def features(self, pcm, lengths=None, gather=None):

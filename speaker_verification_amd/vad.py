@@ -9,6 +9,8 @@ by this build: `EnergyVad(threshold)`.  When `vad_collector` is handed an
 (`csrc/vad.hip`); any other object with an `is_speech` method is served by the
 host-side protocol loop, because an opaque Python callback cannot run on a GPU.
 `energy_vad_batch` is the batched entry point the pipeline uses.
+`AdaptiveEnergyVad` is the level-adaptive rule (`svk_vad_adaptive`): thresholds
+from each clip's own frame-energy quantiles, served on the device like `EnergyVad`.
 """
 import collections
 import contextlib
@@ -95,19 +97,72 @@ class EnergyVad(object):
         return res["keep"][:, 0].to("cpu").numpy().astype(bool)
 
 
+def db_to_q16(db):
+    """A power ratio given in dB (either sign) as the Q16 integer the device multiplies by: round(10^(dB / 10) * 65536)."""
+    return int(round(10.0 ** (float(db) / 10.0) * 65536.0))
+
+
+class AdaptiveEnergyVad(object):
+    """The level-adaptive rule of svk_vad_adaptive (include/svk_vad.h): a frame is speech when its energy exceeds
+    T = max(min(E_floor * above, E_peak * below), min_threshold * n), E_floor and E_peak being the `floor_quantile` and
+    `peak_quantile` order statistics of the CLIP's own frame energies -- at least `above_floor_db` above the clip's quiet
+    level, but no higher than `below_peak_db` below its loud level.  What webrtcvad.Vad(3) does for the reference (vad.py:90,152)
+    and `EnergyVad` does not: the decisions follow the recording level (exactly, for powers of two, while min_threshold is 0).
+    Holds the Q16 integers the device uses.  A clip with no speech at all is kept whole unless `min_threshold` (per sample,
+    like EnergyVad's threshold) sets an absolute floor."""
+
+    def __init__(self, floor_quantile=0.10, peak_quantile=0.95, above_floor_db=10.0, below_peak_db=25.0, min_threshold=0):
+        if not 0.0 <= floor_quantile <= peak_quantile <= 1.0:
+            raise ValueError("quantiles must satisfy 0 <= floor_quantile <= peak_quantile <= 1, got %r, %r"
+                             % (floor_quantile, peak_quantile))
+        if above_floor_db < 0 or below_peak_db < 0 or min_threshold < 0:
+            raise ValueError("above_floor_db, below_peak_db and min_threshold are not negative")
+        self.floor_q16 = int(round(floor_quantile * 65536))
+        self.peak_q16 = int(round(peak_quantile * 65536))
+        self.above_floor_q16 = db_to_q16(above_floor_db)
+        self.below_peak_q16 = db_to_q16(-below_peak_db)
+        if self.above_floor_q16 > 1 << 40:
+            raise ValueError("above_floor_db beyond 10 log10(2^24) = 72.2 dB, got %r" % (above_floor_db,))
+        self.min_threshold = int(min_threshold)
+
+    def is_speech(self, frame_bytes, sample_rate):
+        raise ValueError("AdaptiveEnergyVad decides from the levels of a whole clip; one frame has none.  Use speech_flags(frames, "
+                         "sample_rate), vad_collector or energy_vad_batch(..., vad=...)")
+
+    def speech_flags(self, frames, sample_rate):
+        """The decisions for ALL `frames` (equal-length `Frame`s) as ONE clip: its levels are those of the frames taken
+        together.  (One launch with a ring of one frame; the flags are E_f > T from its `energy` and `levels`, not `keep`: inside
+        one clip the collector also keeps the unvoiced frame that releases it.)"""
+        frames = list(frames)
+        if not frames:
+            return np.zeros((0,), dtype=bool)
+        n = len(frames[0].bytes) // 2
+        pcm = np.frombuffer(b"".join(f.bytes[:2 * n] for f in frames) + b"\0\0", dtype=np.int16)   # offset + n < len (Q12)
+        res = get_engine().vad_adaptive(pcm[None, :], self, fs=sample_rate, compact=False, frame_samples=n, ring_len=1,
+                                        want_energy=True)
+        return (res["energy"][0, :len(frames)] > res["levels"][0, 2]).to("cpu").numpy()
+
+
+def _device_vad(vad, pcm, **kw):
+    """Engine.vad_energy or Engine.vad_adaptive, by the kind of `vad`."""
+    if isinstance(vad, AdaptiveEnergyVad):
+        return get_engine().vad_adaptive(pcm, vad, **kw)
+    return get_engine().vad_energy(pcm, vad.threshold, **kw)
+
+
 def vad_collector(sample_rate, frame_duration_ms, padding_duration_ms, vad, frames):
     """Yield the voiced segments (bytes) of `frames` (vad.py:60-129): a ring
     buffer of padding/frame entries triggers when more than 90 % are voiced and
     releases when more than 90 % are unvoiced (Q13)."""
     frames = list(frames)
-    if isinstance(vad, EnergyVad):
+    if isinstance(vad, (EnergyVad, AdaptiveEnergyVad)):
         if not frames:
             return
         n = len(frames[0].bytes)
         audio = b"".join(f.bytes for f in frames) + b"\0\0"      # the framer needs offset + n < len
         pcm = np.frombuffer(audio, dtype=np.int16)
-        res = get_engine().vad_energy(pcm[None, :], vad.threshold, fs=sample_rate, frame_ms=frame_duration_ms,
-                                      padding_ms=padding_duration_ms, compact=False, want_segments=True)
+        res = _device_vad(vad, pcm[None, :], fs=sample_rate, frame_ms=frame_duration_ms, padding_ms=padding_duration_ms,
+                          compact=False, want_segments=True)
         seg = res["seg"][0].to("cpu").numpy()[:len(frames)]
         for k in range(int(seg.max()) + 1 if seg.size else 0):
             yield b"".join(frames[i].bytes for i in np.nonzero(seg == k)[0])
@@ -141,22 +196,23 @@ def vad_collector(sample_rate, frame_duration_ms, padding_duration_ms, vad, fram
 
 def energy_vad_batch(pcm, threshold=c.VAD_ENERGY_THRESHOLD, sample_rate=c.SAMPLE_RATE,
                      frame_duration_ms=c.VAD_FRAME_MS, padding_duration_ms=c.VAD_PADDING_MS, lengths=None,
-                     compact=True, want_segments=False):
+                     compact=True, want_segments=False, vad=None):
     """[n_utt, L] int16 clips -> dict of device tensors: keep mask per 30 ms
     frame, frames per clip, voiced samples packed to the front of each row and
-    their count (see Engine.vad_energy)."""
-    return get_engine().vad_energy(pcm, threshold, fs=sample_rate, frame_ms=frame_duration_ms,
-                                   padding_ms=padding_duration_ms, lengths=lengths, compact=compact,
-                                   want_segments=want_segments)
+    their count (see Engine.vad_energy).  vad: an `AdaptiveEnergyVad` decides in
+    place of `threshold` (Engine.vad_adaptive: the same dict plus `levels`)."""
+    return _device_vad(vad if vad is not None else EnergyVad(threshold), pcm, fs=sample_rate, frame_ms=frame_duration_ms,
+                       padding_ms=padding_duration_ms, lengths=lengths, compact=compact, want_segments=want_segments)
 
 
-def main(id_list=None, chunked_list='100_speakers_100_samples_chunked_ids.txt', threshold=c.VAD_ENERGY_THRESHOLD, batch=512):
+def main(id_list=None, chunked_list='100_speakers_100_samples_chunked_ids.txt', threshold=c.VAD_ENERGY_THRESHOLD, batch=512, vad=None):
     """vad.py:135-168, the file-driven chunker: every WAV named in the id list (`c.ROOT/100_first_ids_100_samples.txt`,
     the list the reference's second assignment leaves in effect) is read from `c.DATA_ORIGIN/wav/`, cut into its voiced
     segments (30 ms frames, 300 ms of padding) and written as `c.DATA_ORIGIN/wav_chunked/<name>_<i>.wav`; the new
     relative names go to `chunked_list` in the working directory.  The reference walks file by file and frame by frame
     through webrtcvad; here `batch` files share ONE ragged launch of the energy VAD (offsets / lengths into one buffer)
-    and the host only slices the segments out.  Returns the list of written names."""
+    and the host only slices the segments out.  vad: an `AdaptiveEnergyVad` decides in place of `threshold`.  Returns the list
+    of written names."""
     import os
     id_list = id_list or os.path.join(c.ROOT, '100_first_ids_100_samples.txt')
     train_files = [str(f) for f in np.atleast_1d(np.genfromtxt(id_list, dtype='str'))]
@@ -164,7 +220,6 @@ def main(id_list=None, chunked_list='100_speakers_100_samples_chunked_ids.txt', 
     from_path = os.path.join(c.DATA_ORIGIN, 'wav')
     os.makedirs(to_path, exist_ok=True)
     train_list = []
-    eng = get_engine()
     for lo in range(0, len(train_files), batch):
         names = train_files[lo:lo + batch]
         audio = [read_wave(os.path.join(from_path, f)) for f in names]
@@ -177,8 +232,8 @@ def main(id_list=None, chunked_list='100_speakers_100_samples_chunked_ids.txt', 
             buf = np.zeros((int(slots.sum()) if len(idx) else 0,), dtype=np.int16)
             for x, o in zip(pcm, offs):
                 buf[o:o + x.size] = x
-            res = eng.vad_energy(buf, threshold, fs=rate, frame_ms=c.VAD_FRAME_MS, padding_ms=c.VAD_PADDING_MS,
-                                 lengths=lens, offsets=offs, compact=False, want_segments=True)
+            res = _device_vad(vad if vad is not None else EnergyVad(threshold), buf, fs=rate, frame_ms=c.VAD_FRAME_MS,
+                              padding_ms=c.VAD_PADDING_MS, lengths=lens, offsets=offs, compact=False, want_segments=True)
             seg = res["seg"].to("cpu").numpy()
             n = res["frame_samples"]
             for row, k in enumerate(idx):
