@@ -145,13 +145,24 @@ int svk_spectrum(svk_ctx* ctx, const float* d_frames, int32_t n_frames, int32_t 
 /* processing.py:239-271 per clip: d_feat [n_utt][max_frames][n_cols], rows < n_frames[u]
  * (NULL = max_frames) are normalised in place; variance != 0 divides by (std + 2^-30).  Rows >= n_frames[u] are neither
  * read nor written (nor read by svk_cmvn_stats, svk_delta_cmvn_stats, svk_cmvnw and svk_delta_planes: what they hold reaches
- * no statistic). */
+ * no statistic).
+ * ONE CLIP, ONE RESULT (svk_cmvn, svk_cmvn_stats, svk_delta_cmvn_stats): a clip's statistics, and with them its normalised
+ * rows, are a function of its rows and its n_frames[u] -- not of max_frames, n_utt or the clip's place in the batch, to the
+ * last bit (tests/test_cmvn_route_invariance.py).  The launch is chosen by max_frames (above 1 024: chunks of 256 frames on
+ * separate workgroups, otherwise one workgroup per clip), the ORDER of the float64 sums by the clip's own frame count: up to
+ * 1 024 frames row group tr adds rows tr, tr + R, .. (R = 256 / min(n_cols, 256)) of the whole clip and the R partial sums
+ * are added in order; above that the same inside each chunk, and the chunks are added in order.  Two exceptions, neither on
+ * a path the pipeline takes: SVK_CMVN_SPLIT=0 / 1 in the environment (read at every call) forces a launch for tests, and 0
+ * sums a clip of more than 1 024 frames in the one-workgroup order; with more than 65 535 clips in one call the chunked
+ * launch does not fit the grid and every clip is summed in the one-workgroup order, so a clip of more than 1 024 frames
+ * then differs from itself in a smaller call in the last bits of 1 / (std + 2^-30). */
 int svk_cmvn(svk_ctx* ctx, float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
              const int32_t* d_n_frames, int32_t variance);
 /* The same statistics WITHOUT applying them: d_stats float64 [n_utt][2][n_cols], [u][0][c] = mean, [u][1][c] =
  * 1 / (std + 2^-30) (1 when variance == 0) over rows < n_frames[u]; clips with no rows are left untouched.  utils.py:382-397
  * (CMVN) feeds utils.py:351-379 (FeatureCube), which reads 20 x 80 rows of a clip: svk_cube_gather_cmvn below applies the
- * normalisation to just those rows on the way, instead of a pass over every row of a 145 s clip. */
+ * normalisation to just those rows on the way, instead of a pass over every row of a 145 s clip.  The statistics are
+ * svk_cmvn's own, bit for bit, and depend on the clip alone (ONE CLIP, ONE RESULT above). */
 int svk_cmvn_stats(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
                    const int32_t* d_n_frames, int32_t variance, double* d_stats);
 
@@ -168,7 +179,8 @@ int svk_mel_features(svk_ctx* ctx, const float* d_power, int32_t n_frames, int32
  * (population std of the window over the MEAN-SUBTRACTED rows, padded the same way, + 2^-30).
  * d_in / d_out / d_tmp: [n_utt][max_frames][n_cols] float32, all distinct; d_tmp is a workspace, only needed
  * (and only written, in rows < n_frames[u] at most) when variance != 0: with variance == 0 it may be NULL and is left
- * untouched.  Rows >= n_frames[u] are left untouched in d_out. */
+ * untouched.  Rows >= n_frames[u] are left untouched in d_out.  The kernel is chosen by max_frames (up to 3 900: prefix sums,
+ * above: a sliding sum), so a clip's result may depend on the launch in the last bits; svk_cmvnw is not on the embedding path. */
 int svk_cmvnw(svk_ctx* ctx, const float* d_in, int32_t n_utt, int32_t max_frames, int32_t n_cols,
               const int32_t* d_n_frames, int32_t win, int32_t variance, float* d_tmp, float* d_out);
 /* processing.py:201-236 (derivative_extraction) exactly as the reference computes it, Q11 included:
@@ -230,7 +242,8 @@ int svk_cube_gather_cmvn(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32
  * d_stats float64 [n_utt][3][2][n_cols]: for channel ch (0 static, 1 delta, 2 delta-delta)
  * [u][ch][0][c] = mean, [u][ch][1][c] = 1 / (std + 2^-30) (1 when variance == 0) over rows < n_frames[u]; clips with no
  * rows are left untouched.  ONE pass over d_feat [n_utt][max_frames][n_cols]; bit-identical to svk_cmvn_stats on plane ch
- * of svk_delta_planes (the same launch paths, SVK_CMVN_SPLIT included, the same summation order). */
+ * of svk_delta_planes (the same launch paths, SVK_CMVN_SPLIT included, the same summation order), and like them a function
+ * of the clip's rows and n_frames[u] alone, whatever max_frames, n_utt and the clip's place (ONE CLIP, ONE RESULT at svk_cmvn). */
 int svk_delta_cmvn_stats(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
                          const int32_t* d_n_frames, int32_t delta, int32_t variance, double* d_stats);
 /* d_out [n_utt][3][max_frames][n_cols] (svk_c3d2_stage1_c3's d_feat layout): plane 0 = d_feat, 1 = derivative(d_feat),

@@ -307,6 +307,46 @@ __device__ __forceinline__ double cmvn_inv_std(double q, double mean, int T) {
 }
 __device__ __forceinline__ float cmvn_apply(float v, double mean, double inv) { return (float)(((double)v - mean) * inv); }
 
+// A clip's statistics are a function of its rows and its n_frames alone -- not of max_frames, n_utt or its place in the
+// batch (svk.h, svk_cmvn).  So the ORDER of the sums is chosen by the clip's own frame count, whatever launch carries it:
+// up to CMVN_WHOLE frames row group tr adds the rows tr, tr + R, .. of the whole clip (cmvn_rows) and the R partial sums
+// are added in order; above it the same happens inside each chunk of CMVN_CHUNK frames and the chunks are added in order.
+constexpr int CMVN_WHOLE = 1024;
+// rows tr, tr + R, .. < T of one column, in row order; four rows' loads in flight per thread (one load per trip followed
+// by its own use left the pass latency-bound: 1.3 TB/s on 7 s clips)
+__device__ __forceinline__ void cmvn_rows(const float* __restrict__ col, int tr, int R, int T, int ncols, double& s1, double& s2) {
+  int t = tr;
+  for (; t + 3 * R < T; t += 4 * R) {
+    const float v0 = col[(int64_t)t * ncols], v1 = col[(int64_t)(t + R) * ncols], v2 = col[(int64_t)(t + 2 * R) * ncols],
+                v3 = col[(int64_t)(t + 3 * R) * ncols];
+    cmvn_acc(s1, s2, v0);
+    cmvn_acc(s1, s2, v1);
+    cmvn_acc(s1, s2, v2);
+    cmvn_acc(s1, s2, v3);
+  }
+  for (; t < T; t += R) cmvn_acc(s1, s2, col[(int64_t)t * ncols]);
+}
+// the same walk over the three channels of svk_delta_cmvn_stats (values: delta_channels)
+__device__ __forceinline__ void delta_cmvn_rows(const float* __restrict__ base, int c, int tr, int R, int T, int ncols, int delta,
+                                                float inv_scale, double (&s1)[3], double (&s2)[3]) {
+  int t = tr;
+  for (; t + 3 * R < T; t += 4 * R) {   // four rows in flight, summed in row order (cmvn_rows)
+    float v[4][3];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) delta_channels(base + (int64_t)(t + j * R) * ncols, c, ncols, delta, inv_scale, v[j]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) cmvn_acc(s1[ch], s2[ch], v[j][ch]);
+  }
+  for (; t < T; t += R) {
+    float v[3];
+    delta_channels(base + (int64_t)t * ncols, c, ncols, delta, inv_scale, v);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) cmvn_acc(s1[ch], s2[ch], v[ch]);
+  }
+}
+
 // ---- CMVN: one workgroup per clip ------------------------------------------------------
 // Threads form a [R rows][cb cols] grid over a column block; column sums are kept in float64.
 // APPLY = false: the clip's statistics only, stats[utt][0][c] = mean, stats[utt][1][c] = 1 / (std + 2^-30) (svk_cmvn_stats:
@@ -329,21 +369,7 @@ __global__ __launch_bounds__(256) void cmvn_kernel(float* __restrict__ feat, int
     // ONE pass: column sums and sums of squares in float64 (the long-clip path's formula: var = E[x^2] - mean^2; for log-mel /
     // cepstral magnitudes the cancellation costs ~1e-14 relative in float64, far below the float32 the result is stored in)
     double s1 = 0.0, s2 = 0.0;
-    if (active) {
-      // four rows' loads in flight per thread (one load per trip followed by its own use left the pass latency-bound:
-      // 1.3 TB/s on 7 s clips); the sums stay in row order
-      const float* col = base + c0 + tc;
-      int t = tr;
-      for (; t + 3 * R < T; t += 4 * R) {
-        const float v0 = col[(int64_t)t * ncols], v1 = col[(int64_t)(t + R) * ncols], v2 = col[(int64_t)(t + 2 * R) * ncols],
-                    v3 = col[(int64_t)(t + 3 * R) * ncols];
-        cmvn_acc(s1, s2, v0);
-        cmvn_acc(s1, s2, v1);
-        cmvn_acc(s1, s2, v2);
-        cmvn_acc(s1, s2, v3);
-      }
-      for (; t < T; t += R) cmvn_acc(s1, s2, col[(int64_t)t * ncols]);
-    }
+    if (active) cmvn_rows(base + c0 + tc, tr, R, T, ncols, s1, s2);
     red[threadIdx.x] = active ? s1 : 0.0;
     __syncthreads();
     double mean = 0.0;
@@ -399,6 +425,10 @@ __global__ __launch_bounds__(256) void cmvn_partial_kernel(const float* __restri
   const int utt = blockIdx.y, chunk = blockIdx.x;
   int T = n_frames ? n_frames[utt] : max_frames;
   T = T < max_frames ? T : max_frames;
+  // a clip of up to CMVN_WHOLE frames: its chunk-0 workgroup sums ALL its rows in cmvn_kernel's order (the bits the clip
+  // gives in a launch of short clips), its other chunks have nothing to add (cmvn_stats_kernel reads chunk 0 alone)
+  const bool whole = T <= CMVN_WHOLE;
+  if (whole && chunk > 0) return;
   const int t0 = chunk * CMVN_CHUNK, t1 = min(T, t0 + CMVN_CHUNK);
   const float* base = feat + (int64_t)utt * max_frames * ncols;
   double* out = part + ((int64_t)utt * n_chunks + chunk) * 2 * ncols;
@@ -406,8 +436,12 @@ __global__ __launch_bounds__(256) void cmvn_partial_kernel(const float* __restri
     const int cb = min(256, ncols - c0), R = 256 / cb;
     const int tc = threadIdx.x % cb, tr = threadIdx.x / cb;
     double s = 0.0, q = 0.0;
-    if (tr < R)
-      for (int t = t0 + tr; t < t1; t += R) cmvn_acc(s, q, base[(int64_t)t * ncols + c0 + tc]);
+    if (tr < R) {
+      if (whole)
+        cmvn_rows(base + c0 + tc, tr, R, T, ncols, s, q);
+      else
+        for (int t = t0 + tr; t < t1; t += R) cmvn_acc(s, q, base[(int64_t)t * ncols + c0 + tc]);
+    }
     red[0][threadIdx.x] = tr < R ? s : 0.0;
     red[1][threadIdx.x] = tr < R ? q : 0.0;
     __syncthreads();
@@ -432,7 +466,7 @@ __global__ __launch_bounds__(256) void cmvn_stats_kernel(const double* __restric
   int T = n_frames ? n_frames[utt / planes] : max_frames;
   T = T < max_frames ? T : max_frames;
   if (T <= 0) return;
-  const int used = (T + CMVN_CHUNK - 1) / CMVN_CHUNK;
+  const int used = T <= CMVN_WHOLE ? 1 : (T + CMVN_CHUNK - 1) / CMVN_CHUNK;   // cmvn_partial_kernel: chunk 0 holds a short clip
   for (int c = threadIdx.x; c < ncols; c += 256) {
     double s = 0.0, q = 0.0;
     for (int k = 0; k < used; ++k) {        // fixed order: repeatable
@@ -959,24 +993,7 @@ __global__ __launch_bounds__(256) void delta_cmvn_kernel(const float* __restrict
     const int tc = threadIdx.x % cb, tr = threadIdx.x / cb;
     const bool active = tr < R;
     double s1[3] = {0.0, 0.0, 0.0}, s2[3] = {0.0, 0.0, 0.0};
-    if (active) {
-      int t = tr;
-      for (; t + 3 * R < T; t += 4 * R) {   // four rows in flight, summed in row order (cmvn_kernel)
-        float v[4][3];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) delta_channels(base + (int64_t)(t + j * R) * ncols, c0 + tc, ncols, delta, inv_scale, v[j]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) cmvn_acc(s1[ch], s2[ch], v[j][ch]);
-      }
-      for (; t < T; t += R) {
-        float v[3];
-        delta_channels(base + (int64_t)t * ncols, c0 + tc, ncols, delta, inv_scale, v);
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) cmvn_acc(s1[ch], s2[ch], v[ch]);
-      }
-    }
+    if (active) delta_cmvn_rows(base, c0 + tc, tr, R, T, ncols, delta, inv_scale, s1, s2);
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
       red[threadIdx.x] = active ? s1[ch] : 0.0;
@@ -1015,19 +1032,25 @@ __global__ __launch_bounds__(256) void delta_cmvn_partial_kernel(const float* __
   const int utt = blockIdx.y, chunk = blockIdx.x;
   int T = n_frames ? n_frames[utt] : max_frames;
   T = T < max_frames ? T : max_frames;
+  const bool whole = T <= CMVN_WHOLE;   // cmvn_partial_kernel: a short clip is summed by its chunk 0, in delta_cmvn_kernel's order
+  if (whole && chunk > 0) return;
   const int t0 = chunk * CMVN_CHUNK, t1 = min(T, t0 + CMVN_CHUNK);
   const float* base = feat + (int64_t)utt * max_frames * ncols;
   for (int c0 = 0; c0 < ncols; c0 += 256) {
     const int cb = min(256, ncols - c0), R = 256 / cb;
     const int tc = threadIdx.x % cb, tr = threadIdx.x / cb;
     double s[3] = {0.0, 0.0, 0.0}, q[3] = {0.0, 0.0, 0.0};
-    if (tr < R)
-      for (int t = t0 + tr; t < t1; t += R) {
-        float v[3];
-        delta_channels(base + (int64_t)t * ncols, c0 + tc, ncols, delta, inv_scale, v);
+    if (tr < R) {
+      if (whole)
+        delta_cmvn_rows(base, c0 + tc, tr, R, T, ncols, delta, inv_scale, s, q);
+      else
+        for (int t = t0 + tr; t < t1; t += R) {
+          float v[3];
+          delta_channels(base + (int64_t)t * ncols, c0 + tc, ncols, delta, inv_scale, v);
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) cmvn_acc(s[ch], q[ch], v[ch]);
-      }
+          for (int ch = 0; ch < 3; ++ch) cmvn_acc(s[ch], q[ch], v[ch]);
+        }
+    }
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
       red[0][threadIdx.x] = tr < R ? s[ch] : 0.0;
@@ -1346,7 +1369,9 @@ static int cmvn_launch(svk_ctx* ctx, float* d_feat, int32_t n_utt, int32_t max_f
   SVK_REQUIRE(ctx, n_utt >= 0 && max_frames >= 0 && n_cols >= 0, "negative shape");
   if (n_utt == 0 || max_frames == 0 || n_cols == 0) return SVK_OK;
   SVK_REQUIRE(ctx, d_feat, "NULL buffer");
-  // long clips: chunks of a clip go to separate workgroups (see cmvn_partial_kernel); SVK_CMVN_SPLIT=0 / 1 forces a path
+  // long clips: chunks of a clip go to separate workgroups (see cmvn_partial_kernel); SVK_CMVN_SPLIT=0 / 1 forces a path.
+  // max_frames picks the LAUNCH only: the order of a clip's sums follows its own frame count on either (CMVN_WHOLE), except
+  // where a clip of more than CMVN_WHOLE frames lands on cmvn_kernel (SVK_CMVN_SPLIT=0, or more clips than gridDim.y holds)
   const char* force = getenv("SVK_CMVN_SPLIT");
   const bool split = force ? force[0] == '1' : max_frames > 1024;
   if (split && n_utt <= 65535) {

@@ -306,9 +306,14 @@ class VerificationPipeline:
         network: what BatchNorm calibration and the parity legs feed to the CPU oracle.  With cubes_per_clip = K > 1: crop starts
         [n, K, 20] and cubes [n, K, channels, 20, 80, 40]."""
         pcm = self.eng.to_device(pcm)
-        crops, cubes = [], []
+        crops, cubes, done = [], [], 0
         for lo, hi in self.chunks(pcm.shape[0]):
             feat, _, idx = self._front(pcm[lo:hi], first_utt + lo)
+            if lo < done:                              # the shifted last chunk redoes clips lo .. done - 1: its rows replace them
+                crops[-1] = crops[-1][:len(crops[-1]) - (done - lo)]
+                if want_cubes:
+                    cubes[-1] = cubes[-1][:len(cubes[-1]) - (done - lo)]
+            done = hi
             if want_cubes:
                 cubes.append(self.cubes(feat, idx))
             crops.append(idx.cpu().numpy() if hasattr(idx, "cpu") else np.asarray(idx))
@@ -503,8 +508,11 @@ class VerificationPipeline:
         dev_lens, gather = lens, None
         if self.use_vad:
             dev_lens, gather = timed("vad", lambda: self.vad(dev_buf, lengths=lens, offsets=offs, longest=longest))
+        # (at least one crop's worth of rows: the gathers refuse a feature buffer shorter than a crop, and a batch may hold
+        # nothing but clips that are too short to crop -- their starts are -1, their cubes zeros, rows past n_frames are zeros)
+        max_frames = max(self.spec.num_frames(int(longest)), c.CUBE_FRAMES)
         feat, n_frames, _ = timed("frontend", lambda: self.eng.features(dev_buf, self.spec, lengths=dev_lens, offsets=offs,
-                                                                         max_frames=self.spec.num_frames(int(longest)), gather=gather))
+                                                                         max_frames=max_frames, gather=gather))
         cmvn_stats = self.eng.delta_cmvn_stats if self.channels == 3 else self.eng.cmvn_stats
         stats = timed("cmvn", lambda: cmvn_stats(feat, n_frames, variance=True)) if self.normalize else None
         idx = crops if crops is not None else timed("crops", lambda: self.eng.draw_crops(

@@ -1,6 +1,6 @@
 """Float64 references, error bars, CPU emulations and mutants for the feature post-processing kernels of csrc/stages.hip
 (svk_cmvn, svk_cmvn_stats, svk_cmvnw, svk_derivative, svk_log_power, svk_cube_gather[_cmvn], svk_cube_draw_crops).  Used by
-tests/test_postprocessing_float64.py.
+tests/test_postprocessing_float64.py and tests/test_cmvn_route_invariance.py (the two summation orders of the CMVN kernels).
 
 THE BARS.  ulp32(v) is the float32 spacing at |v|.  The CMVN kernels compute in float64 and round to float32 once (cmvnw with
 variance: twice, the centred rows are stored as float32 between the passes).  A kernel's float64 sums differ from the
@@ -102,6 +102,56 @@ def emul_cmvn(x32, variance, mut=None):
             inv = 1.0 / (np.sqrt(var) + (2.0 ** -20 if mut == "eps20" else EPS))
         out[:, c0:c0 + cb] = ((x - mean) * inv).astype(np.float32)
     return out
+
+
+CMVN_CHUNK = 256               # frames per workgroup of cmvn_partial_kernel
+CMVN_WHOLE = 1024              # clips of up to this many frames are summed whole, in cmvn_kernel's order, on every route
+
+
+def _ordered_sums(x, R):
+    """Column sums and sums of squares of x [T, cb] float64 as one workgroup forms them: row group tr adds the rows tr, tr + R, ..
+    in order, then the R partial sums are added in order.  -> (s [cb], q [cb])"""
+    T, cb = x.shape
+    s1 = np.zeros((R, cb))
+    s2 = np.zeros((R, cb))
+    for tr in range(min(R, T)):
+        rows = x[tr::R]
+        s1[tr] = np.cumsum(rows, axis=0)[-1]                         # cumsum adds in order
+        s2[tr] = np.cumsum(rows * rows, axis=0)[-1]                  # the square of a float32 is exact in float64: fused or not
+    return np.cumsum(s1, axis=0)[-1], np.cumsum(s2, axis=0)[-1]
+
+
+def emul_cmvn_sums(x32, order):
+    """The float64 column sums behind a clip's CMVN statistics, in one of the two orders the kernels know.  order = "whole":
+    cmvn_kernel's (and, for clips of up to CMVN_WHOLE frames, the chunk-0 workgroup's of the split launch); order = "chunked":
+    cmvn_partial_kernel's inside each chunk of CMVN_CHUNK frames, the chunks then added in order (cmvn_stats_kernel).
+    -> (s [C], q [C]); mean = s / T."""
+    x32 = np.asarray(x32, dtype=np.float32)
+    T, C = x32.shape
+    s, q = np.zeros(C), np.zeros(C)
+    for c0 in range(0, C, 256):
+        cb = min(256, C - c0)
+        x = x32[:, c0:c0 + cb].astype(np.float64)
+        if order == "whole":
+            s[c0:c0 + cb], q[c0:c0 + cb] = _ordered_sums(x, 256 // cb)
+        else:
+            assert order == "chunked"
+            parts = [_ordered_sums(x[t0:t0 + CMVN_CHUNK], 256 // cb) for t0 in range(0, T, CMVN_CHUNK)]
+            s[c0:c0 + cb] = np.cumsum(np.stack([p[0] for p in parts]), axis=0)[-1]
+            q[c0:c0 + cb] = np.cumsum(np.stack([p[1] for p in parts]), axis=0)[-1]
+    return s, q
+
+
+def cmvn_order(T):
+    """The order a clip's own frame count selects (csrc/stages.hip, CMVN_WHOLE)."""
+    return "whole" if T <= CMVN_WHOLE else "chunked"
+
+
+def ulp64_distance(a, b):
+    """Element-wise distance of two float64 arrays in units of the last place (same-sign finite values)."""
+    a = np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+    b = np.ascontiguousarray(b, dtype=np.float64).view(np.int64)
+    return np.abs(a - b)
 
 
 # ---- cmvnw ------------------------------------------------------------------------------------------------------------

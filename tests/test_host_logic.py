@@ -424,50 +424,104 @@ def test_upload_groups_of_a_host_arena():
 def test_cube_ring_runs_every_clip_once_in_bounded_memory():
     """`VerificationPipeline._CubeRing` (the ragged paths): batches of any size <= step gather into a ring of 2 x step cubes,
     the network runs over `step` cubes at a time, segments never wrap, and every clip's embedding lands in its own row --
-    here with a host stand-in for the two device calls."""
+    here with host stand-ins for the device calls: one channel and three (`cube_gather_delta`), K = 1, 2 and 3 cubes per clip,
+    without statistics and with them.  Every clip has statistics of its own, so a push that hands the wrong slice of `stats`
+    to either of its two gathers (the second one fills the ring's head when a batch wraps) gives wrong rows.  All values are
+    small integers and the scales powers of two: every stand-in result is exact, whatever the order of its sums."""
     import types
     from speaker_verification_amd import constants as c
     from speaker_verification_amd.pipeline import VerificationPipeline
-    launches = []
+    CF, NC = c.CUBE_FRAMES, c.CUBE_CROPS
+    weight = (torch.arange(NC * CF, dtype=torch.float64) + 1.0).view(NC, CF, 1)
 
-    class Eng:
-        device = torch.device("cpu")
+    def cube_of(rows, starts, ch, st):
+        """[20, 80, 40] of channel ch: (rows (ch + 1) - mean) inv at the 20 starts; st [2, 40] or None."""
+        out = torch.stack([rows[int(b):int(b) + CF] for b in starts]) * float(ch + 1)
+        return out if st is None else (out - st[0].float()) * st[1].float()
 
-        @staticmethod
-        def cube_gather(feat, idx, frames, out=None, stats=None):
-            assert stats is None
-            for u in range(feat.shape[0]):
-                for k in range(idx.shape[1]):
-                    out[u, 0, k] = feat[u, idx[u, k]:idx[u, k] + frames]
-            return out
+    def digest(cubes):
+        """[n, channels, 20, 80, 40] -> [n, 128]: a position-weighted sum per channel and column (exact in float64)."""
+        n = cubes.shape[0]
+        d = (cubes.double() * weight).sum((2, 3)).reshape(n, -1).float()
+        return torch.cat([d, torch.zeros((n, 128 - d.shape[1]))], 1)
 
-    def embed_features(rows, starts):
-        launches.append(rows.shape[0])
-        assert torch.equal(starts[0], torch.arange(c.CUBE_CROPS, dtype=torch.int32) * c.CUBE_FRAMES)
-        return rows.reshape(rows.shape[0], -1)[:, :128].clone()
+    for channels, K, with_stats in ((1, 1, False), (1, 1, True), (1, 3, True), (3, 1, True), (3, 2, True)):
+        launches, gathers = [], []
 
-    pipe = types.SimpleNamespace(eng=Eng, embed_features=embed_features,
-                                 embedder=types.SimpleNamespace(crop_starts=lambda n, dev: (torch.arange(c.CUBE_CROPS, dtype=torch.int32)
-                                                                                            * c.CUBE_FRAMES)[None].expand(n, -1).contiguous()))
-    rng = np.random.default_rng(5)
-    sizes = [3, 4, 1, 4, 4, 2, 4, 3, 4, 4, 1]                            # 34 clips, step 4: the ring (8 cubes) wraps several times
-    n = sum(sizes)
-    order = torch.from_numpy(rng.permutation(n))
-    emb = torch.full((n, 128), float("nan"))
-    ring = VerificationPipeline._CubeRing(pipe, 4, emb, order, None)
-    assert ring.cubes.shape[0] == 8
-    pos, want = 0, torch.empty((n, 128))
-    for m in sizes:
-        feat = torch.from_numpy(rng.standard_normal((m, 90, c.NUM_COEF)).astype(np.float32))
-        idx = torch.from_numpy(rng.integers(0, 10, size=(m, c.CUBE_CROPS)).astype(np.int32))
-        for u in range(m):
-            want[order[pos + u]] = feat[u, idx[u, 0]:idx[u, 0] + c.CUBE_FRAMES].reshape(-1)[:128]
-        ring.push(feat, idx)
-        assert ring.at - ring.done < 4                                   # never more than a step pending
-        pos += m
-    ring.finish()
-    assert torch.equal(emb, want)
-    assert launches == [4] * 8 + [2] and ring.done == ring.at == n
+        class Eng:
+            device = torch.device("cpu")
+
+            @staticmethod
+            def cube_gather(feat, idx, frames, out=None, stats=None):
+                m = feat.shape[0]
+                assert channels == 1 and idx.shape == (m, NC * K) and tuple(out.shape) == (m * K, 1, NC, CF, c.NUM_COEF)
+                assert (stats is None) == (not with_stats) and (stats is None or tuple(stats.shape) == (m, 2, c.NUM_COEF))
+                gathers.append(m)
+                wide = out.view(m, NC * K, CF, c.NUM_COEF)          # [m, 1, 20 K, 80, 40] as it lies
+                for u in range(m):
+                    for k in range(K):
+                        wide[u, NC * k:NC * (k + 1)] = cube_of(feat[u], idx[u, NC * k:NC * (k + 1)], 0, None if stats is None else stats[u])
+                return out
+
+            @staticmethod
+            def cube_gather_delta(feat, idx, frames, stats=None, out=None):
+                m = feat.shape[0]
+                assert channels == 3 and idx.shape == (m, NC * K) and tuple(stats.shape) == (m, 3, 2, c.NUM_COEF)
+                assert (out is None) == (K > 1)                      # K > 1: the ring permutes the wide cube into place itself
+                gathers.append(m)
+                wide = torch.empty((m, 3, NC * K, CF, c.NUM_COEF))
+                for u in range(m):
+                    for ch in range(3):
+                        for k in range(K):
+                            wide[u, ch, NC * k:NC * (k + 1)] = cube_of(feat[u], idx[u, NC * k:NC * (k + 1)], ch, stats[u, ch])
+                if out is None:
+                    return wide
+                out.copy_(wide)
+                return out
+
+        def embed_features(rows, starts):
+            launches.append(rows.shape[0])
+            assert torch.equal(starts[0], torch.arange(NC, dtype=torch.int32) * CF)
+            assert tuple(rows.shape[1:]) == ((3,) if channels == 3 else ()) + (NC * CF, c.NUM_COEF)
+            return digest(rows.reshape(rows.shape[0], channels, NC, CF, c.NUM_COEF))
+
+        pipe = types.SimpleNamespace(eng=Eng, embed_features=embed_features, channels=channels,
+                                     embedder=types.SimpleNamespace(crop_starts=lambda n, dev: (torch.arange(NC, dtype=torch.int32)
+                                                                                                * CF)[None].expand(n, -1).contiguous()))
+        rng = np.random.default_rng(5)
+        sizes = [3, 4, 1, 4, 4, 2, 4, 3, 4, 4, 1]                        # 34 clips, step 4 clips: the ring (8 clips) wraps several times
+        n = sum(sizes)
+        order = torch.from_numpy(rng.permutation(n))
+        order_cubes = (order[:, None] * K + torch.arange(K)[None, :]).reshape(-1)
+        emb = torch.full((n * K, 128), float("nan"))
+        ring = VerificationPipeline._CubeRing(pipe, 4 * K, emb, order_cubes, None, K)
+        assert ring.cubes.shape[:2] == (8 * K, channels) and ring.step == 4 * K
+        pos, want, wrapped = 0, torch.empty((n * K, 128)), 0
+        for m in sizes:
+            feat = torch.from_numpy(rng.integers(-50, 50, size=(m, 90, c.NUM_COEF)).astype(np.float32))
+            idx = torch.from_numpy(rng.integers(0, 10, size=(m, NC * K)).astype(np.int32))
+            stats = None
+            if with_stats:                                               # integer means, power-of-two scales, different for every clip
+                shape = (m, 2, c.NUM_COEF) if channels == 1 else (m, 3, 2, c.NUM_COEF)
+                stats = torch.from_numpy(rng.integers(-9, 9, size=shape).astype(np.float64))
+                stats[..., 1, :] = torch.from_numpy(2.0 ** rng.integers(-2, 3, size=shape[:-2] + (c.NUM_COEF,)))
+            for u in range(m):
+                for k in range(K):
+                    cube = torch.stack([cube_of(feat[u], idx[u, NC * k:NC * (k + 1)], ch,
+                                                None if stats is None else (stats[u] if channels == 1 else stats[u, ch]))
+                                        for ch in range(channels)])
+                    want[int(order[pos + u]) * K + k] = digest(cube[None])[0]
+            before = len(gathers)
+            ring.push(feat, idx, stats)
+            assert sum(gathers[before:]) == m
+            wrapped += len(gathers) - before == 2
+            assert ring.at - ring.done < 4 * K                           # never more than a step pending
+            pos += m
+        ring.finish()
+        assert torch.equal(emb, want), (channels, K, with_stats)
+        assert launches == [4 * K] * 8 + [2 * K] and ring.done == ring.at == n * K
+        ends = np.cumsum(sizes)                                          # a push wraps when it crosses a multiple of the ring's 8 clips
+        assert wrapped == sum(1 for e, m in zip(ends, sizes) if (e - m) % 8 + m > 8) == 2
 
 
 def test_bench_result_line_and_detail_record():
