@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsvk.so")
 
 SVK_OK = 0
-VERSION = 114                      # include/svk.h SVK_VERSION (0.1.12: + svk_vad_adaptive in include/svk_vad.h, number unchanged; + svk_spectral_embed, svk_spectral_limits, svk_spectral_workspace_bytes, number unchanged; + svk_window_crops, svk_segment_affinity, svk_ahc, number unchanged; + svk_cohort_moments, svk_score_norm, svk_score_norm_pairs, number unchanged; + svk_calibration_stats, svk_calibration_apply, number unchanged; + svk_plda_scores, svk_plda_pair_scores, number unchanged; + svk_class_scatter, svk_embedding_project, number unchanged; + svk_cosine_topk, number unchanged; + svk_pair_scores, svk_roc_dcf, svk_decision_counts, number unchanged; + svk_c3d2_head; + the svk_delta_* entries, the *_multi first block and svk_embedding_pool, number unchanged)
+VERSION = 114                      # include/svk.h SVK_VERSION (0.1.12: + svk_rocch, svk_rocch_workspace_bytes, svk_rocch_level_counts_offset, svk_rocch_max_vertices, svk_pav_apply in include/svk_rocch.h, number unchanged; + svk_vad_adaptive in include/svk_vad.h, number unchanged; + svk_spectral_embed, svk_spectral_limits, svk_spectral_workspace_bytes, number unchanged; + svk_window_crops, svk_segment_affinity, svk_ahc, number unchanged; + svk_cohort_moments, svk_score_norm, svk_score_norm_pairs, number unchanged; + svk_calibration_stats, svk_calibration_apply, number unchanged; + svk_plda_scores, svk_plda_pair_scores, number unchanged; + svk_class_scatter, svk_embedding_project, number unchanged; + svk_cosine_topk, number unchanged; + svk_pair_scores, svk_roc_dcf, svk_decision_counts, number unchanged; + svk_c3d2_head; + the svk_delta_* entries, the *_multi first block and svk_embedding_pool, number unchanged)
 SVK_ERR_BAD_ARG, SVK_ERR_UNSUPPORTED, SVK_ERR_HIP, SVK_ERR_NO_DEVICE, SVK_ERR_OOM, SVK_ERR_RCCL = -1, -2, -3, -4, -5, -6
 OUT_MFE, OUT_LMFE, OUT_MFCC = 0, 1, 2
 PCM_I16, PCM_F32 = 0, 1
@@ -141,6 +141,17 @@ EXT_SIGNATURES = {
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# Entries of include/svk_rocch.h (the ROC convex hull and the PAV map): load() binds them after the other two tables;
+# tests/test_rocch_host.py checks this table against that header and the built library.
+ROCCH_SIGNATURES = {
+    "svk_rocch_workspace_bytes": (C.c_size_t, [_i64]),
+    "svk_rocch_level_counts_offset": (C.c_size_t, [_i64]),
+    "svk_rocch_max_vertices": (_i64, [_i64]),
+    "svk_rocch": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(C.c_double), _i32, _vp, C.c_size_t, _vp, _vp, _vp, _i64,
+                            C.POINTER(C.c_double)]),
+    "svk_pav_apply": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _vp]),
+}
+
 _lib = None
 
 
@@ -159,7 +170,7 @@ def load():
         except ImportError:
             pass
         lib = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+        for name, (restype, argtypes) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(ROCCH_SIGNATURES.items()):
             fn = getattr(lib, name)            # AttributeError if the .so is stale
             fn.restype = restype
             fn.argtypes = argtypes
@@ -181,14 +192,14 @@ def check(rc, ctx=None):
 
 def provenance():
     """What a measurement was made with: {"csrc_sha": sha256 over the kernel sources (csrc/*.hip, csrc/*.h, csrc/Makefile,
-    include/svk.h, include/svk_vad.h: file names + bytes, sorted), "libsvk_sha": sha256 of the built library}, 16 hex digits each.  Profiles
+    include/svk.h, include/svk_vad.h, include/svk_rocch.h: file names + bytes, sorted), "libsvk_sha": sha256 of the built library}, 16 hex digits each.  Profiles
     under profiles/ carry it (tools/summarize_prof.py) and bench.py marks a roofline row `stale` when the counters it uses
     were collected from other kernel sources than the ones it runs."""
     import hashlib
     here = os.path.dirname(os.path.abspath(__file__))
     csrc = os.path.join(here, "csrc")
     files = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h")) or f == "Makefile")
-    files += [os.path.join(os.path.dirname(here), "include", name) for name in ("svk.h", "svk_vad.h")]
+    files += [os.path.join(os.path.dirname(here), "include", name) for name in ("svk.h", "svk_vad.h", "svk_rocch.h")]
     h = hashlib.sha256()
     for path in files:
         h.update(os.path.basename(path).encode())

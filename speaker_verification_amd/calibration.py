@@ -209,3 +209,153 @@ class Calibration:
             objective = float(z["objective"])
             cal.objective_ = None if math.isnan(objective) else objective
         return cal
+
+
+# ---- the ROC convex hull: minCllr, ROCCH-EER, PAV --------------------------------------------------------------------------
+# How good a calibration COULD have been: minCllr is the Cllr of the best monotone map of the scores, which is PAV (isotonic
+# regression of the labels on the scores); cllr - min_cllr is the calibration loss.  PAV's bins are the edges of the upper
+# convex hull of the ROC and its posteriors their slopes; `Engine.rocch` (svk_rocch, include/svk_rocch.h has the definitions)
+# returns the hull's integer vertices from the device sort.  Everything below is host arithmetic on those K + 1 vertices.
+def hull_chain(points):
+    """Andrew's monotone chain over lexicographically sorted integer points (f, t), popping while cross >= 0: the indices of
+    the upper hull's vertices.  Python integers: exact."""
+    keep = []
+    for i, (f, t) in enumerate(points):
+        f, t = int(f), int(t)
+        while len(keep) >= 2:
+            (af, at), (bf, bt) = points[keep[-2]], points[keep[-1]]
+            af, at, bf, bt = int(af), int(at), int(bf), int(bt)
+            if (bf - af) * (t - at) - (bt - at) * (f - af) >= 0:
+                keep.pop()
+            else:
+                break
+        keep.append(i)
+    return keep
+
+
+def _vertex_list(vertices):
+    v = [(int(f), int(t)) for f, t in np.asarray(vertices).reshape(-1, 2)]
+    if len(v) < 2 or v[0] != (0, 0) or v[-1][0] < 1 or v[-1][1] < 1:
+        raise ValueError("hull vertices run from the origin to (N, P) with both classes present")
+    return v
+
+
+def min_cllr_of(vertices):
+    """minCllr in bits from the hull's vertices [K + 1, 2] (fps, tps): [(1/P) sum_k dt_k log1p(df_k P / (dt_k N)) + (1/N) sum_k
+    df_k log1p(dt_k N / (df_k P))] / (2 ln 2) over the edges, an edge with dt_k = 0 or df_k = 0 contributing 0.  The arguments
+    are quotients of Python integers (rounded once); every term is non-negative."""
+    v = _vertex_list(vertices)
+    n_non, n_tar = v[-1]
+    s_tar = s_non = 0.0
+    for (f0, t0), (f1, t1) in zip(v[:-1], v[1:]):
+        df, dt = f1 - f0, t1 - t0
+        if df and dt:
+            s_tar += dt * math.log1p((df * n_tar) / (dt * n_non))
+            s_non += df * math.log1p((dt * n_non) / (df * n_tar))
+    return (s_tar / n_tar + s_non / n_non) / (2.0 * LN2)
+
+
+def rocch_eer_of(vertices):
+    """The EER of the hull: `svk_roc_eer`'s rule on the vertices.  On the one edge with g_0 = 1 - f_0/N - t_0/P > 0 >= g_1,
+    x_0 + (x_1 - x_0) g_0 / (g_0 - g_1) -- formed as one quotient of Python integers, rounded once."""
+    v = _vertex_list(vertices)
+    n_non, n_tar = v[-1]
+    gap = lambda f, t: n_non * n_tar - f * n_tar - t * n_non            # noqa: E731  (g times N P)
+    for (f0, t0), (f1, t1) in zip(v[:-1], v[1:]):
+        g0, g1 = gap(f0, t0), gap(f1, t1)
+        if g0 > 0 >= g1:
+            return (f0 * (g0 - g1) + (f1 - f0) * g0) / (n_non * (g0 - g1))
+    raise ValueError("no edge of the hull crosses the diagonal")
+
+
+def min_cllr(scores, labels, engine=None):
+    """minCllr of a trial set in bits: one `Engine.rocch` call.  0 <= min_cllr <= 1; cllr - min_cllr is the calibration loss."""
+    from .engine import get_engine
+    return (engine or get_engine()).rocch(scores, labels)["min_cllr"]
+
+
+def rocch_eer(scores, labels, engine=None):
+    """The EER on the ROC convex hull (the one Bosaris-style recipes quote): one `Engine.rocch` call.  rocch_eer <= eer."""
+    from .engine import get_engine
+    return (engine or get_engine()).rocch(scores, labels)["rocch_eer"]
+
+
+def pav_table(vertices, vertex_scores, laplace=False):
+    """The PAV calibration of a trial set from its hull -> (edges float32 [B] descending, llr float32 [B]): bin k holds the
+    scores s >= edges[k] not taken by a bin above it, edges[k] being the lowest score of the bin, and maps them to
+    llr[k] = log(dt_k / df_k) - log(P / N) (+inf for df_k = 0, -inf for dt_k = 0).
+    laplace=True is Bosaris' rule: in descending score order a non-target and then a target are added above the best score and a
+    non-target and then a target below the worst.  The hull of that sequence is the hull of the four dummy points and the
+    shifted vertices (the hull of a union is the hull of the hulls), taken here exactly; only bins that hold a real trial are
+    kept, and all their LLRs are finite.  The prior log odds stay log(P / N) of the real trials."""
+    v = _vertex_list(vertices)
+    sc = np.asarray(vertex_scores, dtype=np.float32).reshape(-1)
+    if sc.size != len(v):
+        raise ValueError("one score per vertex")
+    n_non, n_tar = v[-1]
+    prior = math.log(n_tar) - math.log(n_non)
+    if laplace:
+        pts = [(0, 0), (1, 0), (1, 1)] + [(f + 1, t + 1) for f, t in v[1:]] + [(n_non + 2, n_tar + 1), (n_non + 2, n_tar + 2)]
+        low = [None, None, None] + [float(s) for s in sc[1:]] + [float(sc[-1]), float(sc[-1])]
+        real = lambda f, t: min(max(f - 1, 0), n_non) + min(max(t - 1, 0), n_tar)      # noqa: E731  (real trials at or above)
+        keep = hull_chain(pts)
+    else:
+        pts, low, real, keep = v, [float(s) for s in sc], (lambda f, t: f + t), list(range(len(v)))
+    edges, llr = [], []
+    for a, b in zip(keep[:-1], keep[1:]):
+        (f0, t0), (f1, t1) = pts[a], pts[b]
+        if real(f1, t1) - real(f0, t0) <= 0:
+            continue
+        df, dt = f1 - f0, t1 - t0
+        edges.append(low[b])
+        llr.append(math.inf if df == 0 else -math.inf if dt == 0 else math.log(dt) - math.log(df) - prior)
+    return np.asarray(edges, dtype=np.float32), np.asarray(llr, dtype=np.float32)
+
+
+class PavCalibration:
+    """Non-parametric calibration by PAV: the monotone step map of scores to LLRs that minimises Cllr on the trial list it is
+    fitted on (there, cllr of the mapped scores equals min_cllr).  `fit` on a development trial list, `apply` to any scores; a
+    fitted one can be passed wherever `calibration=` is taken.  Without laplace the best and worst bins of separable ends map
+    to +-inf, which the metrics refuse; laplace=True keeps every LLR finite."""
+
+    n_sys = 1
+
+    def __init__(self, laplace=False):
+        self.laplace = bool(laplace)
+        self.edges_ = self.llr_ = None
+
+    def _fitted(self):
+        if self.edges_ is None:
+            raise RuntimeError("the calibration is not fitted")
+
+    def fit(self, scores=None, labels=None, engine=None, hull=None):
+        """One `Engine.rocch` call, then the table on the host (`pav_table`).  hull: (vertices, vertex_scores) instead of
+        scores and labels, so that the table's logic needs no GPU.  Sets edges_ and llr_ (float32 [bins]); returns self."""
+        if hull is None:
+            from .engine import get_engine
+            res = (engine or get_engine()).rocch(scores, labels)
+            hull = (res["vertices"], res["vertex_scores"])
+        self.edges_, self.llr_ = pav_table(hull[0], hull[1], self.laplace)
+        return self
+
+    def apply(self, scores, engine=None, out=None):
+        """The mapped scores, float32 [n] on the device (`svk_pav_apply`); out may be the scores themselves."""
+        from .engine import get_engine
+        self._fitted()
+        return (engine or get_engine()).pav_apply(scores, self.edges_, self.llr_, out=out)
+
+    def save(self, path):
+        self._fitted()
+        with open(path, "wb") as fh:
+            np.savez(fh, edges=self.edges_, llr=self.llr_, laplace=np.array(self.laplace))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            cal = cls(laplace=bool(z["laplace"]))
+            edges = np.ascontiguousarray(z["edges"], dtype=np.float32).reshape(-1)
+            llr = np.ascontiguousarray(z["llr"], dtype=np.float32).reshape(-1)
+            if edges.size < 1 or edges.size != llr.size or np.isnan(edges).any() or (np.diff(edges) > 0).any():
+                raise ValueError("a PAV table holds at least one bin, one LLR per edge, the edges descending")
+            cal.edges_, cal.llr_ = edges, llr
+        return cal

@@ -25,10 +25,15 @@
 //   6. svk_roc_dcf only: dcf_part_kernel, one pass over the origin + the distinct-score points that leaves every workgroup's
 //      (cost, index) minimum per operating point in the workspace; roc_finish_kernel reduces them (no float64 atomics, no
 //      workgroup waits on another).  The first point among equal costs wins: the highest threshold.
+//   7. svk_rocch only (include/svk_rocch.h, kernels in rocch.h): behind roc_finish_kernel, the upper convex hull of the origin +
+//      the points, exact in int64: one hull per tile of 2 048 points (a monotone chain per thread, 8 merge levels in LDS), then
+//      ceil(log2(tiles)) levels that join adjacent hulls pairwise by their bridge; the vertices' scores come from the sorted keys.
+// svk_pav_apply (same header) maps scores through a step table by one binary search each.
 // svk_decision_counts is a pass of its own over UNSORTED scores: accepted targets / non-targets at up to 16 thresholds.
 // Bit-level equality of eer / auc with sklearn is not expected (float64 accumulation order), |d| ~ 1e-15;
 // the curve counts are exact.  Element indices are u32 (n < 2^32), every address is 64-bit.
 #include "svk_internal.h"
+#include "../../include/svk_rocch.h"
 
 namespace {
 
@@ -657,9 +662,13 @@ __global__ __launch_bounds__(RT) void top1_kernel(const float* __restrict__ s, i
   }
 }
 
+// ---- 7. svk_rocch only: the convex hull of the points; svk_pav_apply's kernel ------------------------------------------
+#include "rocch.h"
+
 // ---- host side ------------------------------------------------------------------------------------------------
 struct RocLayout {
   size_t keys[2], vals[2], pf, pt, counts, parts, hist, misc, total;
+  size_t hull[2], hcount, total_hull;   // svk_rocch only, behind `total`: what every other entry asks for is unchanged
 };
 
 // Workspace of one split of m pairs (splits run one after another through it).
@@ -682,6 +691,17 @@ RocLayout roc_layout(size_t m) {
   l.hist = o;   o += up(1026 * 4);
   l.misc = o;   o += 256;                       // [0..1] doubles eer, auc; then u32 totals at +64
   l.total = o;
+  // two hull buffers of one (f, t) pair per point (the origin + at most m distinct scores), each hull anchored at its first
+  // tile's offset; then every hull's vertex count, level after level: the tile pass's, then each merge level's (half as many
+  // each time, rounded up: below 2 tiles + 64 in all).  svk_rocch_level_counts_offset gives their offset (svk_rocch.h, Diagnostics).
+  const size_t tiles = (m + 1 + TILE - 1) / TILE;
+  for (int b = 0; b < 2; ++b) {
+    l.hull[b] = o;
+    o += up((m + 1) * 8);
+  }
+  l.hcount = o;
+  o += up((2 * tiles + 64) * 4);
+  l.total_hull = o;
   return l;
 }
 
@@ -698,6 +718,14 @@ struct DcfRequest {
   DcfOps ops;
   double fin[1 + 4 * DCF_MAX_OPS];
   float thr[DCF_MAX_OPS];
+};
+
+// What svk_rocch asks of a split beyond that: the hull of the origin + the points in the caller's planes, count = its vertices.
+struct HullRequest {
+  unsigned *vf, *vt;
+  float* vscore;
+  int64_t capacity;
+  unsigned count;
 };
 
 // span (a multiple of `unit`) and grid so that at most GMAX workgroups cover n elements
@@ -729,9 +757,11 @@ int span_pass(svk_ctx* ctx, const Op& op, unsigned* pa, unsigned* pb, unsigned* 
 // One split of m pairs.  strict (svk_roc_k): non-finite scores and a single class are errors found before the
 // sort, named by `split`.  cf / ct: the split's curve planes, or NULL.  h4 = {eer, auc, positives, points}: points =
 // distinct scores (curve == false) or the length of roc_curve's output (curve == true).  dcf: NULL, or the operating points
-// whose detection-cost minima this split's points are searched for; it also takes the EER point's score.
+// whose detection-cost minima this split's points are searched for; it also takes the EER point's score.  hull: NULL (nothing
+// more is launched), or the planes the hull of the points goes to; the workspace then holds l.total_hull bytes.
 int roc_split(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, size_t m, char* w, const RocLayout& l,
-              bool strict, int split, bool curve, unsigned* cf, unsigned* ct, double* h4, DcfRequest* dcf = nullptr) {
+              bool strict, int split, bool curve, unsigned* cf, unsigned* ct, double* h4, DcfRequest* dcf = nullptr,
+              HullRequest* hull = nullptr) {
   hipStream_t st = ctx->stream;
   unsigned* keys[2] = {reinterpret_cast<unsigned*>(w + l.keys[0]), reinterpret_cast<unsigned*>(w + l.keys[1])};
   uint8_t* vals[2] = {reinterpret_cast<uint8_t*>(w + l.vals[0]), reinterpret_cast<uint8_t*>(w + l.vals[1])};
@@ -811,6 +841,24 @@ int roc_split(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, size
   hipLaunchKernelGGL(roc_finish_kernel, dim3(1), dim3(RT), 0, st, area_parts, pgrid, totals + 4, pf, pt, src, n_op, pcost, pidx,
                      dgrid, out, fin, thr);
   SVK_LAUNCH_CHECK(ctx);
+  // the hull, behind the last reader of pf / pt: one hull per tile, then pairwise merges; the level count depends on M alone
+  const uint2* hfinal = nullptr;
+  if (hull) {
+    uint2* hb[2] = {reinterpret_cast<uint2*>(w + l.hull[0]), reinterpret_cast<uint2*>(w + l.hull[1])};
+    unsigned* hc = reinterpret_cast<unsigned*>(w + l.hcount);   // this level's counts; the next level's follow them
+    const size_t points = (size_t)M + 1;
+    unsigned hulls = (unsigned)((points + TILE - 1) / TILE);
+    hipLaunchKernelGGL(hull_tile_kernel, dim3(hulls), dim3(RT), 0, st, pf, pt, points, hb[0], hc);
+    SVK_LAUNCH_CHECK(ctx);
+    int at = 0;
+    for (size_t hspan = TILE; hulls > 1; hspan *= 2, hc += hulls, hulls = (hulls + 1) / 2, at ^= 1) {
+      hipLaunchKernelGGL(hull_merge_kernel, dim3((hulls + 1) / 2), dim3(RT), 0, st, hb[at], hc, hulls, hspan, hb[at ^ 1],
+                         hc + hulls);
+      SVK_LAUNCH_CHECK(ctx);
+    }
+    hfinal = hb[at];
+    SVK_HIP(ctx, hipMemcpyAsync(&hull->count, hc, 4, hipMemcpyDeviceToHost, st));
+  }
   unsigned C = M;
   if (curve) {
     const CurveOp cop{pf, pt, M, cf, ct};
@@ -829,6 +877,14 @@ int roc_split(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, size
   SVK_HIP(ctx, hipStreamSynchronize(st));
   h4[2] = (double)P;
   h4[3] = curve ? (double)C + 1.0 : (double)M;
+  if (hull) {
+    if ((int64_t)hull->count > hull->capacity)
+      return svk_fail(ctx, SVK_ERR_BAD_ARG, "bad argument: capacity %lld is below the hull's %u vertices", (long long)hull->capacity,
+                      hull->count);
+    hipLaunchKernelGGL(hull_emit_kernel, dim3((hull->count + RT - 1) / RT), dim3(RT), 0, st, hfinal, hull->count, src, hull->vf,
+                       hull->vt, hull->vscore);
+    SVK_LAUNCH_CHECK(ctx);
+  }
   return SVK_OK;
 }
 
@@ -899,8 +955,13 @@ int svk_top1(svk_ctx* ctx, const float* d_scores, int64_t n_rows, int32_t n_cols
 
 size_t svk_roc_dcf_workspace_bytes(int64_t n) { return n >= 2 ? roc_layout((size_t)n).total : 0; }
 
-int svk_roc_dcf(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, int64_t n, const double* h_ops, int32_t n_op,
-                void* d_workspace, size_t workspace_bytes, double* h_out) {
+}  // extern "C"
+
+namespace {
+
+// svk_roc_dcf, and svk_rocch with a hull request: the same checks in the same words, the same launches in front of the hull's
+int roc_dcf_entry(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, int64_t n, const double* h_ops, int32_t n_op,
+                  void* d_workspace, size_t workspace_bytes, double* h_out, HullRequest* hull) {
   if (!ctx || !h_out) return SVK_ERR_BAD_ARG;
   SVK_REQUIRE(ctx, n >= 2, "need at least two (label, score) pairs");
   SVK_REQUIRE(ctx, n < ((int64_t)1 << 32), "at most 2^32 - 1 pairs");
@@ -918,10 +979,16 @@ int svk_roc_dcf(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, in
     req.ops.b[o] = c_fa * (1.0 - p);
   }
   const RocLayout l = roc_layout((size_t)n);
-  SVK_REQUIRE(ctx, workspace_bytes >= l.total, "workspace smaller than svk_roc_dcf_workspace_bytes(n)");
+  if (hull) {
+    SVK_REQUIRE(ctx, hull->vf && hull->vt && hull->vscore, "NULL buffer");
+    SVK_REQUIRE(ctx, hull->capacity >= 1, "capacity < 1");
+    SVK_REQUIRE(ctx, workspace_bytes >= l.total_hull, "workspace smaller than svk_rocch_workspace_bytes(n)");
+  } else {
+    SVK_REQUIRE(ctx, workspace_bytes >= l.total, "workspace smaller than svk_roc_dcf_workspace_bytes(n)");
+  }
   double h4[4];
   if (int rc = roc_split(ctx, d_scores, d_labels, (size_t)n, reinterpret_cast<char*>(d_workspace), l, true, 0, false, nullptr,
-                         nullptr, h4, &req))
+                         nullptr, h4, &req, hull))
     return rc;
   const double P = h4[2], N = (double)n - P;
   for (int i = 0; i < 4; ++i) h_out[i] = h4[i];
@@ -934,6 +1001,60 @@ int svk_roc_dcf(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, in
     r[2] = 1.0 - f[3] / P;
     r[3] = f[2] / N;
   }
+  if (hull) h_out[5 + 4 * n_op] = (double)hull->count;
+  return SVK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int svk_roc_dcf(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, int64_t n, const double* h_ops, int32_t n_op,
+                void* d_workspace, size_t workspace_bytes, double* h_out) {
+  return roc_dcf_entry(ctx, d_scores, d_labels, n, h_ops, n_op, d_workspace, workspace_bytes, h_out, nullptr);
+}
+
+size_t svk_rocch_workspace_bytes(int64_t n) { return n >= 2 ? roc_layout((size_t)n).total_hull : 0; }
+
+size_t svk_rocch_level_counts_offset(int64_t n) { return n >= 2 ? roc_layout((size_t)n).hcount : 0; }
+
+int64_t svk_rocch_max_vertices(int64_t n) {
+  if (n < 1) return 0;
+  // S = the smallest integer with S (S + 1) (S + 2) / 3 >= m (include/svk_rocch.h).  m = n, held to the 2^32 - 1 trials svk_rocch
+  // takes (a larger n gets that bound's S: the K <= n term no longer binds there): S <= 2 345 and every product is below 2^34
+  const int64_t m = std::min<int64_t>(n, ((int64_t)1 << 32) - 1);
+  int64_t s = 1;
+  while (s * (s + 1) * (s + 2) / 3 < m) ++s;
+  return std::min(s * (s + 3) / 2, n) + 1;
+}
+
+int svk_rocch(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, int64_t n, const double* h_ops, int32_t n_op,
+              void* d_workspace, size_t workspace_bytes, uint32_t* d_vf, uint32_t* d_vt, float* d_vscore, int64_t capacity,
+              double* h_out) {
+  HullRequest hull{d_vf, d_vt, d_vscore, capacity, 0};
+  return roc_dcf_entry(ctx, d_scores, d_labels, n, h_ops, n_op, d_workspace, workspace_bytes, h_out, &hull);
+}
+
+int svk_pav_apply(svk_ctx* ctx, const float* d_scores, int64_t n, const float* d_edges, const float* d_llr, int32_t n_bins,
+                  float* d_out) {
+  if (!ctx) return SVK_ERR_BAD_ARG;
+  SVK_REQUIRE(ctx, n >= 0, "negative size");
+  SVK_REQUIRE(ctx, n_bins >= 1, "n_bins < 1");
+  SVK_REQUIRE(ctx, d_edges && d_llr, "NULL table");
+  if (n == 0) return SVK_OK;
+  SVK_REQUIRE(ctx, d_scores && d_out, "NULL buffer");
+  const uintptr_t ps = reinterpret_cast<uintptr_t>(d_scores), po = reinterpret_cast<uintptr_t>(d_out);
+  SVK_REQUIRE(ctx, ((ps | po | reinterpret_cast<uintptr_t>(d_edges) | reinterpret_cast<uintptr_t>(d_llr)) & 3) == 0,
+              "scores, table and output must be 4-byte aligned");
+  const bool vec = (ps & 15) == (po & 15);
+  const size_t head = vec ? std::min<size_t>((size_t)n, ((16 - (ps & 15)) & 15) / 4) : 0;
+  const size_t quads = ((size_t)n - head + 3) / 4;
+  const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((quads + RT - 1) / RT, (size_t)ctx->num_cu * 8));
+  const bool lds = n_bins <= PAV_LDS_BINS;
+  auto kern = lds ? (vec ? pav_apply_kernel<true, true> : pav_apply_kernel<true, false>)
+                  : (vec ? pav_apply_kernel<false, true> : pav_apply_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(RT), 0, ctx->stream, d_scores, (size_t)n, head, d_edges, d_llr, (int)n_bins, d_out);
+  SVK_LAUNCH_CHECK(ctx);
   return SVK_OK;
 }
 

@@ -802,20 +802,71 @@ class Engine:
         entry per operating point in the lists min_dcf, threshold, p_miss, p_fa (accept when score >= threshold; the origin of
         the ROC, "reject everything", has threshold +inf).  eer and auc are roc_eer's values, bit for bit.  Raises for a
         non-finite score or a single class."""
+        return self._roc_dcf_call(scores, labels, operating_points, None)[0]
+
+    def _roc_dcf_call(self, scores, labels, operating_points, planes):
+        """svk_roc_dcf (planes None) or svk_rocch (planes: int32 [3, capacity] on the device) -> (roc_dcf's dict, the vertex
+        count or None): the two entries' shared arguments and the shared head of h_out, stated once."""
         sc, lb = self._scores_labels(scores, labels)
         n = sc.numel()
         ops = np.ascontiguousarray(np.asarray(operating_points, dtype=np.float64).reshape(-1, 3))
         n_op = int(ops.shape[0])
-        work = self._workspace(self.lib.svk_roc_dcf_workspace_bytes(n))
-        out = (C.c_double * (5 + 4 * max(n_op, 0)))()
+        h_ops = ops.ctypes.data_as(C.POINTER(C.c_double))
+        out = (C.c_double * (6 + 4 * n_op))()
         self._stream()
-        check(self.lib.svk_roc_dcf(self.ctx, self._ptr(sc), self._ptr(lb), n, ops.ctypes.data_as(C.POINTER(C.c_double)), n_op,
-                                   self._ptr(work), work.numel(), out), self.ctx)
+        if planes is None:
+            work = self._workspace(self.lib.svk_roc_dcf_workspace_bytes(n))
+            check(self.lib.svk_roc_dcf(self.ctx, self._ptr(sc), self._ptr(lb), n, h_ops, n_op, self._ptr(work), work.numel(), out),
+                  self.ctx)
+        else:
+            work = self._workspace(self.lib.svk_rocch_workspace_bytes(n))
+            check(self.lib.svk_rocch(self.ctx, self._ptr(sc), self._ptr(lb), n, h_ops, n_op, self._ptr(work), work.numel(),
+                                     self._ptr(planes[0]), self._ptr(planes[1]), self._ptr(planes[2]), int(planes.shape[1]), out),
+                  self.ctx)
         res = {"eer": float(out[0]), "auc": float(out[1]), "positives": int(out[2]), "points": int(out[3]),
                "eer_threshold": float(out[4])}
         for j, name in enumerate(("min_dcf", "threshold", "p_miss", "p_fa")):
             res[name] = [float(out[5 + 4 * o + j]) for o in range(n_op)]
+        return res, (None if planes is None else int(out[5 + 4 * n_op]))
+
+    def rocch(self, scores, labels, operating_points=()):
+        """svk_rocch (include/svk_rocch.h): roc_dcf's dict -- the same values, bit for bit -- plus the ROC convex hull from
+        the same sort: vertices (int64 [K + 1, 2] on the host: fps, tps, the origin first, (N, P) last), vertex_scores (float32
+        [K + 1]: the score at each vertex, +inf at the origin), and min_cllr and rocch_eer, computed from the integer vertices
+        in float64 on the host (`calibration.min_cllr_of`, `calibration.rocch_eer_of`).  ONE library call, the planes sized by
+        svk_rocch_max_vertices.  Raises as roc_dcf does."""
+        from . import calibration as cal
+        torch = _torch()
+        sc, lb = self._scores_labels(scores, labels)
+        cap = max(1, int(self.lib.svk_rocch_max_vertices(sc.numel())))
+        planes = torch.empty((3, cap), dtype=torch.int32, device=self.device)
+        res, count = self._roc_dcf_call(sc, lb, operating_points, planes)
+        host = planes[:, :count].cpu().numpy()
+        res["vertices"] = np.ascontiguousarray(host[:2].view(np.uint32).T.astype(np.int64))
+        res["vertex_scores"] = host[2].view(np.float32).copy()
+        res["min_cllr"] = cal.min_cllr_of(res["vertices"])
+        res["rocch_eer"] = cal.rocch_eer_of(res["vertices"])
         return res
+
+    def pav_apply(self, scores, edges, llr, out=None):
+        """svk_pav_apply: float32 [n] on the device, out[p] = llr[k] for the smallest k with scores[p] >= edges[k] (edges
+        descending; the last bin below every edge; a NaN stays NaN).  out: the tensor to write; it may be the scores
+        themselves (in place)."""
+        torch = _torch()
+        sc = self.to_device(scores, torch.float32).reshape(-1)
+        ed = self.to_device(edges, torch.float32).reshape(-1)
+        ll = self.to_device(llr, torch.float32).reshape(-1)
+        n = sc.numel()
+        if ed.numel() < 1 or ed.numel() != ll.numel():
+            raise ValueError("pav_apply wants one LLR per edge and at least one bin")
+        if out is None:
+            out = torch.empty((n,), dtype=torch.float32, device=self.device)
+        else:
+            self._given_out(out, n, torch.float32, "out wants a contiguous float32 device tensor of %d elements" % n)
+        self._stream()
+        check(self.lib.svk_pav_apply(self.ctx, self._ptr(sc), n, self._ptr(ed), self._ptr(ll), ed.numel(), self._ptr(out)),
+              self.ctx)
+        return out.reshape(-1)
 
     def decision_counts(self, scores, labels, thresholds):
         """svk_decision_counts: one pass over unsorted scores / 0-1 labels.  thresholds: 1 to 16 floats (+-inf allowed).  Returns

@@ -157,7 +157,7 @@ def make_trials(speaker_ids, n_target, n_nontarget, seed):
 
 
 def evaluate_trials(embeddings, labels, idx_a, idx_b, metric="cosine", operating_points=DEFAULT_OPERATING_POINTS, device=True,
-                    backend=None, plda=None, calibration=None, score_norm=None):
+                    backend=None, plda=None, calibration=None, score_norm=None, rocch=False):
     """Verification over a trial list: trial p compares embeddings[idx_a[p]] with embeddings[idx_b[p]] (`svk_pair_scores`,
     metric "cosine" or "l2"), labels[p] = 1 for the same speaker.  Returns a dict: eer, auc, eer_threshold, and per operating
     point (p_target, c_miss, c_fa) the lists min_dcf, threshold, p_miss, p_fa; scores = the float32 trial scores on the device.
@@ -171,8 +171,13 @@ def evaluate_trials(embeddings, labels, idx_a, idx_b, metric="cosine", operating
     threshold (`svk_decision_counts`; min_dcf <= act_dcf, the gap is the calibration loss).  None (the default) changes nothing.
     score_norm: a `score_norm.ScoreNorm` fitted on a cohort for the same back end and PLDA: the trial scores are normalised
     (between the raw score and the calibration) before the metrics, and scores = the normalised scores.  None (the default)
-    changes nothing."""
+    changes nothing.
+    rocch=True (with device=True): the metrics come from ONE `svk_rocch` call instead of `svk_roc_dcf` -- the same values, bit
+    for bit -- and the dict gains min_cllr and rocch_eer (the ROC convex hull, `calibration.min_cllr_of`); with a calibration
+    also calibration_loss = cllr - min_cllr.  False (the default) changes nothing."""
     from .pipeline import trial_scores
+    if rocch and not device:
+        raise ValueError("evaluate_trials: rocch=True takes the hull from the device ROC (device=True)")
     eng = get_engine()
     if calibration is not None and calibration.n_sys != 1:
         raise ValueError("evaluate_trials scores one system: the calibration must be fitted on one, not %r" % (calibration.n_sys,))
@@ -186,8 +191,10 @@ def evaluate_trials(embeddings, labels, idx_a, idx_b, metric="cosine", operating
         raise ValueError("one label per trial")
     ops = [tuple(float(v) for v in op) for op in operating_points]
     if device:
-        res = eng.roc_dcf(scores, labels, ops)
+        res = eng.rocch(scores, labels, ops) if rocch else eng.roc_dcf(scores, labels, ops)
         out = {k: res[k] for k in ("eer", "auc", "eer_threshold", "min_dcf", "threshold", "p_miss", "p_fa")}
+        if rocch:
+            out["min_cllr"], out["rocch_eer"] = res["min_cllr"], res["rocch_eer"]
     else:
         from sklearn.metrics import roc_curve
         sc = scores.cpu().numpy()
@@ -202,6 +209,8 @@ def evaluate_trials(embeddings, labels, idx_a, idx_b, metric="cosine", operating
         from . import calibration as cal
         out["cllr"] = cal.cllr(scores, labels, engine=eng)
         out["act_dcf"] = cal.act_dcf(scores, labels, ops, engine=eng)[0]
+        if rocch:
+            out["calibration_loss"] = out["cllr"] - out["min_cllr"]
     out["scores"] = scores
     return out
 

@@ -46,6 +46,7 @@ def load_lib():
         _lib.VERSION = lib.svk_version()
         _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(lib, k)}
         _lib.EXT_SIGNATURES = {k: v for k, v in _lib.EXT_SIGNATURES.items() if hasattr(lib, k)}
+        _lib.ROCCH_SIGNATURES = {k: v for k, v in _lib.ROCCH_SIGNATURES.items() if hasattr(lib, k)}
     return _lib, _lib.load()
 
 
