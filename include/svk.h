@@ -839,7 +839,8 @@ int svk_score_norm_pairs(svk_ctx* ctx, const float* d_scores, int64_t n, const d
                          float* d_out, int32_t* d_bad_count);
 
 /* ---- the embedding network --------------------------------------------------------------------------
- * Every entry of this section (svk_c3d2_stage1 .. svk_c3d2_fc5) writes its whole d_out and, beside it, only its workspace where
+ * Every entry of this section (svk_c3d2_stage1 .. svk_c3d2_fc5) writes its whole d_out (the first-block entries under flags bit
+ * 5: all of it but pooled column 17, see there) and, beside it, only its workspace where
  * it has one: svk_c3d2_fc5's d_work, and svk_c3d2_stage2's d_act2 under SVK_C3D2_STAGE2_TWO_KERNELS.  The work-item counters
  * the persistent kernels draw tickets from live in the handle and are zeroed by every call: a result does not depend on what
  * ran on the handle before.
@@ -871,7 +872,13 @@ int svk_score_norm_pairs(svk_ctx* ctx, const float* d_scores, int64_t n, const d
  * crop that runs off the clip -> zero rows from max_frames on; feature rows that no crop names are not read).
  * d_out: the activation after the pool, float32, channels last: [n_utt][16 d][36 h][18 w][16 c]
  * flags bit 1 (value 2) = the caller asserts every PReLU slope lies in [0, 1] (then prelu(v) = max(v, slope v): two
- * instructions per value instead of four); every other bit must be 0.
+ * instructions per value instead of four).
+ * flags bit 5 (value 32) = the 17-column form, on all four first-block entries (this one, svk_c3d2_stage1_c3 and the two *_multi):
+ * The caller consumes the output through svk_c3d2_stage2 only.  Pooled column 17 (d_out[u][d][h][17][0..15]) is neither computed
+ * nor written.  It keeps what it held on entry.  Columns 0 ... 16 are bit-identical to a call without the flag.  (Why column 17 is
+ * dead: conv2_1 is 4 columns wide, so it has 15 output columns; conv2_2 is 1 wide and pool2 drops its 15th, so conv2_1's last
+ * live column is 13, which reads pooled columns 13 ... 16.)  The launch then has 34 work items per cube instead of 36.
+ * Every other bit must be 0: 1, 4, 8 and 16 are undefined and SVK_ERR_BAD_ARG, as is any bit above 5.
  * Geometry other than the 20 x 80 x 40 cube -> SVK_ERR_UNSUPPORTED (the torch module is the path for other models). */
 size_t svk_c3d2_stage1_lds_bytes(void);
 int svk_c3d2_stage1(svk_ctx* ctx, const float* d_feat, int32_t n_utt, int32_t max_frames, int32_t n_cols,
@@ -924,7 +931,8 @@ int svk_c3d2_stage1_c3_multi(svk_ctx* ctx, const float* d_feat, int32_t n_clips,
  * through two-piece products like svk_c3d2_stage1 (direct form; the weights of all taps sit in registers): conv2_1 is handed
  * to conv2_2 depth pair by depth pair through LDS, already split into (h, l) halves, so its activation never reaches memory;
  * epilogues carry bias, PReLU and the pool.
- *   d_in     [n_utt][16][36][18][16]  = svk_c3d2_stage1's output
+ *   d_in     [n_utt][16][36][18][16]  = svk_c3d2_stage1's output; pooled column 17 (d_in[u][d][h][17][.]) enters no product and
+ *            may hold anything, NaNs included (svk_c3d2_stage1's flags bit 5 leaves it unwritten)
  *   d_w21blk [2 nt][6 pairs][2][64][8 halves]: conv2_1, lane l = (co = 16 nt + (l & 15), kk = l >> 4), element e =
  *            W[co][ci = 8 (kk & 1) + e][kd][kw + (kk >= 2)] of the tap pair 2 kd + kw / 2 (kw = 0, 2); block 0 = H, 1 = L
  *   d_w22blk [2 nt][24 taps][2][64][8 halves]: conv2_2, element e = W[co][ci = 8 kk + e][kd][kh], tap = 8 kd + kh; H | L
@@ -935,7 +943,7 @@ int svk_c3d2_stage1_c3_multi(svk_ctx* ctx, const float* d_feat, int32_t n_clips,
  *            15 columns -- conv2_2 is one column wide and pool2 drops its 15th, so conv2_1's 15th is never computed), and NULL
  *            is SVK_ERR_BAD_ARG;
  *   d_out    [n_utt][12][15][7][32] (channels last)
- * flags as for svk_c3d2_stage1. */
+ * flags bit 1 as for svk_c3d2_stage1; every other bit must be 0 (bit 5 belongs to the first-block entries alone). */
 int svk_c3d2_stage2(svk_ctx* ctx, const float* d_in, int32_t n_utt, const void* d_w21blk, const float* d_bias21,
                     const float* d_slope21, const void* d_w22blk, const float* d_bias22, const float* d_slope22,
                     int32_t flags, float* d_act2, float* d_out);

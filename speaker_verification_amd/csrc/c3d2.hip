@@ -54,13 +54,20 @@ constexpr int S_W = 16, S_PAR = OWP * 16, S_D = OH * OWP * 16, S_N = OD * OH * O
 // A work item (cube u, rem = 18 q + j: half q of the output depths, pooled column j), decoded ONCE when its index is known (two
 // items ahead) and handed down: item / 36, % 36, / 18 for the item, the next one (patch fetch) and the one after (crop starts)
 // were three division chains of scalar instructions per item, in front of the barrier where nothing hides them.
+// NJ = the LIVE pooled columns of the launch, a cube's items being 2 NJ: 18, or 17 where the caller hands the output to the second
+// block only (flags bit 5; see stage1 below).  The 17-column form numbers a cube's items 17 q + j and decodes them to the SAME
+// rem = 18 q + j, j <= 16, so everything behind the decode -- patch, tiles, output strides -- is the 18-column kernel's; NJ is
+// compile-time for the reason S_W is (the divisor).
 struct ItemPos {
   int u, rem;
   __device__ __forceinline__ int q() const { return rem >= 18 ? 1 : 0; }
   __device__ __forceinline__ int j() const { return rem >= 18 ? rem - 18 : rem; }
+  template <int NJ>
   __device__ static __forceinline__ ItemPos of(int item) {
-    const int u = item / 36;
-    return ItemPos{u, item - 36 * u};
+    static_assert(NJ == OWP || NJ == OWP - 1, "18 live columns, or 17");
+    const int u = item / (2 * NJ), r = item - 2 * NJ * u;
+    if constexpr (NJ == OWP) return ItemPos{u, r};
+    else return ItemPos{u, r >= NJ ? r + (OWP - NJ) : r};
   }
 };
 
@@ -476,7 +483,8 @@ __device__ __forceinline__ void conv12_chain(const unsigned* act, const u32x4 (&
 // patch is fetched (crop starts: `starts`), item2's crop starts are fetched, item3 is drawn from the device-wide counter.
 // (NCH = 3 keeps conv1_2's tile loop: with 13 conv1_1 accumulators behind it the chain takes its spill from 6 to 16 VGPRs)
 // MULTI: p.n_utt counts CUBES, K = p.cubes_per_clip of them per clip's feature rows (feat_pos); nothing else differs.
-template <bool SLOPE01, int NCH = 1, bool MULTI = false>
+// NJ: the live pooled columns (ItemPos): 2 NJ items per cube; with NJ = 17 nothing computes or writes column 17.
+template <bool SLOPE01, int NCH = 1, bool MULTI = false, int NJ = OWP>
 __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p) {
   constexpr bool CONV12_CHAINS = NCH == 1;
   extern __shared__ __attribute__((aligned(16))) float smem_c3d2[];
@@ -484,7 +492,7 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
   float* const patch = smem_c3d2 + HACT_WORDS;                    // [WP_FLOATS]: [12 dd][80 h][8], f32 from the DMA, then (l << 16 | h) words
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const Lane1 L{lane, wave, lane & 15, lane >> 4, wave & 3, wave >> 2};
-  const int n_items = p.n_utt * 36;
+  const int n_items = p.n_utt * (2 * NJ);
 
   u32x4 W2[HPAIRS][2];
   load_wblk(p.w2blk, 0, lane, W2);
@@ -499,7 +507,7 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
   int starts_cur = 0;   // NCH = 3: the current item's crop starts (`starts` is already the next item's by the top of the loop)
   __shared__ int q_item3;
   int item = blockIdx.x, item1 = item + (int)gridDim.x, item2 = item1 + (int)gridDim.x;
-  ItemPos cur = ItemPos::of(item), nx = ItemPos::of(item1), nx2 = ItemPos::of(item2);
+  ItemPos cur = ItemPos::of<NJ>(item), nx = ItemPos::of<NJ>(item1), nx2 = ItemPos::of<NJ>(item2);
   if (item < n_items) {
     starts = fetch_starts(p, cur, lane);
     if (L.part == 0) dma_patch_ch0<NCH, MULTI>(p, cur, starts, L, patch);
@@ -554,20 +562,25 @@ __global__ __launch_bounds__(512) void c3d2_stage1h_kernel(const Stage1Params p)
     item2 = item3;
     cur = nx;
     nx = nx2;
-    nx2 = ItemPos::of(item3);
+    nx2 = ItemPos::of<NJ>(item3);
   }
 }
 
 // svk_c3d2_stage1 (NCH = 1) and svk_c3d2_stage1_c3 (NCH = 3): the same arguments, checks and launch.  Their *_multi forms
 // (MULTI) take `n_clips` feature matrices and K = cubes_per_clip cubes of each: every check below then applies to the cube count
 // n_clips K, which is what the kernel calls n_utt.
+// flags: bit 1 (value 2) = every slope in [0, 1]; bit 5 (value 32) = the 17-column form: the caller hands d_out to svk_c3d2_stage2
+// only, which reads pooled columns 0 .. 16 (conv2_1 is 4 wide and pool2 drops its 15th column), so column 17 is neither computed nor
+// written.  The bits between them stay UNDEFINED, like 1: the tests pin 1, 4, 8 and 16 as SVK_ERR_BAD_ARG on these entries.
+constexpr int32_t STAGE1_SLOPE01 = 2, STAGE1_LIVE17 = 32;
 template <int NCH, bool MULTI = false>
 int stage1(svk_ctx* ctx, const char* name, const float* d_feat, int32_t n_clips, int32_t max_frames, int32_t n_cols,
            const int32_t* d_crop_idx, int32_t n_crops, int32_t crop_frames, const void* d_w1blk, const float* d_bias1,
            const float* d_slope1, const void* d_w2blk, const float* d_bias2, const float* d_slope2, int32_t flags, float* d_out,
            int32_t cubes_per_clip = 1) {
   if (!ctx) return SVK_ERR_BAD_ARG;
-  SVK_REQUIRE(ctx, (flags & ~2) == 0, "flags: only bit 1 (slopes in [0, 1]) is defined");
+  SVK_REQUIRE(ctx, (flags & ~(STAGE1_SLOPE01 | STAGE1_LIVE17)) == 0,
+              "flags: only bit 1 (slopes in [0, 1]) and bit 5 (pooled column 17 left unwritten) are defined");
   SVK_REQUIRE(ctx, cubes_per_clip >= 1, "cubes_per_clip must be at least 1");
   SVK_REQUIRE(ctx, n_clips >= 0 && max_frames >= 1, "shape");
   SVK_REQUIRE(ctx, (int64_t)n_clips * cubes_per_clip <= INT32_MAX, "too many cubes for one launch");   // (the item count: below)
@@ -581,6 +594,7 @@ int stage1(svk_ctx* ctx, const char* name, const float* d_feat, int32_t n_clips,
   SVK_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(d_feat) & 7) == 0 && ((reinterpret_cast<uintptr_t>(d_w1blk) | reinterpret_cast<uintptr_t>(d_w2blk) |
                                                                     reinterpret_cast<uintptr_t>(d_out)) & 15) == 0,
               "d_feat must be 8-byte, the weight blocks and d_out 16-byte aligned");
+  // (36 items per cube: the 18-column count, the stricter bound for either form)
   SVK_REQUIRE(ctx, (int64_t)n_utt * 36 + 4 * (int64_t)ctx->num_cu < ((int64_t)1 << 31), "too many cubes for one launch");
   Stage1Params p;
   p.feat = d_feat;
@@ -595,9 +609,13 @@ int stage1(svk_ctx* ctx, const char* name, const float* d_feat, int32_t n_clips,
   p.slope2 = d_slope2;
   p.out = d_out;
   p.cubes_per_clip = cubes_per_clip;
-  void (*kern)(const Stage1Params) = (flags & 2) ? c3d2_stage1h_kernel<true, NCH, MULTI> : c3d2_stage1h_kernel<false, NCH, MULTI>;
+  const bool slope01 = flags & STAGE1_SLOPE01;
+  const int live = (flags & STAGE1_LIVE17) ? OWP - 1 : OWP;
+  void (*kern)(const Stage1Params) =
+      live == OWP ? (slope01 ? c3d2_stage1h_kernel<true, NCH, MULTI, OWP> : c3d2_stage1h_kernel<false, NCH, MULTI, OWP>)
+                  : (slope01 ? c3d2_stage1h_kernel<true, NCH, MULTI, OWP - 1> : c3d2_stage1h_kernel<false, NCH, MULTI, OWP - 1>);
   unsigned grid;
-  if (int rc = svk_persistent_grid(ctx, name, kern, svk_c3d2_stage1_lds_bytes(), 512, 1, (int64_t)n_utt * 36, &grid)) return rc;
+  if (int rc = svk_persistent_grid(ctx, name, kern, svk_c3d2_stage1_lds_bytes(), 512, 1, (int64_t)n_utt * 2 * live, &grid)) return rc;
   if (int rc = svk_work_queue(ctx, SVK_SLOT_STAGE1, 1, &p.queue)) return rc;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), svk_c3d2_stage1_lds_bytes(), ctx->stream, p);
   SVK_LAUNCH_CHECK(ctx);

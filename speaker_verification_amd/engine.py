@@ -627,15 +627,20 @@ class Engine:
                                              int(delta), self._ptr(stats), self._ptr(out)), self.ctx)
         return out
 
-    def c3d2_stage1(self, feat, crop_idx, tables, crop_frames=80, cubes_per_clip=1):
+    def c3d2_stage1(self, feat, crop_idx, tables, crop_frames=80, cubes_per_clip=1, live_cols=18):
         """svk_c3d2_stage1: feature rows [n, T, 40] + crop starts [n, 20] -> the activation after C3D2's first block (conv1_1,
         conv1_2, pool1 with their BN + PReLU): [n, 16, 36, 18, 16] f32, channels last.  Two-piece f16 products on
         v_mfma_f32_16x16x32_f16 (x = h + l, three piece products per f32 product, f32 accumulation: ~1e-6 of the scale from the
         f32 form); tables: `FusedEmbedder.stage1_tables()`.  The tables of a three-channel model (conv1_1 block [3, 2, 64, 8])
         run svk_c3d2_stage1_c3 on feature rows [n, 3, T, 40] (static, delta, delta-delta) instead: the same output layout.
         cubes_per_clip = K > 1 (or crop starts [n, K, 20]): K cubes of every clip's rows through svk_c3d2_stage1_multi /
-        svk_c3d2_stage1_c3_multi -> [n K, 16, 36, 18, 16], cube-major; K = 1 with [n, 20] starts runs the entries above."""
+        svk_c3d2_stage1_c3_multi -> [n K, 16, 36, 18, 16], cube-major; K = 1 with [n, 20] starts runs the entries above.
+        live_cols = 17 (flags bit 5) is for an output that goes to `c3d2_stage2` and nowhere else: pooled column 17, which the
+        second block never reads, is neither computed nor written -- out[:, :, :, 17] is whatever the allocator handed over --
+        and columns 0 .. 16 are the bits of the default call."""
         torch = _torch()
+        if live_cols not in (17, 18):
+            raise ValueError("live_cols must be 18 (the whole output) or 17 (column 17 left unwritten), got %r" % (live_cols,))
         feat = self.to_device(feat, torch.float32)
         idx = self.to_device(crop_idx, torch.int32)
         three = tuple(tables[0].shape) == (3, 2, 64, 8)
@@ -654,6 +659,8 @@ class Engine:
         elif not multi and (idx.dim() != 2 or idx.shape[0] != n):
             raise ValueError("crop_idx must be [n, n_crops] for the n = %d cubes, got %s" % (n, tuple(idx.shape)))
         layers = self._c3d2_layers(tables, ((3, 2, 64, 8) if three else (2, 64, 8), (14, 2, 64, 8)), torch.float16, 16)
+        if live_cols == 17:
+            layers[-1] |= 32
         out = torch.empty((n * max(K, 0), 16, 36, 18, 16), dtype=torch.float32, device=self.device)
         self._stream()
         if multi:
@@ -697,7 +704,9 @@ class Engine:
 
     def c3d2_stage2(self, act1, tables):
         """svk_c3d2_stage2: [n, 16, 36, 18, 16] (svk_c3d2_stage1's output) -> conv2_1 -> conv2_2 -> pool2 with their
-        BN + PReLU -> [n, 12, 15, 7, 32] f32 (channels last), both convolutions through two-piece f16 products."""
+        BN + PReLU -> [n, 12, 15, 7, 32] f32 (channels last), both convolutions through two-piece f16 products.  Pooled column
+        17 of act1 is not read by any product (conv2_1's last live column, 13, ends at column 16): `c3d2_stage1(live_cols=17)`
+        may leave it unwritten."""
         if tuple(act1.shape[1:]) != (16, 36, 18, 16) or not act1.is_contiguous():
             raise ValueError("c3d2_stage2 wants the activation [n, 16, 36, 18, 16]")
         # conv2_1's activation stays in LDS; only the two-kernel reference path (SVK_C3D2_STAGE2_TWO_KERNELS, read by the library at

@@ -302,7 +302,7 @@ class FusedEmbedder:
                 return emb.view(-1, K, EMBED_DIM)
             return run("pool", lambda: eng.embedding_pool(emb, rows_per_seg=K, l2_rows=pool == "mean_l2"))
         self._check_rows(feat)
-        return self._network(run, lambda: eng.c3d2_stage1(feat, crop_idx, self.stage1_tables()))
+        return self._network(run, lambda: eng.c3d2_stage1(feat, crop_idx, self.stage1_tables(), live_cols=17))
 
     def _check_rows(self, feat):
         want = 3 if self.num_channels == 1 else 4
@@ -314,10 +314,12 @@ class FusedEmbedder:
         """[n, K, 20] crop starts -> [n K, 128], cube-major: the first block reads clip u / K for cube u, the other six kernels
         see n K independent cubes."""
         self._check_rows(feat)
-        return self._network(run, lambda: self.eng.c3d2_stage1(feat, crop_idx, self.stage1_tables(), cubes_per_clip=int(crop_idx.shape[1])))
+        return self._network(run, lambda: self.eng.c3d2_stage1(feat, crop_idx, self.stage1_tables(), cubes_per_clip=int(crop_idx.shape[1]),
+                                                               live_cols=17))
 
     def _network(self, run, stage1):
-        """The seven kernels behind `stage1()`, each through the timing hook."""
+        """The seven kernels behind `stage1()`, each through the timing hook.  The first block's output goes to the second block
+        and nowhere else, so the callers ask for its 17 live columns (Engine.c3d2_stage1)."""
         eng = self.eng
         y = run("stage1", stage1)
         z = run("stage2", lambda: eng.c3d2_stage2(y, self.stage2_tables()))
