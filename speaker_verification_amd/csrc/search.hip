@@ -8,6 +8,7 @@
 
 #include "score_common.h"
 #include "svk_internal.h"
+#include "svk_search_norm.h"
 
 namespace {
 
@@ -84,12 +85,20 @@ __device__ __forceinline__ void sr_insert(uint2* __restrict__ row_list, int k, i
 // rows' k-th scores as thresholds (NaN while the list is not full: everything passes; +inf for a k-th score of NaN).
 // Columns arrive in ascending order, so a score EQUAL to the threshold loses on its index: the test is one `>` per score
 // and one ballot per block; only a block in which some score passes walks its candidates, one insertion at a time.
-template <bool HOIST>
+// NORM (svk_cosine_topk_norm): bit 0 = the query rows' {mean, std} table qmom is given, bit 1 = the gallery rows' gmom.  The
+// selection then ranks norm_value of the raw score (score_common.h: svk_score_norm's expression, float64) in place of the
+// raw score; thresholds, lists, write-out and phase 2 hold normalised values and do not know it.  A lane keeps the moment
+// pairs of its eight rows in registers for the whole kernel and loads its two columns' pairs per gallery tile, next to sinv
+// (the kernel is LDS-bound at two waves per SIMD, so the registers are free: DESIGN 3.19).  NORM == 0 is the plain search and
+// reads neither table.
+template <bool HOIST, int NORM>
 __global__ __launch_bounds__(256) void search_tiles_kernel(const float* __restrict__ query, const float* __restrict__ gallery,
                                                            const float* __restrict__ qinv, const float* __restrict__ ginv,
                                                            int nq, int ng, int dim, int k, int spans, int tiles,
                                                            long long index_base, const long long* __restrict__ exclude,
-                                                           float* __restrict__ ws_score, int* __restrict__ ws_idx) {
+                                                           float* __restrict__ ws_score, int* __restrict__ ws_idx,
+                                                           const double* __restrict__ qmom, const double* __restrict__ gmom) {
+  constexpr bool NORM_Q = (NORM & 1) != 0, NORM_G = (NORM & 2) != 0;
   __shared__ __attribute__((aligned(16))) float bs[2][SR_BN * SR_LD];
   __shared__ __attribute__((aligned(16))) uint2 lists[SR_BM * SR_KMAX];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -137,12 +146,15 @@ __global__ __launch_bounds__(256) void search_tiles_kernel(const float* __restri
   }
   float rinv[2][4], thr[2][4];
   int exc[2][4];
+  double qmu[2][4], qsd[2][4];   // NORM_Q only; a row past the query reads the last row's pair and is never a candidate
 #pragma unroll
   for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = m0 + 16 * rt + 4 * kk + r;
       rinv[rt][r] = qinv[min(row, nq - 1)];
+      qmu[rt][r] = NORM_Q ? qmom[2 * (size_t)min(row, nq - 1)] : 0.0;
+      qsd[rt][r] = NORM_Q ? qmom[2 * (size_t)min(row, nq - 1) + 1] : 0.0;
       thr[rt][r] = __builtin_nanf("");
       exc[rt][r] = -1;
       if (exclude && row < nq) {
@@ -152,7 +164,8 @@ __global__ __launch_bounds__(256) void search_tiles_kernel(const float* __restri
     }
   const bool rows_in = m0 + 32 <= nq;  // wave-uniform
 
-  auto select = [&](const f32x4 (&accv)[2][2], int st, const float (&sinv)[2]) __attribute__((always_inline)) {
+  auto select = [&](const f32x4 (&accv)[2][2], int st, const float (&sinv)[2], const double (&gmu)[2],
+                    const double (&gsd)[2]) __attribute__((always_inline)) {
     const bool ragged = !rows_in || (st + 1) * SR_BN > ng;  // wave-uniform
     float sc[2][2][4];
     bool pass[2][2][4];
@@ -164,6 +177,7 @@ __global__ __launch_bounds__(256) void search_tiles_kernel(const float* __restri
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           sc[rt][ct][r] = accv[rt][ct][r] * rinv[rt][r] * sinv[ct];
+          if (NORM) sc[rt][ct][r] = norm_value(sc[rt][ct][r], NORM_Q, qmu[rt][r], qsd[rt][r], NORM_G, gmu[ct], gsd[ct]);
           bool p = !(sc[rt][ct][r] <= thr[rt][r]);
           if (ragged) p = p && (m0 + 16 * rt + 4 * kk + r < nq) && (st * SR_BN + 16 * ct + i < ng);
           pass[rt][ct][r] = p;
@@ -210,10 +224,13 @@ __global__ __launch_bounds__(256) void search_tiles_kernel(const float* __restri
 #pragma unroll
       for (int ct = 0; ct < 2; ++ct) acc[rt][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float sinv[2];
+    double gmu[2], gsd[2];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
       const int col = st * SR_BN + 16 * ct + i;
       sinv[ct] = ginv[col < ng ? col : ng - 1];
+      gmu[ct] = NORM_G ? gmom[2 * (size_t)(col < ng ? col : ng - 1)] : 0.0;
+      gsd[ct] = NORM_G ? gmom[2 * (size_t)(col < ng ? col : ng - 1) + 1] : 0.0;
     }
     for (int kb = 0; kb < nkb; ++kb) {
       // prefetch the next (gallery block, K block) while this one is multiplied
@@ -250,7 +267,7 @@ __global__ __launch_bounds__(256) void search_tiles_kernel(const float* __restri
       __syncthreads();  // everyone is done with bs[cur]; bs[cur ^ 1] is complete
       cur ^= 1;
     }
-    select(acc, st, sinv);   // between two workgroup barriers: the lists are this wave's own
+    select(acc, st, sinv, gmu, gsd);   // between two workgroup barriers: the lists are this wave's own
   }
 
   // this unit's partial lists: [span][query row][k], columns still local to this call's gallery
@@ -372,19 +389,18 @@ __global__ __launch_bounds__(64) void search_merge_kernel(const float* __restric
   }
 }
 
-}  // namespace
+using sr_tiles_fn = void (*)(const float*, const float*, const float*, const float*, int, int, int, int, int, int, long long,
+                             const long long*, float*, int*, const double*, const double*);
+// [dim <= SR_KB: the hoisted instance][NORM]
+const sr_tiles_fn sr_tiles_kernels[2][4] = {
+    {search_tiles_kernel<false, 0>, search_tiles_kernel<false, 1>, search_tiles_kernel<false, 2>, search_tiles_kernel<false, 3>},
+    {search_tiles_kernel<true, 0>, search_tiles_kernel<true, 1>, search_tiles_kernel<true, 2>, search_tiles_kernel<true, 3>}};
 
-extern "C" {
-
-size_t svk_cosine_topk_workspace_bytes(int32_t n_query, int32_t n_gallery, int32_t dim, int32_t k) {
-  sr_plan p;
-  return sr_make_plan(n_query, n_gallery, dim, k, &p) ? p.bytes : 0;
-}
-
-int svk_cosine_topk(svk_ctx* ctx, const float* d_query, int32_t n_query, const float* d_gallery, int32_t n_gallery,
-                    int32_t dim, int32_t k, int64_t index_base, const int64_t* d_exclude, int32_t flags, void* d_workspace,
-                    size_t workspace_bytes, float* d_top_score, int64_t* d_top_index) {
-  if (!ctx) return SVK_ERR_BAD_ARG;
+// svk_cosine_topk (both tables NULL) and svk_cosine_topk_norm: one set of argument rules, one plan, one launch sequence.
+int sr_search(svk_ctx* ctx, const float* d_query, int32_t n_query, const float* d_gallery, int32_t n_gallery, int32_t dim,
+              int32_t k, int64_t index_base, const int64_t* d_exclude, int32_t flags, const double* d_query_moments,
+              const double* d_gallery_moments, void* d_workspace, size_t workspace_bytes, float* d_top_score,
+              int64_t* d_top_index) {
   SVK_REQUIRE(ctx, n_query >= 0 && n_gallery >= 0, "negative size");
   SVK_REQUIRE(ctx, dim >= 1 && dim <= 4096, "dim must be in [1, 4096]");
   SVK_REQUIRE(ctx, k >= 1 && k <= SR_KMAX, "k must be in [1, 32]");
@@ -408,6 +424,8 @@ int svk_cosine_topk(svk_ctx* ctx, const float* d_query, int32_t n_query, const f
   SVK_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(d_query) | reinterpret_cast<uintptr_t>(d_gallery)) & 3) == 0,
               "rows must be 4-byte aligned");
   SVK_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(d_workspace) & 15) == 0, "the workspace must be 16-byte aligned");
+  SVK_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(d_query_moments) | reinterpret_cast<uintptr_t>(d_gallery_moments)) & 7) == 0,
+              "the moment tables must be 8-byte aligned");
   sr_plan p;
   sr_make_plan(n_query, n_gallery, dim, k, &p);
   if (workspace_bytes < p.bytes)
@@ -421,10 +439,11 @@ int svk_cosine_topk(svk_ctx* ctx, const float* d_query, int32_t n_query, const f
 
   svk_launch_inv_norm(ctx, d_query, n_query, dim, qinv);   // scoring.hip's pre-pass (one wave per row), here for both matrices
   svk_launch_inv_norm(ctx, d_gallery, n_gallery, dim, ginv);
-  auto kern = dim <= SR_KB ? search_tiles_kernel<true> : search_tiles_kernel<false>;
+  const int norm = (d_query_moments ? 1 : 0) | (d_gallery_moments ? 2 : 0);
+  const sr_tiles_fn kern = sr_tiles_kernels[dim <= SR_KB ? 1 : 0][norm];
   hipLaunchKernelGGL(kern, dim3((unsigned)(p.n_rb * p.spans)), dim3(256), 0, ctx->stream, d_query, d_gallery, qinv, ginv,
                      n_query, n_gallery, dim, k, p.spans, p.tiles, (long long)index_base,
-                     reinterpret_cast<const long long*>(d_exclude), ws_score, ws_idx);
+                     reinterpret_cast<const long long*>(d_exclude), ws_score, ws_idx, d_query_moments, d_gallery_moments);
   if (p.spans == 1 && !accumulate) {
     hipLaunchKernelGGL(search_convert_kernel, dim3(flat_grid), dim3(256), 0, ctx->stream, ws_score, ws_idx, n_out,
                        (long long)index_base, d_top_score, reinterpret_cast<long long*>(d_top_index));
@@ -435,6 +454,38 @@ int svk_cosine_topk(svk_ctx* ctx, const float* d_query, int32_t n_query, const f
   }
   SVK_LAUNCH_CHECK(ctx);
   return SVK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t svk_cosine_topk_workspace_bytes(int32_t n_query, int32_t n_gallery, int32_t dim, int32_t k) {
+  sr_plan p;
+  return sr_make_plan(n_query, n_gallery, dim, k, &p) ? p.bytes : 0;
+}
+
+int svk_cosine_topk(svk_ctx* ctx, const float* d_query, int32_t n_query, const float* d_gallery, int32_t n_gallery,
+                    int32_t dim, int32_t k, int64_t index_base, const int64_t* d_exclude, int32_t flags, void* d_workspace,
+                    size_t workspace_bytes, float* d_top_score, int64_t* d_top_index) {
+  if (!ctx) return SVK_ERR_BAD_ARG;
+  return sr_search(ctx, d_query, n_query, d_gallery, n_gallery, dim, k, index_base, d_exclude, flags, nullptr, nullptr, d_workspace,
+                   workspace_bytes, d_top_score, d_top_index);
+}
+
+size_t svk_cosine_topk_norm_workspace_bytes(int32_t n_query, int32_t n_gallery, int32_t dim, int32_t k) {
+  return svk_cosine_topk_workspace_bytes(n_query, n_gallery, dim, k);
+}
+
+int svk_cosine_topk_norm(svk_ctx* ctx, const float* d_query, int32_t n_query, const float* d_gallery, int32_t n_gallery,
+                         int32_t dim, int32_t k, int64_t index_base, const int64_t* d_exclude, int32_t flags,
+                         const double* d_query_moments, const double* d_gallery_moments, void* d_workspace,
+                         size_t workspace_bytes, float* d_top_score, int64_t* d_top_index) {
+  if (!ctx) return SVK_ERR_BAD_ARG;
+  SVK_REQUIRE(ctx, d_query_moments || d_gallery_moments,
+              "no moment table: give the query table, the gallery table or both (svk_cosine_topk ranks raw scores)");
+  return sr_search(ctx, d_query, n_query, d_gallery, n_gallery, dim, k, index_base, d_exclude, flags, d_query_moments,
+                   d_gallery_moments, d_workspace, workspace_bytes, d_top_score, d_top_index);
 }
 
 }  // extern "C"

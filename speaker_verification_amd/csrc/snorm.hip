@@ -235,14 +235,6 @@ __global__ __launch_bounds__(RT) void cohort_moments_kernel(const unsigned* __re
   }
 }
 
-// One entry of the normalised matrix: float64 throughout, every operation rounded on its own, in the order written.
-__device__ __forceinline__ float norm_value(float s, bool has_r, double mu_r, double sd_r, bool has_c, double mu_c, double sd_c) {
-#pragma clang fp contract(off)
-  const double x = (double)s;
-  if (has_r && has_c) return (float)(0.5 * ((x - mu_r) / sd_r + (x - mu_c) / sd_c));
-  return (float)(has_r ? (x - mu_r) / sd_r : (x - mu_c) / sd_c);
-}
-
 // Four consecutive columns of one row per thread; workgroup b = row b / tiles, columns 4 RT (b % tiles) onwards.  Every load
 // of a thread precedes its stores and no other thread touches its entries: d_out may be the scores themselves.
 template <bool VEC>

@@ -1387,16 +1387,10 @@ class Engine:
                                             self._ptr(out), self._ptr(bad_count)), self.ctx)
         return out
 
-    def cosine_topk(self, query, gallery, k, exclude=None, index_base=0, into=None):
-        """svk_cosine_topk: the k best gallery rows of every query row by cosine score, without the score matrix ->
-        (scores float32 [n, k], indices int64 [n, k]) on the device, best first; an index is index_base + the gallery row,
-        empty slots hold -1 / -inf.  Higher score first, NaN above every number, the lower index among equal scores.
-        exclude: int64 [n], the global index that is no candidate for each query (a self-search).  into=(scores, indices):
-        accumulate into those tensors (lists of earlier calls over other chunks of the gallery, disjoint index ranges); the
-        result equals one call over the whole gallery bit for bit.  The workspace is a torch allocation sized by the library."""
+    def _search_lists(self, n, k, exclude, into):
+        """The operands `cosine_topk` and `cosine_topk_norm` share: (exclude as int64 [n] on the device or None, scores,
+        indices), the two lists fresh or the caller's `into`."""
         torch = _torch()
-        q, g = self._two_matrices(query, gallery, "cosine_topk")
-        n, ng, dim, k = int(q.shape[0]), int(g.shape[0]), int(q.shape[1]), int(k)
         ex = None
         if exclude is not None:
             ex = self.to_device(exclude, torch.int64).reshape(-1)
@@ -1409,11 +1403,44 @@ class Engine:
             scores, indices = into
             for t, dt in ((scores, torch.float32), (indices, torch.int64)):
                 self._given_out(t, (n, k), dt, "into wants contiguous device tensors (float32 [n, k], int64 [n, k])")
+        return ex, scores, indices
+
+    def cosine_topk(self, query, gallery, k, exclude=None, index_base=0, into=None):
+        """svk_cosine_topk: the k best gallery rows of every query row by cosine score, without the score matrix ->
+        (scores float32 [n, k], indices int64 [n, k]) on the device, best first; an index is index_base + the gallery row,
+        empty slots hold -1 / -inf.  Higher score first, NaN above every number, the lower index among equal scores.
+        exclude: int64 [n], the global index that is no candidate for each query (a self-search).  into=(scores, indices):
+        accumulate into those tensors (lists of earlier calls over other chunks of the gallery, disjoint index ranges); the
+        result equals one call over the whole gallery bit for bit.  The workspace is a torch allocation sized by the library."""
+        q, g = self._two_matrices(query, gallery, "cosine_topk")
+        n, ng, dim, k = int(q.shape[0]), int(g.shape[0]), int(q.shape[1]), int(k)
+        ex, scores, indices = self._search_lists(n, k, exclude, into)
         work = self._workspace(self.lib.svk_cosine_topk_workspace_bytes(n, ng, dim, k))
         self._stream()
         check(self.lib.svk_cosine_topk(self.ctx, self._ptr(q), n, self._ptr(g), ng, dim, k, int(index_base), self._ptr(ex),
                                        0 if into is None else 1, self._ptr(work), work.numel(), self._ptr(scores),
                                        self._ptr(indices)), self.ctx)
+        return scores, indices
+
+    def cosine_topk_norm(self, query, gallery, k, query_moments=None, gallery_moments=None, exclude=None, index_base=0, into=None):
+        """svk_cosine_topk_norm: `cosine_topk` ranked by the NORMALISED score -- `score_norm`'s expression on the cosine, bit
+        for bit, inside the selection; the score matrix is never written -> (normalised scores float32 [n, k], indices int64
+        [n, k]) on the device.  query_moments float64 [n, 2] (the T-norm side, `score_norm`'s row table), gallery_moments
+        float64 [n_gallery, 2] of THIS call's gallery rows (the Z-norm side, the column table), as `cohort_moments` returns
+        them; one of the two may be None, not both (that is `cosine_topk`).  exclude, index_base and into as in `cosine_topk`;
+        the lists in `into` hold normalised scores."""
+        q, g = self._two_matrices(query, gallery, "cosine_topk_norm")
+        n, ng, dim, k = int(q.shape[0]), int(g.shape[0]), int(q.shape[1]), int(k)
+        qm, gm = self._moments(query_moments, n, "query_moments"), self._moments(gallery_moments, ng, "gallery_moments")
+        # an empty tensor has no address, and the entry tells a given table by its address: an empty side (a chunk without
+        # rows) hands over one spare pair, of which the entry reads nothing
+        qm, gm = (m.new_empty((1, 2)) if m is not None and m.shape[0] == 0 else m for m in (qm, gm))
+        ex, scores, indices = self._search_lists(n, k, exclude, into)
+        work = self._workspace(self.lib.svk_cosine_topk_norm_workspace_bytes(n, ng, dim, k))
+        self._stream()
+        check(self.lib.svk_cosine_topk_norm(self.ctx, self._ptr(q), n, self._ptr(g), ng, dim, k, int(index_base), self._ptr(ex),
+                                            0 if into is None else 1, self._ptr(qm), self._ptr(gm), self._ptr(work),
+                                            work.numel(), self._ptr(scores), self._ptr(indices)), self.ctx)
         return scores, indices
 
     def l2_dist(self, a, b):

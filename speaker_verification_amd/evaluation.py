@@ -554,15 +554,21 @@ def identification_accuracy(model, data, labels=None, topk=(1, 5), batch=4096):
     return out
 
 
-def rank_speakers(test_embeddings, enroll_embeddings, speaker_ids, k=5, threshold=None):
+def rank_speakers(test_embeddings, enroll_embeddings, speaker_ids, k=5, threshold=None, pipeline=None):
     """The k nearest enrolled speakers of every test utterance (`svk_cosine_topk`: no score matrix) -> {"ids": [n][k] lists of
     speaker ids, best first, "scores": float32 [n, k], "indices": int64 [n, k]} (NumPy).  speaker_ids[j] names row j of
     enroll_embeddings.  threshold: open-set rejection -- an entry whose score is below it (or a slot past the enrolled rows,
-    index -1) is reported as None; a NaN score is never below a threshold."""
+    index -1) is reported as None; a NaN score is never below a threshold.
+    pipeline: a `VerificationPipeline`; ranks, scores and the rejection are then `pipeline.identify`'s -- the scores of its
+    back end, score normalisation and calibration.  On calibrated scores the threshold of an operating point is
+    `calibration.bayes_threshold(p_target, c_miss, c_fa)`, which, unlike a raw cosine threshold, transfers between speakers."""
     speaker_ids = list(speaker_ids)
     if len(speaker_ids) != int(enroll_embeddings.shape[0]):
         raise ValueError("one speaker id per enrolled row")
-    scores, indices = get_engine().cosine_topk(test_embeddings, enroll_embeddings, k)
+    if pipeline is None:
+        scores, indices = get_engine().cosine_topk(test_embeddings, enroll_embeddings, k)
+    else:
+        scores, indices = pipeline.identify(test_embeddings, enroll_embeddings, k=k)
     scores, indices = scores.cpu().numpy(), indices.cpu().numpy()
     keep = indices >= 0
     if threshold is not None:

@@ -146,12 +146,13 @@ class VerificationPipeline:
         None (the default) changes no code path.
         calibration: a fitted one-system `calibration.Calibration` (fitted on the scores this pipeline produces: cosines, or
         with `plda` its LLRs), or None.  With one, `score` and `score_trials` return calibrated log-likelihood ratios
-        (svk_calibration_apply, in place on the fresh scores) and `decide` thresholds them; `search` raises ValueError.  None
-        (the default) changes no code path.
+        (svk_calibration_apply, in place on the fresh scores) and `decide` thresholds them; `search` raises ValueError, `identify`
+        ranks by the calibrated score.  None (the default) changes no code path.
         score_norm: a `score_norm.ScoreNorm` fitted on a cohort with this pipeline's `backend` and `plda`, or None.  With one,
         `score` and `score_trials` normalise between the raw score and the calibration (svk_cohort_moments of both sides
         against the cohort, then svk_score_norm / svk_score_norm_pairs in place on the fresh scores; a calibration is then one
-        fitted on normalised scores); `search` raises ValueError.  None (the default) changes no code path.
+        fitted on normalised scores); `search` raises ValueError, `identify` ranks by the normalised score (svk_cosine_topk_norm).
+        None (the default) changes no code path.
         vad: a `vad.AdaptiveEnergyVad`, or None.  With one, `voiced` and `vad` -- and so `embed`, the ragged and arena paths and
         `diarize` -- decide by the level-adaptive rule (svk_vad_adaptive: thresholds from each clip's own frame-energy
         quantiles) and `vad_threshold` is unused; together with use_vad=False it is a ValueError.  None (the default) is the
@@ -830,9 +831,14 @@ class VerificationPipeline:
         if self.plda is not None:
             raise ValueError("search ranks by cosine score: top-k by PLDA log-likelihood ratio is not built (use score)")
         if self.calibration is not None:
-            raise ValueError("search ranks by raw cosine score: calibrated top-k is not built (use score)")
+            raise ValueError("search ranks by raw cosine score: calibrated top-k is `identify` (or use score)")
         if self.score_norm is not None:
-            raise ValueError("search ranks by raw cosine score: top-k on normalised scores is not built (use score)")
+            raise ValueError("search ranks by raw cosine score: top-k on normalised scores is `identify` (or use score)")
+        return self._search(test_emb, enroll_emb, k, exclude_self, chunk_rows, None)
+
+    def _search(self, test_emb, enroll_emb, k, exclude_self, chunk_rows, score_norm):
+        """`search` (score_norm None: svk_cosine_topk) and `identify` (a ScoreNorm: svk_cosine_topk_norm, the test side's
+        moments taken once, the enrolled side's per gallery chunk) over one chunking rule."""
         eng = self.eng
         n_gallery, dim = int(enroll_emb.shape[0]), int(enroll_emb.shape[1])
         query = self.project(eng.to_device(test_emb, torch.float32))
@@ -841,19 +847,63 @@ class VerificationPipeline:
             if int(query.shape[0]) != n_gallery:
                 raise ValueError("exclude_self wants the same rows on both sides (%d against %d)" % (query.shape[0], n_gallery))
             exclude = torch.arange(n_gallery, dtype=torch.int64, device=eng.device)
+        if score_norm is None:
+            def topk(rows, **kw):
+                return eng.cosine_topk(query, rows, k, exclude=exclude, **kw)
+        else:
+            sides = score_norm.mode        # a side the mode does not use is not computed; _tables drops it
+            test_moments = score_norm.moments(query, "test") if sides in ("t", "s") else None
+
+            def topk(rows, **kw):
+                row, col = score_norm._tables(test_moments, score_norm.moments(rows, "enroll") if sides in ("z", "s") else None)
+                return eng.cosine_topk_norm(query, rows, k, query_moments=row, gallery_moments=col, exclude=exclude, **kw)
         on_host = not (isinstance(enroll_emb, torch.Tensor) and enroll_emb.is_cuda)
         if chunk_rows is None and on_host and 4 * n_gallery * dim > self.SEARCH_UPLOAD_BYTES:
             chunk_rows = max(1, self.SEARCH_UPLOAD_BYTES // (4 * dim))
         if chunk_rows is None or n_gallery == 0:
-            return eng.cosine_topk(query, self.project(enroll_emb), k, exclude=exclude)
+            return topk(self.project(enroll_emb))
         chunk_rows = int(chunk_rows)
         if chunk_rows < 1:
             raise ValueError("chunk_rows must be at least 1")
         into = None
         for lo in range(0, n_gallery, chunk_rows):
-            out = eng.cosine_topk(query, self.project(enroll_emb[lo:lo + chunk_rows]), k, exclude=exclude, index_base=lo, into=into)
-            into = out
+            into = topk(self.project(enroll_emb[lo:lo + chunk_rows]), index_base=lo, into=into)
         return into
+
+    def identify(self, test_emb, enroll_emb, k=1, exclude_self=False, chunk_rows=None):
+        """The k best enrolled rows of every test row under the scores `score` gives -- the cosine through the back end, the
+        score normalisation and the calibration -- without the test x enrolled matrix -> (scores float32 [n, k], indices int64
+        [n, k]) on the device, best first, -1 / -inf past the enrolled rows.  Open-set identification: reject the returned
+        scores at `calibration.bayes_threshold` (`decide`), a threshold that transfers between speakers and conditions where
+        a raw cosine's does not.
+        With `score_norm` the normalisation sits inside the selection (`svk_cosine_topk_norm`: for one test row the normalised
+        score is no monotone function of the cosine across enrolled rows, so `search`'s lists cannot be re-ranked into
+        these); the test side's cohort moments are taken once, the enrolled side's per gallery chunk (a row's moments depend
+        on that row alone).  The scores are `svk_score_norm`'s bits on `svk_cosine_topk`'s raw bits.
+        With `calibration` (one system, weight > 0) `calibration.apply` then runs on the returned [n, k] scores in place.  The
+        map is increasing, so the ranking is the normalised score's: calibrated values are NON-INCREASING along a list, not
+        strictly decreasing, and entries that the final rounding to float32 makes equal keep the order of their
+        uncalibrated scores (which need not be index order).  A weight <= 0 (a decreasing map) or anything but an affine
+        one-system calibration raises ValueError; so does a PLDA: top-k by log-likelihood ratio is not built.
+        With neither normalisation nor calibration the result is `search`'s, byte for byte.  Chunking (chunk_rows, host
+        galleries above SEARCH_UPLOAD_BYTES) and exclude_self behave as in `search`: the same bytes as one call."""
+        if self.plda is not None:
+            raise ValueError("identify ranks by cosine-based scores: top-k by PLDA log-likelihood ratio is not built (use score)")
+        cal = self.calibration
+        if cal is not None:
+            weights = getattr(cal, "weights_", None)
+            if weights is None or np.size(weights) != 2:
+                raise ValueError("identify wants a fitted affine calibration of ONE system (weight, offset): a fusion of several "
+                                 "systems or a step map does not rank by this pipeline's score")
+            if not float(np.asarray(weights).reshape(-1)[0]) > 0.0:
+                raise ValueError("identify wants a calibration weight > 0 (an increasing map keeps the ranking), got %r"
+                                 % (float(np.asarray(weights).reshape(-1)[0]),))
+        if self.score_norm is not None:
+            self.score_norm.check_scorer(self.backend, self.plda)
+        scores, indices = self._search(test_emb, enroll_emb, k, exclude_self, chunk_rows, self.score_norm)
+        if cal is not None:
+            cal.apply(scores.reshape(-1), engine=self.eng, out=scores.reshape(-1))
+        return scores, indices
 
     def diarize(self, pcm, **kw):
         """"Who spoke when": int16 PCM [n_rec, samples] of recordings with several speakers -> one list of
