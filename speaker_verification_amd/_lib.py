@@ -159,6 +159,14 @@ SEARCH_NORM_SIGNATURES = {
     "svk_cosine_topk_norm": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
 }
 
+# Entries of include/svk_cluster.h (corpus clustering from k-NN lists): load() binds them after the other tables;
+# tests/test_knn_cluster_host.py checks this table against that header and the built library.
+KNN_CLUSTER_MUTUAL = 1             # svk_knn_cluster's flag bit 0 (SVK_KNN_CLUSTER_MUTUAL)
+CLUSTER_SIGNATURES = {
+    "svk_knn_cluster_workspace_bytes": (C.c_size_t, [_i64, _i32]),
+    "svk_knn_cluster": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _f32, _i32, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -178,7 +186,7 @@ def load():
             pass
         lib = C.CDLL(LIB_PATH)
         for name, (restype, argtypes) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(ROCCH_SIGNATURES.items()) \
-                + list(SEARCH_NORM_SIGNATURES.items()):
+                + list(SEARCH_NORM_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()):
             fn = getattr(lib, name)            # AttributeError if the .so is stale
             fn.restype = restype
             fn.argtypes = argtypes
@@ -200,14 +208,14 @@ def check(rc, ctx=None):
 
 def provenance():
     """What a measurement was made with: {"csrc_sha": sha256 over the kernel sources (csrc/*.hip, csrc/*.h, csrc/Makefile,
-    include/svk.h, include/svk_vad.h, include/svk_rocch.h, include/svk_search_norm.h: file names + bytes, sorted), "libsvk_sha": sha256 of the built library}, 16 hex digits each.  Profiles
+    include/svk.h, include/svk_vad.h, include/svk_rocch.h, include/svk_search_norm.h, include/svk_cluster.h: file names + bytes, sorted), "libsvk_sha": sha256 of the built library}, 16 hex digits each.  Profiles
     under profiles/ carry it (tools/summarize_prof.py) and bench.py marks a roofline row `stale` when the counters it uses
     were collected from other kernel sources than the ones it runs."""
     import hashlib
     here = os.path.dirname(os.path.abspath(__file__))
     csrc = os.path.join(here, "csrc")
     files = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h")) or f == "Makefile")
-    files += [os.path.join(os.path.dirname(here), "include", name) for name in ("svk.h", "svk_vad.h", "svk_rocch.h", "svk_search_norm.h")]
+    files += [os.path.join(os.path.dirname(here), "include", name) for name in ("svk.h", "svk_vad.h", "svk_rocch.h", "svk_search_norm.h", "svk_cluster.h")]
     h = hashlib.sha256()
     for path in files:
         h.update(os.path.basename(path).encode())

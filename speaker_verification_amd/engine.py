@@ -1443,6 +1443,29 @@ class Engine:
                                             work.numel(), self._ptr(scores), self._ptr(indices)), self.ctx)
         return scores, indices
 
+    def knn_cluster(self, nbr_score, nbr_index, k=None, *, threshold, min_shared=0, mutual=True, min_size=1):
+        """svk_knn_cluster (include/svk_cluster.h): the connected components of the shared-neighbour graph read off the k-NN
+        lists of a self-search (`cosine_topk(x, x, k, exclude=arange(n))`: float32 / int64 [n, list_stride]) -> (labels int32
+        [n], roots int32 [n], sizes int32 [n], counts int32 [4]) on the device.  Only the first k slots of a row count (None:
+        all of them).  An edge {i, j} needs the arcs i -> j and j -> i (mutual; either one otherwise), an arc a slot with
+        score >= threshold (float32; -inf: every slot), and at least min_shared common neighbours.  roots[i] is the smallest
+        row of i's component; components of at least min_size rows are labelled 0 .. C-1 by their smallest member, the other
+        rows -1; sizes holds the C cluster sizes, then zeros; counts = (C, rows labelled -1, bad slots, gave_up)."""
+        torch = _torch()
+        sc, ix = self.to_device(nbr_score, torch.float32), self.to_device(nbr_index, torch.int64)
+        if sc.dim() != 2 or tuple(sc.shape) != tuple(ix.shape):
+            raise ValueError("knn_cluster wants the two lists of a search: float32 [n, list_stride] and int64 [n, list_stride]")
+        n, stride = int(sc.shape[0]), int(sc.shape[1])
+        k = stride if k is None else int(k)
+        labels, roots, sizes = (torch.empty((n,), dtype=torch.int32, device=self.device) for _ in range(3))
+        counts = torch.empty((4,), dtype=torch.int32, device=self.device)
+        work = self._workspace(self.lib.svk_knn_cluster_workspace_bytes(n, k))
+        self._stream()
+        check(self.lib.svk_knn_cluster(self.ctx, self._ptr(sc), self._ptr(ix), n, k, stride, float(threshold), int(min_shared),
+                                       int(min_size), _lib.KNN_CLUSTER_MUTUAL if mutual else 0, self._ptr(work), work.numel(),
+                                       self._ptr(labels), self._ptr(roots), self._ptr(sizes), self._ptr(counts)), self.ctx)
+        return labels, roots, sizes, counts
+
     def l2_dist(self, a, b):
         torch = _torch()
         a, b = self._two_matrices(a, b, "l2_dist")

@@ -905,6 +905,26 @@ class VerificationPipeline:
             cal.apply(scores.reshape(-1), engine=self.eng, out=scores.reshape(-1))
         return scores, indices
 
+    def cluster(self, emb, *, k, threshold, min_shared=0, mutual=True, min_size=1, chunk_rows=None):
+        """Pseudo-speaker labels for unlabelled rows: the self-search of `search` (exclude_self; with a back end the rows
+        are projected first; chunk_rows as there) and `svk_knn_cluster` on its lists -> `clustering.Clustering(labels, roots,
+        sizes, counts)` on the device.  Rows i and j are joined when each is among the other's k nearest with a cosine >=
+        threshold (mutual=False: one direction is enough) and they share at least min_shared of their k neighbours; a cluster
+        is a connected component of at least min_size rows, numbered by its smallest row, and the other rows are labelled -1.
+        k (1 .. 32) and threshold have no default: nothing tuned is built in.  `clustering.segments` turns the labels into
+        what `backend.solve` and `enroll_mean`'s pool take.  The lists are raw cosines: with a PLDA, a score normalisation or
+        a calibration this raises, as `search` does."""
+        from .clustering import Clustering
+        if self.plda is not None:
+            raise ValueError("cluster ranks by cosine score: top-k by PLDA log-likelihood ratio is not built (use score)")
+        if self.calibration is not None:
+            raise ValueError("cluster ranks by raw cosine score: calibrated top-k is `identify` (or use score)")
+        if self.score_norm is not None:
+            raise ValueError("cluster ranks by raw cosine score: top-k on normalised scores is `identify` (or use score)")
+        scores, indices = self._search(emb, emb, k, True, chunk_rows, None)
+        return Clustering(*self.eng.knn_cluster(scores, indices, threshold=threshold, min_shared=min_shared, mutual=mutual,
+                                                min_size=min_size))
+
     def diarize(self, pcm, **kw):
         """"Who spoke when": int16 PCM [n_rec, samples] of recordings with several speakers -> one list of
         `diarization.Turn(start_s, end_s, speaker)` per recording (`diarization.Diarizer.diarize`, which lists the keywords:

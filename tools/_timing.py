@@ -48,6 +48,7 @@ def load_lib():
         _lib.EXT_SIGNATURES = {k: v for k, v in _lib.EXT_SIGNATURES.items() if hasattr(lib, k)}
         _lib.ROCCH_SIGNATURES = {k: v for k, v in _lib.ROCCH_SIGNATURES.items() if hasattr(lib, k)}
         _lib.SEARCH_NORM_SIGNATURES = {k: v for k, v in _lib.SEARCH_NORM_SIGNATURES.items() if hasattr(lib, k)}
+        _lib.CLUSTER_SIGNATURES = {k: v for k, v in _lib.CLUSTER_SIGNATURES.items() if hasattr(lib, k)}
     return _lib, _lib.load()
 
 
