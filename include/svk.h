@@ -19,7 +19,7 @@
  *     and are asynchronous w.r.t. the host; svk_sync waits for that stream.
  *   - a context is bound to one device and is not thread-safe.
  *   - the memory contract (tests/memory_contract.py; tests/test_memory_contract_{scoring,backend,evaluation,diarization,
- *     frontend,stages,ingest,network}.py hold every entry that touches device memory to it on guarded buffers, and
+ *     frontend,stages,ingest,network,vad_adaptive,rocch,search_norm,cluster}.py hold every entry that touches device memory to it on guarded buffers, and
  *     tests/test_memory_contract_helper.py walks the sources so that none is left out):
  *       a call writes only the buffers it documents as outputs, and only the elements it documents -- nothing in front of a
  *       buffer, behind it, in the padding between strided rows or in elements an entry calls "not written";
@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SVK_VERSION 114 /* 0.1.12 (number unchanged, additions only -- tests/test_identification.py pins it): + svk_spectral_embed, svk_spectral_limits, svk_spectral_workspace_bytes (spectral clustering for diarization: batched Jacobi eigendecompositions of graph Laplacians, the speaker count from the eigengap, the neighbour count by the normalised maximum eigengap); earlier under the same number: + svk_window_crops, svk_segment_affinity, svk_ahc, svk_ahc_limits, svk_ahc_workspace_bytes (speaker diarization: sliding-window crop tables, the window-against-window cosines of every recording and average-linkage clustering, one workgroup per recording); earlier under the same number: + svk_cohort_moments, svk_score_norm, svk_score_norm_pairs (adaptive score normalisation: the top-K cohort moments of every row by an exact radix select, and Z- / T- / S-norm from them); earlier under the same number: + svk_calibration_stats, svk_calibration_stats_workspace_bytes, svk_calibration_apply (score calibration and fusion: the statistics of a prior-weighted logistic regression in one pass, and the affine map); earlier under the same number: + svk_plda_scores, svk_plda_scores_workspace_bytes, svk_plda_pair_scores (PLDA log-likelihood ratios: the score matrix on the f32 matrix pipe, trial lists in float64); earlier under the same number: svk_c3d2_stage2 runs as one kernel and no longer touches d_act2, which may be NULL (same results, bit for bit); earlier under the same number: + svk_class_scatter, svk_class_scatter_workspace_bytes, svk_embedding_project (the embedding back end: class statistics in float64 and centre / project / length-normalise in one pass); earlier additions under the same number: + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag); earlier additions under the same number: + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run); earlier additions under the same number: + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows); + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass); 0.1.12: + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); 0.1.11: + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB); 0.1.10: + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True); 0.1.9: conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated; 0.1.8: svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks); 0.1.7: gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk); 0.1.6: one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn */
+#define SVK_VERSION 114 /* 0.1.12; what each version added: History, at the end of this header */
 
 typedef enum svk_status {
   SVK_OK = 0,
@@ -214,7 +214,61 @@ int svk_vad_energy(svk_ctx* ctx, const int16_t* d_pcm, const int64_t* d_offsets,
                    int32_t ring_len, int32_t ring_thresh, int64_t threshold, int32_t max_vad_frames,
                    uint8_t* d_keep, int32_t* d_seg, int32_t* d_n_vad_frames, int16_t* d_voiced,
                    int32_t* d_voiced_len, int32_t* d_src_frame);
-/* svk_vad.h declares svk_vad_adaptive: the same framer, hysteresis and outputs with a threshold derived per clip from its levels. */
+
+/* ---- level-adaptive energy VAD -------------------------------------------------
+ * The reference's per-frame decision is webrtcvad.Vad(3) (vad.py:90,152), which adapts to the signal's level;
+ * svk_vad_energy replaces it with ONE absolute threshold for every clip, so a quietly recorded clip loses all its frames.
+ * This entry is the same framer (vad.py:44-57, Q12), the same ring-buffer hysteresis (vad.py:60-129, Q13), the same
+ * compaction and index form as svk_vad_energy -- ring_len, ring_thresh, d_keep, d_seg, d_n_vad_frames, d_voiced,
+ * d_voiced_len and d_src_frame mean exactly what they mean there -- with a threshold derived PER CLIP from two order
+ * statistics of the clip's own frame energies.  All of it is integer arithmetic; no float is used anywhere.
+ *
+ * The rule.  A clip of L samples has nf = (2 L - 1) / (2 frame_samples) whole frames, capped at max_vad_frames (the samples
+ * of the partial frame behind them are not read); E_f = sum of x^2 over frame f (int64; frame_samples <= 65536 keeps
+ * E_f <= 2^46).
+ *     rank(q) = (q * (nf - 1)) >> 16
+ *     E_lo, E_hi = the rank(floor_q16)-th and the rank(peak_q16)-th smallest of the clip's E_f (0-based; ties are equal values)
+ *     A = (E_lo * above_floor_q16) >> 16,   B = (E_hi * below_peak_q16) >> 16     (the products are formed in 128 bits)
+ *     T = max(min(A, B), min_threshold * frame_samples)
+ *     frame f is speech  iff  E_f > T                                             (strict, like the absolute rule)
+ * A clip without a whole frame (nf == 0) has the levels {0, 0, min_threshold * frame_samples} and nothing else.
+ *   - below_peak_q16 = 0 is the absolute rule with threshold = min_threshold: every output equals svk_vad_energy's.
+ *   - with min_threshold = 0, multiplying every sample by 2^k (without clipping) changes no decision: E scales by 4^k exactly
+ *     and the floor of the shift moves T by less than one unscaled unit.
+ *   - a clip with no speech at all is kept whole unless min_threshold is set: the rule has only the clip's own levels.
+ *     min_threshold is the caller's absolute floor and costs the exact invariance.
+ *
+ * floor_q16, peak_q16 : the two quantiles times 65536, in [0, 65536], floor_q16 <= peak_q16
+ * above_floor_q16     : a linear power ratio times 65536, in [65536, 2^40]: T is at least this far above the floor level ...
+ * below_peak_q16      : a linear power ratio times 65536, in [0, 65536]: ... but no higher than this far below the peak level
+ * min_threshold       : >= 0, per sample like svk_vad_energy's threshold; min_threshold * frame_samples must fit 63 bits
+ * d_levels            : [n_utt][3] int64 = {E_lo, E_hi, T} per clip, or NULL
+ * d_energy            : [n_utt][max_vad_frames] int64, E_f of the clip's frames; entries from the clip's frame count on are
+ *                       left untouched; or NULL
+ *
+ * Refusals, each with a message that names the parameter and with no output written: SVK_ERR_BAD_ARG for a quantile or a
+ * ratio outside its domain, floor_q16 > peak_q16, a negative min_threshold or one whose product with frame_samples overflows,
+ * NULL d_pcm / d_keep, d_voiced or d_src_frame without d_voiced_len, d_voiced == d_pcm; SVK_ERR_UNSUPPORTED for
+ * frame_samples > 65536 and for max_vad_frames > 8192.  n_utt == 0 launches nothing.
+ *
+ * Asynchronous on the context's stream, no host round trip; workspaces come from the handle.  Routes (SVK_VAD_SPLIT = 0 / 1 / 2
+ * forces them as for svk_vad_energy: 1 the long-clip route, 2 the general one, 0 never the long-clip route):
+ *   short clips   frame_samples a multiple of 8 and <= 512, max_vad_frames <= 512: one kernel per clip; the energies stay in
+ *                 LDS, the order statistics come from rank counting
+ *   long clips    same frame geometry, max_vad_frames > 512: frame energies over frame chunks of the whole grid, then one
+ *                 workgroup per clip selects both order statistics exactly (radix select over the 8-bit digits of the 48-bit
+ *                 energies) and writes levels and flags, then svk_vad_energy's own walk and copy kernels
+ *   general       any other frame_samples: the same energy and select kernels with a frame loop for any length and
+ *                 alignment, then svk_vad_energy's general kernel for the walk and the copy
+ * On the last two the energies go through d_energy when it is given and through the handle's workspace otherwise.
+ */
+int svk_vad_adaptive(svk_ctx* ctx, const int16_t* d_pcm, const int64_t* d_offsets, const int32_t* d_lengths,
+                     int64_t clip_stride, int32_t clip_len, int32_t n_utt, int32_t frame_samples,
+                     int32_t ring_len, int32_t ring_thresh,
+                     int32_t floor_q16, int32_t peak_q16, int64_t above_floor_q16, int64_t below_peak_q16,
+                     int64_t min_threshold, int32_t max_vad_frames,
+                     uint8_t* d_keep, int32_t* d_seg, int32_t* d_n_vad_frames, int16_t* d_voiced,
+                     int32_t* d_voiced_len, int32_t* d_src_frame, int64_t* d_levels, int64_t* d_energy);
 
 /* ---- feature cube ------------------------------------------------------------
  * utils.py:351-379 (FeatureCube): out[u][0][c][r][:] = feat[u][crop[u][c] + r][:].
@@ -500,6 +554,44 @@ int svk_cosine_topk(svk_ctx* ctx, const float* d_query, int32_t n_query, const f
                     int32_t dim, int32_t k, int64_t index_base, const int64_t* d_exclude, int32_t flags,
                     void* d_workspace, size_t workspace_bytes, float* d_top_score, int64_t* d_top_index);
 
+/* ---- top-k search on normalised scores -------------------------------------------
+ * svk_cosine_topk_norm is svk_cosine_topk (above) in every respect except that it selects, merges and accumulates NORMALISED
+ * scores: the Z- / T- / S-norm of svk_score_norm sits inside the selection, and the [n_query x n_gallery] matrix is never
+ * written.  For a fixed query the normalised score is no monotone function of the raw score across gallery rows (every row
+ * has its own mean and deviation), so this ranking cannot be recovered from svk_cosine_topk's lists.
+ *
+ * The raw score s of (query row, gallery row) has exactly the bits svk_cosine_topk gives that pair: the same K order and
+ * the same acc * 1/|q| * 1/|g|.
+ *
+ * The ranked and returned score is svk_score_norm's expression on s, bit for bit:
+ *     both tables   f32(0.5 * ((s - mu_q) / sd_q + (s - mu_g) / sd_g))
+ *     one table     f32((s - mu) / sd)
+ * Each difference, quotient, sum and product is float64 and rounded on its own, in the order written, with no contraction.
+ * A zero, negative or NaN sd, or a NaN moment, gives what IEEE arithmetic gives; nothing is clamped.
+ *
+ * The order is svk_cosine_topk's total order applied to the normalised value: higher first, NaN above every number,
+ * -0 equal to +0, the lower index among equal normalised scores, empty slots (-inf, -1) last.  The order is total and a
+ * score's bits depend on its two rows, their two moment pairs and dim alone, so the result is the same bytes for any split
+ * into spans, chunks, k, batch or run.
+ *
+ * d_query_moments   : [n_query][2] float64 {mean, std} of the query rows (the T-norm side: svk_score_norm's row table), or NULL
+ * d_gallery_moments : [n_gallery][2] float64 {mean, std} of THIS call's gallery rows (the Z-norm side: the column table), or
+ *                     NULL.  Row j of the table belongs to row j of d_gallery, whatever index_base is
+ * Both as svk_cohort_moments writes them; 8-byte aligned; read only in their [n][2] extent.  Both NULL is SVK_ERR_BAD_ARG:
+ * svk_cosine_topk exists for that.  A table is GIVEN by its pointer: the table of an empty side (n_query or n_gallery of 0,
+ * a chunk without rows) is never read, but only a non-NULL pointer says that it is there.
+ * flags & 1 (accumulate): the lists already in the outputs are NORMALISED scores of earlier calls (other chunks of the
+ *                     gallery under the same query table).  d_exclude and index_base are global, as in svk_cosine_topk.
+ * Every other argument, the empty-query and empty-gallery cases, the refusals and the workspace rule are svk_cosine_topk's.
+ * svk_cosine_topk_norm_workspace_bytes gives the workspace size (host arithmetic only; 0 for arguments the entry refuses).
+ * Asynchronous on the context's stream.
+ */
+size_t svk_cosine_topk_norm_workspace_bytes(int32_t n_query, int32_t n_gallery, int32_t dim, int32_t k);
+int svk_cosine_topk_norm(svk_ctx* ctx, const float* d_query, int32_t n_query, const float* d_gallery, int32_t n_gallery,
+                         int32_t dim, int32_t k, int64_t index_base, const int64_t* d_exclude, int32_t flags,
+                         const double* d_query_moments, const double* d_gallery_moments, void* d_workspace,
+                         size_t workspace_bytes, float* d_top_score, int64_t* d_top_index);
+
 /* ---- speaker diarization (csrc/cluster.hip) ---------------------------------------------------
  * "Who spoke when" in recordings with several speakers: sliding windows over a recording's feature rows, one embedding per
  * window (svk_c3d2_stage1_multi with K = max_windows), the cosine of every pair of windows of a recording, and agglomerative
@@ -653,6 +745,52 @@ int svk_spectral_embed(svk_ctx* ctx, const float* d_aff, int32_t n_rec, int32_t 
                        size_t workspace_bytes, float* d_embed, int32_t* d_n_nodes, int32_t* d_n_speakers, int32_t* d_neighbours,
                        double* d_eigval, double* d_eigvec, uint8_t* d_graph, double* d_ratio, int32_t* d_bad_count);
 
+/* ---- shared-neighbour (Jarvis-Patrick) clustering of k-NN lists -------------------
+ * svk_knn_cluster labels the n rows of a corpus by the connected components of a graph whose edges are read off the rows'
+ * k-nearest-neighbour lists, as svk_cosine_topk writes them for a self-search (d_exclude = the row itself).  No [n x n]
+ * matrix and no host round trip; every output is defined in integers, so it is a function of the inputs alone and the same
+ * bytes on every run.  tests/knn_cluster_ref.py restates the rule below in plain Python.
+ *
+ * Input.  d_nbr_index int64 [n][list_stride], d_nbr_score f32 [n][list_stride], best first.  Only the first k slots of a row
+ * are read, 1 <= k <= 32, k <= list_stride: k < list_stride gives what a search with that smaller k gives.
+ *
+ * Slots.  A slot of row i is EMPTY if its index is -1.  It is BAD if its index is < -1 or >= n, equals i, or repeats the
+ * index of an earlier slot of the same row.  A bad slot is counted once in n_bad, treated as empty and never followed: no
+ * index is dereferenced before it is known to lie in [0, n).  N(i) is the set of indices in row i's valid (neither empty nor
+ * bad) slots, whatever their scores.
+ *
+ * Arcs.  The arc i -> j holds iff j is in N(i) and that slot's score s satisfies  s >= threshold  as an IEEE float32
+ * comparison: a NaN score fails, -0 >= +0 holds.  threshold = -inf switches the test off: every valid slot is an arc, a NaN
+ * score included.  A NaN threshold is SVK_ERR_BAD_ARG.
+ *
+ * Edges.  flags & 1 ("mutual"): {i, j} is an edge iff i -> j AND j -> i, each arc by its own list's score (the two scores of
+ * a pair need not be the same bits).  Bit 0 clear: iff i -> j OR j -> i.  In both modes  |N(i) & N(j)| >= min_shared  is
+ * required as well; min_shared in [0, 32], 0 disables the test.  Every other bit of flags must be 0.
+ *
+ * Outputs, all int32 on the device.
+ * d_root   : [n]  the smallest row index of row i's connected component
+ * d_labels : [n]  components of at least min_size rows (min_size >= 1) are numbered 0 .. C-1 in increasing order of their
+ *                 smallest member; d_labels[i] is that number, -1 for the rows of smaller components
+ * d_sizes  : [n]  the sizes of clusters 0 .. C-1, then zeros
+ * d_counts : [4]  {C, rows labelled -1, n_bad, gave_up}.  gave_up is 0 unless a bounded loop of the union-find ran out (a
+ *                 find is given n steps, a hook n retries; neither is reached); when it is 1 the other outputs are undefined
+ * n <= 2^31 - 1.  n == 0 launches nothing and writes d_counts = 0; the other buffers are then not touched and may be NULL.
+ *
+ * d_workspace: at least svk_knn_cluster_workspace_bytes(n, k) bytes, 16-byte aligned (NULL allowed where that is 0); the size
+ * depends on the shape alone and is 0 for arguments the entry refuses (host arithmetic only).  d_nbr_index 8-byte aligned,
+ * every other buffer 4-byte aligned.
+ * SVK_ERR_BAD_ARG: NULL context or buffer, negative n or n above 2^31 - 1, k outside [1, 32], list_stride < k, min_shared
+ * outside [0, 32], min_size < 1, NaN threshold, undefined flag bits, misalignment, short workspace.
+ * Asynchronous on the context's stream.
+ */
+#define SVK_KNN_CLUSTER_MUTUAL 1
+
+size_t svk_knn_cluster_workspace_bytes(int64_t n, int32_t k);
+int svk_knn_cluster(svk_ctx* ctx, const float* d_nbr_score, const int64_t* d_nbr_index, int64_t n, int32_t k,
+                    int64_t list_stride, float threshold, int32_t min_shared, int32_t min_size, int32_t flags,
+                    void* d_workspace, size_t workspace_bytes, int32_t* d_labels, int32_t* d_root, int32_t* d_sizes,
+                    int32_t* d_counts);
+
 /* ---- ROC / EER / AUC on the device ------------------------------------------------------------
  * evaluation.py:47-52 (sklearn roc_curve + roc_auc_score + brentq on interp1d) for pair sets too
  * large for the host: LSD radix sort of the scores (descending, 8-bit digits, the label riding along;
@@ -710,6 +848,91 @@ int svk_decision_counts(svk_ctx* ctx, const float* d_scores, const uint8_t* d_la
  * rows of d_true (all zeros for -1).  *h_correct (HOST) = rows with argmax == d_true.  Synchronises the stream. */
 int svk_top1(svk_ctx* ctx, const float* d_scores, int64_t n_rows, int32_t n_cols, const int32_t* d_true,
              int32_t* d_argmax, uint8_t* d_labels, int64_t* h_correct);
+
+/* ---- the ROC convex hull ---------------------------------------------------------
+ * minCllr, the ROCCH-EER and the PAV (isotonic) calibration of a trial set are one object: the upper convex hull of its ROC.
+ * PAV's bins are the hull's edges, its posteriors their slopes, minCllr a sum over the edges.
+ *
+ * The points.  With the n trials sorted by descending score (-0.0 equals +0.0) and every group of equal scores pooled,
+ *     Q_0 = (0, 0),   Q_j = (fps_j, tps_j), j = 1 .. M: non-targets / targets with a score at or above the j-th distinct score,
+ *     Q_M = (N, P).
+ * These are svk_roc_dcf's points (its "points" output is M).  Along the sequence f never decreases and t rises where f stands
+ * still: it is lexicographically sorted.
+ *
+ * The hull.  cross(a, b, c) = (b.f - a.f) (c.t - a.t) - (b.t - a.t) (c.f - a.f).  The hull is the subsequence
+ * V_0 = Q_0, ..., V_K = Q_M in which every interior vertex makes a STRICT right turn, cross(V_k-1, V_k, V_k+1) < 0; collinear
+ * points are not vertices.  It is what Andrew's monotone chain leaves when it pops while cross >= 0.  n < 2^32 gives
+ * N P < 2^62: every cross product is exact in int64, and no floating point takes part in deciding a vertex.  The result is a
+ * function of the multiset of (score, label) pairs alone: the stored order of the trials changes nothing, nor does a rerun.
+ *
+ * Per edge k (V_k-1 -> V_k), dt_k targets and df_k non-targets lie in it:
+ *     PAV posterior  dt_k / (dt_k + df_k)
+ *     llr_k        = log(dt_k / df_k) - log(P / N)          (+inf for df_k = 0, -inf for dt_k = 0)
+ *     e_k          = the score of V_k: the lowest score of the bin, a value of the input
+ *     minCllr      = [ (1/P) sum_k dt_k log1p(df_k P / (dt_k N)) + (1/N) sum_k df_k log1p(dt_k N / (df_k P)) ] / (2 ln 2),
+ *                    an edge with dt_k = 0 or df_k = 0 contributing 0
+ *     ROCCH-EER    : svk_roc_eer's rule on the hull's vertices: on the one edge with g_0 = 1 - f_0/N - t_0/P > 0 >= g_1,
+ *                    eer = x_0 + (x_1 - x_0) g_0 / (g_0 - g_1),  x = f / N
+ * The library returns the integer vertices and their scores; the derived values are a few float64 operations per edge on the
+ * host (speaker_verification_amd/calibration.py).
+ *
+ * svk_rocch is svk_roc_dcf plus the hull: the same kernels in the same order produce h_out[0 .. 5 + 4 n_op), bit for bit what
+ * svk_roc_dcf writes there for the same arguments (see above), and behind svk_roc_dcf's last kernel the hull passes run:
+ *   tile pass     one workgroup per 2 048 consecutive points (the origin included), staged in LDS as (f, t) pairs; each thread
+ *                 runs the monotone chain over its 8 points, then 8 levels in LDS merge adjacent hulls pairwise
+ *   merge levels  ceil(log2(tiles)) kernels, one workgroup per pair of adjacent hulls A, B: the bridge (u, v) -- for a
+ *                 candidate u, v(u) is the first i with cross(A[u], B[i], B[i+1]) < 0 (or B's last index), by binary search;
+ *                 u is the bridge's left end iff (u == 0 or cross(A[u-1], A[u], B[v]) < 0) and (u == last or
+ *                 cross(A[u], A[u+1], B[v]) >= 0); exactly one u qualifies -- and the copy A[0..u] ++ B[v..].  A hull
+ *                 stays anchored at the offset of its first point's tile, so no level needs a scan of the counts.
+ * Integers only; no atomic, no workgroup waits on another; the number of levels depends on M alone.
+ *
+ * n, d_scores, d_labels, h_ops, n_op : as for svk_roc_dcf
+ * d_workspace  : svk_rocch_workspace_bytes(n) bytes (more than svk_roc_dcf's: two hull buffers of 8 bytes per point)
+ * d_vf, d_vt   : [capacity] uint32: fps and tps of the K + 1 vertices, the origin first; elements from K + 1 on are untouched
+ * d_vscore     : [capacity] float: the score at each vertex (the threshold "accept when score >= it" that reaches the vertex),
+ *                bit for bit a score of the input with -0.0 read as +0.0; the origin gets +inf
+ * capacity     : elements of each plane.  svk_rocch_max_vertices(n) always suffices
+ * h_out        : [5 + 4 n_op + 1] doubles: svk_roc_dcf's values, then the vertex count K + 1
+ *
+ * Refusals: everything svk_roc_dcf refuses, in the same words (n < 2, n >= 2^32, more than 8 or malformed operating points,
+ * NULL buffers, a non-finite score, a single class, a workspace smaller than svk_rocch_workspace_bytes(n)); NULL planes,
+ * capacity < 1; and a capacity below the vertex count: SVK_ERR_BAD_ARG with the count in the message, nothing written to
+ * the planes or to h_out.  Synchronous like svk_roc_dcf up to the last kernel, which writes the planes in stream order.
+ *
+ * Diagnostics.  After a call the workspace holds, from byte svk_rocch_level_counts_offset(n) on (host arithmetic only; 0 for
+ * n < 2), uint32 vertex counts: one per tile of the M + 1 points (ceil((M + 1) / 2048) of them), then one per hull of every
+ * merge level in turn (half as many each level, rounded up), the last being K + 1.  Their sums per level are the points that
+ * survive it (tools/time_rocch.py reports them).  This is for measurement only: where the counts lie is the library's to
+ * change between builds, which is why the offset is asked of the library and not derived by the caller.
+ *
+ * svk_rocch_max_vertices(n) (host arithmetic only, any int64 n; svk_rocch itself takes n < 2^32) is an integer bound on
+ * K + 1.  Edges have pairwise distinct slopes, so pairwise distinct vectors (df, dt); at most s + 1 vectors have df + dt = s; the edge vectors sum to (N, P), df + dt over
+ * them to n.  The most edges a budget of n buys takes every vector of weight 1, 2, ... in turn: all weights up to S cost
+ * T(S) = S (S + 1) (S + 2) / 3 and give C(S) = S (S + 3) / 2 edges.  With S the smallest integer with T(S) >= n,
+ * K <= C(S) (~ 1.04 n^(2/3) + 2.2 n^(1/3)), and K <= n trivially: the bound is min(C(S), n) + 1; 0 for n < 1.  For n >= 2^32,
+ * which svk_rocch refuses, S is the one of 2^32 - 1.
+ */
+size_t svk_rocch_workspace_bytes(int64_t n);
+size_t svk_rocch_level_counts_offset(int64_t n);
+int64_t svk_rocch_max_vertices(int64_t n);
+int svk_rocch(svk_ctx* ctx, const float* d_scores, const uint8_t* d_labels, int64_t n, const double* h_ops, int32_t n_op,
+              void* d_workspace, size_t workspace_bytes, uint32_t* d_vf, uint32_t* d_vt, float* d_vscore, int64_t capacity,
+              double* h_out);
+
+/* ---- the PAV map -----------------------------------------------------------------
+ * d_out[p] = d_llr[k] for the smallest k with d_scores[p] >= d_edges[k], the last bin when the score is below every edge:
+ * a step function; a score in the gap between two bins goes to the lower bin.  A NaN score stays that NaN.
+ * d_edges : [n_bins] float, descending (the e_k above), no NaN; n_bins >= 1
+ * d_llr   : [n_bins] float, any values
+ * d_out   : [n] float; may be d_scores itself (in place; no other overlap)
+ * One binary search per score.  The table sits in LDS for n_bins <= 4096 (32 KiB) and is read from global memory above that.
+ * 16-byte loads and stores where d_scores and d_out are equally placed within 16 bytes (an aligned body between a scalar head
+ * and tail), scalar ones otherwise; both pointers 4-byte aligned.  Asynchronous on the context's stream.  n == 0 launches
+ * nothing.  Refusals: n < 0, n_bins < 1, NULL d_edges / d_llr, NULL d_scores / d_out with n > 0, a misaligned pointer.
+ */
+int svk_pav_apply(svk_ctx* ctx, const float* d_scores, int64_t n, const float* d_edges, const float* d_llr, int32_t n_bins,
+                  float* d_out);
 
 /* ---- score calibration and fusion (csrc/calibration.hip) ---------------------------------------
  * An affine map from the scores of n_sys systems to a calibrated log-likelihood ratio, llr = sum_d w_d s_d + b, fitted by
@@ -1036,6 +1259,32 @@ int svk_allgather_f32(svk_ctx* ctx, const float* d_send, float* d_recv, size_t c
 int svk_comm_destroy(svk_ctx* ctx);
 /* out[0] = ranks of the context's communicator (0 = none), out[1] = this rank */
 int svk_comm_info(const svk_ctx* ctx, int32_t out[2]);
+
+/* History -- one version or addition per line, newest first.  0.1.12 (SVK_VERSION 114) kept its number through every addition;
+ * the ten entries of the first four lines came under it too, declared at first in headers of their own, since folded in here.
+ * 0.1.12  + svk_knn_cluster, svk_knn_cluster_workspace_bytes (corpus clustering: shared-neighbour components of k-NN lists)
+ * 0.1.12  + svk_cosine_topk_norm, svk_cosine_topk_norm_workspace_bytes (the speaker search ranked by normalised scores)
+ * 0.1.12  + svk_rocch, svk_rocch_workspace_bytes, svk_rocch_level_counts_offset, svk_rocch_max_vertices, svk_pav_apply (the ROC convex hull: minCllr, ROCCH-EER, PAV)
+ * 0.1.12  + svk_vad_adaptive (the level-adaptive VAD: per-clip thresholds from two quantiles of the frame energies)
+ * 0.1.12  + svk_spectral_embed, svk_spectral_limits, svk_spectral_workspace_bytes (spectral clustering for diarization: batched Jacobi eigendecompositions of graph Laplacians, the speaker count from the eigengap, the neighbour count by the normalised maximum eigengap)
+ * 0.1.12  + svk_window_crops, svk_segment_affinity, svk_ahc, svk_ahc_limits, svk_ahc_workspace_bytes (speaker diarization: sliding-window crop tables, the window-against-window cosines of every recording and average-linkage clustering, one workgroup per recording)
+ * 0.1.12  + svk_cohort_moments, svk_score_norm, svk_score_norm_pairs (adaptive score normalisation: the top-K cohort moments of every row by an exact radix select, and Z- / T- / S-norm from them)
+ * 0.1.12  + svk_calibration_stats, svk_calibration_stats_workspace_bytes, svk_calibration_apply (score calibration and fusion: the statistics of a prior-weighted logistic regression in one pass, and the affine map)
+ * 0.1.12  + svk_plda_scores, svk_plda_scores_workspace_bytes, svk_plda_pair_scores (PLDA log-likelihood ratios: the score matrix on the f32 matrix pipe, trial lists in float64)
+ * 0.1.12  svk_c3d2_stage2 runs as one kernel and no longer touches d_act2, which may be NULL (same results, bit for bit)
+ * 0.1.12  + svk_class_scatter, svk_class_scatter_workspace_bytes, svk_embedding_project (the embedding back end: class statistics in float64 and centre / project / length-normalise in one pass)
+ * 0.1.12  + svk_cosine_topk, svk_cosine_topk_workspace_bytes (the k best gallery rows of every query without the score matrix; chunked galleries through an accumulate flag)
+ * 0.1.12  + svk_pair_scores (one score per trial of a list), svk_roc_dcf, svk_roc_dcf_workspace_bytes (minDCF and the EER / minDCF thresholds on the ROC sort), svk_decision_counts (accepts at given thresholds); the AUC of svk_roc_eer / svk_roc_k is summed in a fixed order (same bits on every run)
+ * 0.1.12  + svk_c3d2_stage1_multi, svk_c3d2_stage1_c3_multi (K cubes per clip), svk_embedding_pool (the mean over groups of embedding rows)
+ * 0.1.12  + svk_delta_cmvn_stats, svk_delta_planes, svk_cube_gather_delta (the three-channel input from static features in one statistics pass and one writing pass)
+ * 0.1.12  + svk_c3d2_head (PReLU5 -> FC6 -> softmax, top-k and hits: the classification head); tests/test_identification.py pins the number
+ * 0.1.11  + svk_roc_k, svk_roc_k_workspace_bytes (k-fold splits, roc_curve in counts), svk_top1; the ROC sort and scans are the library's own kernels (no hipCUB)
+ * 0.1.10  + svk_c3d2_stage1_c3 (the three-channel first block, DERIVATIVE = True)
+ * 0.1.9   conv1_2's last tap as ONE [h | l] fragment (d_w2blk pair 13 = [H | H], [L | 0]: 41 MFMAs per tile, not 42), conv2_1 leaves out the column pool2 makes dead (d_act2 [..][14][32]); half-pair domain stated
+ * 0.1.8   svk_c3d2_stage1 / svk_c3d2_stage2 / svk_c3d2_conv31 / svk_c3d2_conv32t run on the f16 matrix pipe through two-piece products (new weight tables: half-pair blocks)
+ * 0.1.7   gathered front-end input (svk_vad_energy d_src_frame -> svk_frontend_run d_src_chunk)
+ * 0.1.6   one kernel per network layer (svk_c3d2_conv32, svk_bias_prelu, svk_cube_gather_windows and the direct-form flag bits are gone); + svk_cmvn_stats, svk_cube_gather_cmvn
+ */
 
 #ifdef __cplusplus
 }

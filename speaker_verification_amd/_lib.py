@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsvk.so")
 
 SVK_OK = 0
-VERSION = 114                      # include/svk.h SVK_VERSION (0.1.12: + svk_rocch, svk_rocch_workspace_bytes, svk_rocch_level_counts_offset, svk_rocch_max_vertices, svk_pav_apply in include/svk_rocch.h, number unchanged; + svk_vad_adaptive in include/svk_vad.h, number unchanged; + svk_spectral_embed, svk_spectral_limits, svk_spectral_workspace_bytes, number unchanged; + svk_window_crops, svk_segment_affinity, svk_ahc, number unchanged; + svk_cohort_moments, svk_score_norm, svk_score_norm_pairs, number unchanged; + svk_calibration_stats, svk_calibration_apply, number unchanged; + svk_plda_scores, svk_plda_pair_scores, number unchanged; + svk_class_scatter, svk_embedding_project, number unchanged; + svk_cosine_topk, number unchanged; + svk_pair_scores, svk_roc_dcf, svk_decision_counts, number unchanged; + svk_c3d2_head; + the svk_delta_* entries, the *_multi first block and svk_embedding_pool, number unchanged)
+VERSION = 114                      # include/svk.h SVK_VERSION (0.1.12; the header's History block says what each version added)
 SVK_ERR_BAD_ARG, SVK_ERR_UNSUPPORTED, SVK_ERR_HIP, SVK_ERR_NO_DEVICE, SVK_ERR_OOM, SVK_ERR_RCCL = -1, -2, -3, -4, -5, -6
 OUT_MFE, OUT_LMFE, OUT_MFCC = 0, 1, 2
 PCM_I16, PCM_F32 = 0, 1
@@ -38,8 +38,8 @@ class FrontendCfg(C.Structure):
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
-# name -> (restype, argtypes).  Must list every symbol include/svk.h declares
-# (tests/test_cabi.py checks the two against each other).
+# name -> (restype, argtypes), in the header's order.  Must list every symbol include/svk.h declares
+# (tests/test_cabi.py checks the two against each other and against the built library).
 SIGNATURES = {
     "svk_version": (C.c_int, []),
     "svk_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
@@ -69,39 +69,30 @@ SIGNATURES = {
     "svk_log_power": (C.c_int, [_vp, _vp, _i64, _i32]),
     "svk_vad_energy": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i64, _i32,
                                   _vp, _vp, _vp, _vp, _vp, _vp]),
-    "svk_cube_draw_crops": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _i32, _i32, C.c_uint64, _vp, _vp]),
+    "svk_vad_adaptive": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "svk_cube_gather": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "svk_cube_gather_cmvn": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
     "svk_delta_cmvn_stats": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "svk_delta_planes": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
     "svk_cube_gather_delta": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "svk_cube_draw_crops": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _i32, _i32, C.c_uint64, _vp, _vp]),
+    "svk_ingest_resample": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _i32,
+                                      _i64, _i32, _vp]),
     "svk_cosine_scores": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "svk_roc_workspace_bytes": (C.c_size_t, [_i64]),
-    "svk_roc_eer": (C.c_int, [_vp, _vp, _vp, _i64, _vp, C.c_size_t, C.POINTER(C.c_double)]),
-    "svk_roc_k_workspace_bytes": (C.c_size_t, [_i64, _i32]),
-    "svk_roc_k": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, C.c_size_t, _vp, C.POINTER(C.c_double)]),
-    "svk_roc_dcf_workspace_bytes": (C.c_size_t, [_i64]),
-    "svk_roc_dcf": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(C.c_double), _i32, _vp, C.c_size_t, C.POINTER(C.c_double)]),
-    "svk_decision_counts": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(_f32), _i32, C.POINTER(_i64)]),
-    "svk_calibration_stats_workspace_bytes": (C.c_size_t, [_i64, _i32]),
-    "svk_calibration_stats": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _i64, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double),
-                                        _i32, _vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(_i64)]),
-    "svk_calibration_apply": (C.c_int, [_vp, _vp, _i32, _i64, _i64, C.POINTER(C.c_double), _vp]),
-    "svk_cohort_moments": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp]),
-    "svk_score_norm": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64]),
-    "svk_score_norm_pairs": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
-    "svk_top1": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, C.POINTER(_i64)]),
     "svk_l2_dist": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
-    "svk_pair_scores": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _vp]),
-    "svk_plda_scores_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32]),
-    "svk_plda_scores": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, C.c_size_t, _vp]),
-    "svk_plda_pair_scores": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "svk_embedding_pool": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _i32, _vp, _vp]),
     "svk_class_scatter_workspace_bytes": (C.c_size_t, [_i64, _i32, _i64]),
     "svk_class_scatter": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, C.c_size_t, _vp, _vp]),
     "svk_embedding_project": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp]),
+    "svk_pair_scores": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "svk_plda_scores_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32]),
+    "svk_plda_scores": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "svk_plda_pair_scores": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "svk_cosine_topk_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32]),
     "svk_cosine_topk": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i64, _vp, _i32, _vp, C.c_size_t, _vp, _vp]),
+    "svk_cosine_topk_norm_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32]),
+    "svk_cosine_topk_norm": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "svk_window_crops": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "svk_segment_affinity": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "svk_ahc_limits": (C.c_int, [C.POINTER(_i32)]),
@@ -111,6 +102,29 @@ SIGNATURES = {
     "svk_spectral_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32]),
     "svk_spectral_embed": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, C.c_size_t, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "svk_knn_cluster_workspace_bytes": (C.c_size_t, [_i64, _i32]),
+    "svk_knn_cluster": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _f32, _i32, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "svk_roc_workspace_bytes": (C.c_size_t, [_i64]),
+    "svk_roc_eer": (C.c_int, [_vp, _vp, _vp, _i64, _vp, C.c_size_t, C.POINTER(C.c_double)]),
+    "svk_roc_k_workspace_bytes": (C.c_size_t, [_i64, _i32]),
+    "svk_roc_k": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, C.c_size_t, _vp, C.POINTER(C.c_double)]),
+    "svk_roc_dcf_workspace_bytes": (C.c_size_t, [_i64]),
+    "svk_roc_dcf": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(C.c_double), _i32, _vp, C.c_size_t, C.POINTER(C.c_double)]),
+    "svk_decision_counts": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(_f32), _i32, C.POINTER(_i64)]),
+    "svk_top1": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "svk_rocch_workspace_bytes": (C.c_size_t, [_i64]),
+    "svk_rocch_level_counts_offset": (C.c_size_t, [_i64]),
+    "svk_rocch_max_vertices": (_i64, [_i64]),
+    "svk_rocch": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(C.c_double), _i32, _vp, C.c_size_t, _vp, _vp, _vp, _i64,
+                            C.POINTER(C.c_double)]),
+    "svk_pav_apply": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "svk_calibration_stats_workspace_bytes": (C.c_size_t, [_i64, _i32]),
+    "svk_calibration_stats": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _i64, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double),
+                                        _i32, _vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(_i64)]),
+    "svk_calibration_apply": (C.c_int, [_vp, _vp, _i32, _i64, _i64, C.POINTER(C.c_double), _vp]),
+    "svk_cohort_moments": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp]),
+    "svk_score_norm": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64]),
+    "svk_score_norm_pairs": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "svk_c3d2_stage1_lds_bytes": (C.c_size_t, []),
     "svk_c3d2_stage1": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "svk_c3d2_stage1_c3_lds_bytes": (C.c_size_t, []),
@@ -130,42 +144,9 @@ SIGNATURES = {
     "svk_allgather_f32": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
     "svk_comm_destroy": (C.c_int, [_vp]),
     "svk_comm_info": (C.c_int, [_vp, C.POINTER(_i32)]),
-    "svk_ingest_resample": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _i32,
-                                      _i64, _i32, _vp]),
 }
 
-# Entries declared in further headers (include/svk_vad.h): load() binds them after SIGNATURES.  tests/test_vad_adaptive_host.py
-# checks this table against that header and the built library, as tests/test_cabi.py does for SIGNATURES and svk.h.
-EXT_SIGNATURES = {
-    "svk_vad_adaptive": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32,
-                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-}
-
-# Entries of include/svk_rocch.h (the ROC convex hull and the PAV map): load() binds them after the other two tables;
-# tests/test_rocch_host.py checks this table against that header and the built library.
-ROCCH_SIGNATURES = {
-    "svk_rocch_workspace_bytes": (C.c_size_t, [_i64]),
-    "svk_rocch_level_counts_offset": (C.c_size_t, [_i64]),
-    "svk_rocch_max_vertices": (_i64, [_i64]),
-    "svk_rocch": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(C.c_double), _i32, _vp, C.c_size_t, _vp, _vp, _vp, _i64,
-                            C.POINTER(C.c_double)]),
-    "svk_pav_apply": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _vp]),
-}
-
-# Entries of include/svk_search_norm.h (the speaker search ranked by normalised scores): load() binds them last;
-# tests/test_search_norm_host.py checks this table against that header and the built library.
-SEARCH_NORM_SIGNATURES = {
-    "svk_cosine_topk_norm_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32]),
-    "svk_cosine_topk_norm": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
-}
-
-# Entries of include/svk_cluster.h (corpus clustering from k-NN lists): load() binds them after the other tables;
-# tests/test_knn_cluster_host.py checks this table against that header and the built library.
 KNN_CLUSTER_MUTUAL = 1             # svk_knn_cluster's flag bit 0 (SVK_KNN_CLUSTER_MUTUAL)
-CLUSTER_SIGNATURES = {
-    "svk_knn_cluster_workspace_bytes": (C.c_size_t, [_i64, _i32]),
-    "svk_knn_cluster": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _f32, _i32, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
-}
 
 _lib = None
 
@@ -185,8 +166,7 @@ def load():
         except ImportError:
             pass
         lib = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(ROCCH_SIGNATURES.items()) \
-                + list(SEARCH_NORM_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()):
+        for name, (restype, argtypes) in SIGNATURES.items():
             fn = getattr(lib, name)            # AttributeError if the .so is stale
             fn.restype = restype
             fn.argtypes = argtypes
@@ -207,15 +187,17 @@ def check(rc, ctx=None):
 
 
 def provenance():
-    """What a measurement was made with: {"csrc_sha": sha256 over the kernel sources (csrc/*.hip, csrc/*.h, csrc/Makefile,
-    include/svk.h, include/svk_vad.h, include/svk_rocch.h, include/svk_search_norm.h, include/svk_cluster.h: file names + bytes, sorted), "libsvk_sha": sha256 of the built library}, 16 hex digits each.  Profiles
+    """What a measurement was made with: {"csrc_sha": sha256 over the kernel sources (csrc/*.hip, csrc/*.h, csrc/Makefile and
+    every *.h a listing of include/ returns: file names + bytes, each directory sorted), "libsvk_sha": sha256 of the built
+    library}, 16 hex digits each.  Profiles
     under profiles/ carry it (tools/summarize_prof.py) and bench.py marks a roofline row `stale` when the counters it uses
     were collected from other kernel sources than the ones it runs."""
     import hashlib
     here = os.path.dirname(os.path.abspath(__file__))
     csrc = os.path.join(here, "csrc")
     files = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h")) or f == "Makefile")
-    files += [os.path.join(os.path.dirname(here), "include", name) for name in ("svk.h", "svk_vad.h", "svk_rocch.h", "svk_search_norm.h", "svk_cluster.h")]
+    include = os.path.join(os.path.dirname(here), "include")
+    files += sorted(os.path.join(include, f) for f in os.listdir(include) if f.endswith(".h"))
     h = hashlib.sha256()
     for path in files:
         h.update(os.path.basename(path).encode())

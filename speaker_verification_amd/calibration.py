@@ -214,7 +214,7 @@ class Calibration:
 # ---- the ROC convex hull: minCllr, ROCCH-EER, PAV --------------------------------------------------------------------------
 # How good a calibration COULD have been: minCllr is the Cllr of the best monotone map of the scores, which is PAV (isotonic
 # regression of the labels on the scores); cllr - min_cllr is the calibration loss.  PAV's bins are the edges of the upper
-# convex hull of the ROC and its posteriors their slopes; `Engine.rocch` (svk_rocch, include/svk_rocch.h has the definitions)
+# convex hull of the ROC and its posteriors their slopes; `Engine.rocch` (svk_rocch; include/svk.h, "the ROC convex hull", has the definitions)
 # returns the hull's integer vertices from the device sort.  Everything below is host arithmetic on those K + 1 vertices.
 def hull_chain(points):
     """Andrew's monotone chain over lexicographically sorted integer points (f, t), popping while cross >= 0: the indices of

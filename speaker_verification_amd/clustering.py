@@ -1,7 +1,7 @@
 """Corpus clustering: unlabelled embeddings -> pseudo-speaker labels, on the device.
 
 `cluster_embeddings` is a self-search (`svk_cosine_topk`, no [n x n] matrix) followed by `svk_knn_cluster`
-(include/svk_cluster.h): the connected components of the shared-neighbour (Jarvis-Patrick) graph read off the k-NN lists.
+(include/svk.h, "shared-neighbour (Jarvis-Patrick) clustering of k-NN lists"): the connected components of the shared-neighbour (Jarvis-Patrick) graph read off the k-NN lists.
 `segments` turns the labels into the CSR form `svk_embedding_pool` and `svk_class_scatter` take, so the clusters feed
 `centroids`, `backend.solve` and `plda.solve_plda` like speaker labels.  `purity` and `pair_precision_recall_f` measure a
 clustering against known labels on the host.  Nothing is tuned in here: k and the threshold are the caller's."""

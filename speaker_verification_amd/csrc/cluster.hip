@@ -18,8 +18,7 @@
 //                       compares the new W[m][i] with what it holds (average linkage is reducible: the new value cannot beat the
 //                       row's best by more than rounding, and where it does or ties at a lower index the comparison takes it).
 //                       The update is two products, a sum and a quotient, each rounded once (no contraction in this file).
-// svk_knn_cluster       (include/svk_cluster.h; kernels and their notes in knn_cluster.h) corpus clustering: the connected
-//                       components of the shared-neighbour graph read off k-NN lists.  Integers only; the entry is at the end.
+// (Corpus clustering, svk_knn_cluster, is a file of its own: knn_cluster.hip.)
 #include "svk_internal.h"
 
 #pragma clang fp contract(off)
@@ -340,8 +339,6 @@ size_t ahc_lds_bytes(int stride) {
   return stride > AHC_LDS_N ? std::max(lds_inst, ahc_vec_bytes(ahc_even(stride))) : lds_inst;
 }
 
-inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 }  // namespace
 
 extern "C" {
@@ -426,45 +423,6 @@ int svk_ahc(svk_ctx* ctx, const float* d_aff, int32_t n_rec, int32_t seg_stride,
   hipLaunchKernelGGL(ahc_kernel, dim3((unsigned)n_rec), dim3(AHC_THREADS), lds, ctx->stream, p);
   SVK_LAUNCH_CHECK(ctx);
   return SVK_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------ svk_knn_cluster
-#include "../../include/svk_cluster.h"
-#include "knn_cluster.h"
-
-extern "C" {
-
-size_t svk_knn_cluster_workspace_bytes(int64_t n, int32_t k) {
-  if (n <= 0 || n > INT32_MAX || k < 1 || k > 32) return 0;
-  return knn_layout((size_t)n).total;
-}
-
-int svk_knn_cluster(svk_ctx* ctx, const float* d_nbr_score, const int64_t* d_nbr_index, int64_t n, int32_t k, int64_t list_stride,
-                    float threshold, int32_t min_shared, int32_t min_size, int32_t flags, void* d_workspace, size_t workspace_bytes,
-                    int32_t* d_labels, int32_t* d_root, int32_t* d_sizes, int32_t* d_counts) {
-  if (!ctx) return SVK_ERR_BAD_ARG;
-  SVK_REQUIRE(ctx, n >= 0, "negative shape");
-  SVK_REQUIRE(ctx, n <= INT32_MAX, "n above 2^31 - 1 (labels are int32)");
-  SVK_REQUIRE(ctx, k >= 1 && k <= 32, "k outside [1, 32]");
-  SVK_REQUIRE(ctx, list_stride >= k, "list_stride below k");
-  SVK_REQUIRE(ctx, min_shared >= 0 && min_shared <= 32, "min_shared outside [0, 32]");
-  SVK_REQUIRE(ctx, min_size >= 1, "min_size below 1");
-  SVK_REQUIRE(ctx, threshold == threshold, "threshold is NaN");
-  SVK_REQUIRE(ctx, (flags & ~SVK_KNN_CLUSTER_MUTUAL) == 0, "undefined flag bits");
-  SVK_REQUIRE(ctx, d_counts && (n == 0 || (d_nbr_score && d_nbr_index && d_labels && d_root && d_sizes)), "NULL buffer");
-  SVK_REQUIRE(ctx, !misaligned(d_nbr_index, 8) && !misaligned(d_nbr_score, 4) && !misaligned(d_labels, 4) && !misaligned(d_root, 4) &&
-                       !misaligned(d_sizes, 4) && !misaligned(d_counts, 4), "misaligned buffer (int32 / f32: 4 bytes, int64: 8)");
-  if (n == 0) {
-    SVK_HIP(ctx, hipMemsetAsync(d_counts, 0, 4 * sizeof(int32_t), ctx->stream));
-    return SVK_OK;
-  }
-  SVK_REQUIRE(ctx, d_workspace && workspace_bytes >= svk_knn_cluster_workspace_bytes(n, k),
-              "workspace below svk_knn_cluster_workspace_bytes");
-  SVK_REQUIRE(ctx, !misaligned(d_workspace, 16), "workspace must be 16-byte aligned");
-  return knn_cluster_launch(ctx, d_nbr_score, d_nbr_index, n, k, list_stride, threshold, min_shared, min_size,
-                            flags & SVK_KNN_CLUSTER_MUTUAL, d_workspace, d_labels, d_root, d_sizes, d_counts);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
-// Corpus clustering from k-NN lists (the rule: include/svk_cluster.h).  Included by cluster.hip, which holds the
-// entry svk_knn_cluster; everything here is int32 / uint32 arithmetic except one float32 comparison per slot.
+// Corpus clustering from k-NN lists: svk_knn_cluster (the rule: include/svk.h, "shared-neighbour (Jarvis-Patrick)
+// clustering of k-NN lists").  The kernels, the workspace layout, the launch sequence and, at the end, the two entries;
+// everything here is int32 / uint32 arithmetic except one float32 comparison per slot.
 //
 // knn_edge_kernel    TWO rows per wave, one on each 32-lane half (k <= 32: a row's slots fit a half, and at k = 32 no lane
 //                    idles).  Lane `slot` of a half holds slot `slot` of its row: it range-checks the index (a bad or empty slot
@@ -24,8 +25,6 @@
 //                    min_size): per-tile counts, one block's exclusive scan of the tile counts (the total is C), then every
 //                    flagged root writes its cluster's size to sizes[label] and keeps the label in its size slot.
 // knn_label_kernel   labels[i] = the label its root kept, the -1 rows counted (integer atomic), sizes[C ..] zeroed.
-#pragma once
-
 #include "svk_internal.h"
 
 namespace {
@@ -300,3 +299,38 @@ inline int knn_cluster_launch(svk_ctx* ctx, const float* d_score, const int64_t*
 }
 
 }  // namespace
+
+extern "C" {
+
+size_t svk_knn_cluster_workspace_bytes(int64_t n, int32_t k) {
+  if (n <= 0 || n > INT32_MAX || k < 1 || k > 32) return 0;
+  return knn_layout((size_t)n).total;
+}
+
+int svk_knn_cluster(svk_ctx* ctx, const float* d_nbr_score, const int64_t* d_nbr_index, int64_t n, int32_t k, int64_t list_stride,
+                    float threshold, int32_t min_shared, int32_t min_size, int32_t flags, void* d_workspace, size_t workspace_bytes,
+                    int32_t* d_labels, int32_t* d_root, int32_t* d_sizes, int32_t* d_counts) {
+  if (!ctx) return SVK_ERR_BAD_ARG;
+  SVK_REQUIRE(ctx, n >= 0, "negative shape");
+  SVK_REQUIRE(ctx, n <= INT32_MAX, "n above 2^31 - 1 (labels are int32)");
+  SVK_REQUIRE(ctx, k >= 1 && k <= 32, "k outside [1, 32]");
+  SVK_REQUIRE(ctx, list_stride >= k, "list_stride below k");
+  SVK_REQUIRE(ctx, min_shared >= 0 && min_shared <= 32, "min_shared outside [0, 32]");
+  SVK_REQUIRE(ctx, min_size >= 1, "min_size below 1");
+  SVK_REQUIRE(ctx, threshold == threshold, "threshold is NaN");
+  SVK_REQUIRE(ctx, (flags & ~SVK_KNN_CLUSTER_MUTUAL) == 0, "undefined flag bits");
+  SVK_REQUIRE(ctx, d_counts && (n == 0 || (d_nbr_score && d_nbr_index && d_labels && d_root && d_sizes)), "NULL buffer");
+  SVK_REQUIRE(ctx, !misaligned(d_nbr_index, 8) && !misaligned(d_nbr_score, 4) && !misaligned(d_labels, 4) && !misaligned(d_root, 4) &&
+                       !misaligned(d_sizes, 4) && !misaligned(d_counts, 4), "misaligned buffer (int32 / f32: 4 bytes, int64: 8)");
+  if (n == 0) {
+    SVK_HIP(ctx, hipMemsetAsync(d_counts, 0, 4 * sizeof(int32_t), ctx->stream));
+    return SVK_OK;
+  }
+  SVK_REQUIRE(ctx, d_workspace && workspace_bytes >= svk_knn_cluster_workspace_bytes(n, k),
+              "workspace below svk_knn_cluster_workspace_bytes");
+  SVK_REQUIRE(ctx, !misaligned(d_workspace, 16), "workspace must be 16-byte aligned");
+  return knn_cluster_launch(ctx, d_nbr_score, d_nbr_index, n, k, list_stride, threshold, min_shared, min_size,
+                            flags & SVK_KNN_CLUSTER_MUTUAL, d_workspace, d_labels, d_root, d_sizes, d_counts);
+}
+
+}  // extern "C"

@@ -25,7 +25,7 @@
 //   6. svk_roc_dcf only: dcf_part_kernel, one pass over the origin + the distinct-score points that leaves every workgroup's
 //      (cost, index) minimum per operating point in the workspace; roc_finish_kernel reduces them (no float64 atomics, no
 //      workgroup waits on another).  The first point among equal costs wins: the highest threshold.
-//   7. svk_rocch only (include/svk_rocch.h, kernels in rocch.h): behind roc_finish_kernel, the upper convex hull of the origin +
+//   7. svk_rocch only (include/svk.h "the ROC convex hull", kernels in rocch.h): behind roc_finish_kernel, the upper convex hull of the origin +
 //      the points, exact in int64: one hull per tile of 2 048 points (a monotone chain per thread, 8 merge levels in LDS), then
 //      ceil(log2(tiles)) levels that join adjacent hulls pairwise by their bridge; the vertices' scores come from the sorted keys.
 // svk_pav_apply (same header) maps scores through a step table by one binary search each.
@@ -33,7 +33,6 @@
 // Bit-level equality of eer / auc with sklearn is not expected (float64 accumulation order), |d| ~ 1e-15;
 // the curve counts are exact.  Element indices are u32 (n < 2^32), every address is 64-bit.
 #include "svk_internal.h"
-#include "../../include/svk_rocch.h"
 
 namespace {
 
@@ -693,7 +692,7 @@ RocLayout roc_layout(size_t m) {
   l.total = o;
   // two hull buffers of one (f, t) pair per point (the origin + at most m distinct scores), each hull anchored at its first
   // tile's offset; then every hull's vertex count, level after level: the tile pass's, then each merge level's (half as many
-  // each time, rounded up: below 2 tiles + 64 in all).  svk_rocch_level_counts_offset gives their offset (svk_rocch.h, Diagnostics).
+  // each time, rounded up: below 2 tiles + 64 in all).  svk_rocch_level_counts_offset gives their offset (svk.h, "the ROC convex hull", Diagnostics).
   const size_t tiles = (m + 1 + TILE - 1) / TILE;
   for (int b = 0; b < 2; ++b) {
     l.hull[b] = o;
@@ -1020,8 +1019,9 @@ size_t svk_rocch_level_counts_offset(int64_t n) { return n >= 2 ? roc_layout((si
 
 int64_t svk_rocch_max_vertices(int64_t n) {
   if (n < 1) return 0;
-  // S = the smallest integer with S (S + 1) (S + 2) / 3 >= m (include/svk_rocch.h).  m = n, held to the 2^32 - 1 trials svk_rocch
-  // takes (a larger n gets that bound's S: the K <= n term no longer binds there): S <= 2 345 and every product is below 2^34
+  // S = the smallest integer with S (S + 1) (S + 2) / 3 >= m (include/svk.h, at svk_rocch_max_vertices).  m = n, held to the
+  // 2^32 - 1 trials svk_rocch takes (a larger n gets that bound's S: the K <= n term no longer binds there): S <= 2 345 and
+  // every product is below 2^34
   const int64_t m = std::min<int64_t>(n, ((int64_t)1 << 32) - 1);
   int64_t s = 1;
   while (s * (s + 1) * (s + 2) / 3 < m) ++s;

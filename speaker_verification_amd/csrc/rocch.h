@@ -1,4 +1,4 @@
-// The ROC convex hull and the PAV map (include/svk_rocch.h): device code of roc.hip, included there inside its namespace
+// The ROC convex hull and the PAV map (include/svk.h, "the ROC convex hull"): device code of roc.hip, included there inside its namespace
 // (it uses RT, TILE, WAVES and key_value).  The hull of the origin + the distinct-score points (pf, pt) by divide and conquer:
 // hull_tile_kernel leaves one hull per tile of TILE points, hull_merge_kernel joins adjacent hulls pairwise, level by level.
 // A hull stays anchored at the offset of its first point's tile in a buffer of one (f, t) pair per point, its length beside it:

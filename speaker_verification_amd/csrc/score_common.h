@@ -30,7 +30,7 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// One normalised score, svk_score_norm's expression (svk.h "score normalisation"; svk_search_norm.h ranks by the same bits):
+// One normalised score, svk_score_norm's expression (svk.h "score normalisation"; svk_cosine_topk_norm ranks by the same bits):
 // float64 throughout, every operation rounded on its own, in the order written.  r: the row (test, T-norm) side's moments,
 // c: the column (enrolled, Z-norm) side's.  Nothing is clamped: a zero, negative or NaN sd gives what IEEE arithmetic gives.
 __device__ __forceinline__ float norm_value(float s, bool has_r, double mu_r, double sd_r, bool has_c, double mu_c, double sd_c) {

@@ -8,7 +8,6 @@
 
 #include "score_common.h"
 #include "svk_internal.h"
-#include "svk_search_norm.h"
 
 namespace {
 

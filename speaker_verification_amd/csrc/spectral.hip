@@ -433,8 +433,6 @@ __global__ __launch_bounds__(SP_THREADS) void spectral_embed_kernel(const SpPara
   if (tid == 0) p.n_nodes[rec] = m, p.n_speakers[rec] = k, p.neighbours[rec] = best_p;
 }
 
-inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 }  // namespace
 
 extern "C" {

@@ -78,6 +78,9 @@ inline int svk_ensure_work(svk_ctx* ctx, size_t bytes) {
     if (!(cond)) return svk_fail((ctx), SVK_ERR_BAD_ARG, "bad argument: %s", (msg));  \
   } while (0)
 
+// p does not lie on a multiple of a bytes (a: a power of two); NULL is aligned to everything
+inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
 // Every launch is followed by this: catches bad grids / missing code objects at once.
 #define SVK_LAUNCH_CHECK(ctx)                                                                  \
   do {                                                                                         \

@@ -11,13 +11,12 @@
 // Phase 3 (all waves): kept frames are copied to the front of the clip's output slot.
 // HBM-bound: 2 bytes read per sample (+2 written when compacting).
 //
-// svk_vad_adaptive (include/svk_vad.h) is the same framer, walk and compaction with a threshold derived per clip from two
+// svk_vad_adaptive (include/svk.h, "level-adaptive energy VAD") is the same framer, walk and compaction with a threshold derived per clip from two
 // order statistics of the clip's frame energies; its kernels are at the end of the namespace and share the ones above them.
 #include <cstdint>
 #include <cstdlib>
 
 #include "svk_internal.h"
-#include "../../include/svk_vad.h"
 
 namespace {
 
@@ -26,7 +25,7 @@ constexpr int VAD_THREADS = 256;
 
 typedef short i16x8 __attribute__((ext_vector_type(8)));
 
-// The level-adaptive rule's parameters and its two optional outputs, as the kernels carry them (svk_vad.h has the definition).
+// The level-adaptive rule's parameters and its two optional outputs, as the kernels carry them (svk.h has the definition).
 struct VadAdaptive {
   int floor_q16, peak_q16;
   long long above_floor_q16, below_peak_q16, min_threshold;

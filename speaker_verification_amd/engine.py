@@ -551,7 +551,7 @@ class Engine:
     def vad_adaptive(self, pcm, vad, fs=16000, frame_ms=30, padding_ms=300, lengths=None, compact=True,
                      want_segments=False, frame_samples=None, ring_len=None, offsets=None, voiced_out=None, longest=None,
                      want_energy=False):
-        """`vad_energy` under the level-adaptive rule (svk_vad_adaptive, include/svk_vad.h): `vad` is a `vad.AdaptiveEnergyVad`
+        """`vad_energy` under the level-adaptive rule (svk_vad_adaptive, include/svk.h "level-adaptive energy VAD"): `vad` is a `vad.AdaptiveEnergyVad`
         (anything with its five integer attributes floor_q16, peak_q16, above_floor_q16, below_peak_q16, min_threshold).  The
         same arguments and the same dict, plus levels [n, 3] i64 = (E_lo, E_hi, T) per clip and, with want_energy, energy
         [n, F] i64 (a clip's entries from its frame count on are unspecified)."""
@@ -839,7 +839,7 @@ class Engine:
         return res, (None if planes is None else int(out[5 + 4 * n_op]))
 
     def rocch(self, scores, labels, operating_points=()):
-        """svk_rocch (include/svk_rocch.h): roc_dcf's dict -- the same values, bit for bit -- plus the ROC convex hull from
+        """svk_rocch (include/svk.h, "the ROC convex hull"): roc_dcf's dict -- the same values, bit for bit -- plus the ROC convex hull from
         the same sort: vertices (int64 [K + 1, 2] on the host: fps, tps, the origin first, (N, P) last), vertex_scores (float32
         [K + 1]: the score at each vertex, +inf at the origin), and min_cllr and rocch_eer, computed from the integer vertices
         in float64 on the host (`calibration.min_cllr_of`, `calibration.rocch_eer_of`).  ONE library call, the planes sized by
@@ -1444,7 +1444,7 @@ class Engine:
         return scores, indices
 
     def knn_cluster(self, nbr_score, nbr_index, k=None, *, threshold, min_shared=0, mutual=True, min_size=1):
-        """svk_knn_cluster (include/svk_cluster.h): the connected components of the shared-neighbour graph read off the k-NN
+        """svk_knn_cluster (include/svk.h, "shared-neighbour (Jarvis-Patrick) clustering of k-NN lists"): the connected components of the shared-neighbour graph read off the k-NN
         lists of a self-search (`cosine_topk(x, x, k, exclude=arange(n))`: float32 / int64 [n, list_stride]) -> (labels int32
         [n], roots int32 [n], sizes int32 [n], counts int32 [4]) on the device.  Only the first k slots of a row count (None:
         all of them).  An edge {i, j} needs the arcs i -> j and j -> i (mutual; either one otherwise), an arc a slot with

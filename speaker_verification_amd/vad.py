@@ -103,7 +103,7 @@ def db_to_q16(db):
 
 
 class AdaptiveEnergyVad(object):
-    """The level-adaptive rule of svk_vad_adaptive (include/svk_vad.h): a frame is speech when its energy exceeds
+    """The level-adaptive rule of svk_vad_adaptive (include/svk.h, "level-adaptive energy VAD"): a frame is speech when its energy exceeds
     T = max(min(E_floor * above, E_peak * below), min_threshold * n), E_floor and E_peak being the `floor_quantile` and
     `peak_quantile` order statistics of the CLIP's own frame energies -- at least `above_floor_db` above the clip's quiet
     level, but no higher than `below_peak_db` below its loud level.  What webrtcvad.Vad(3) does for the reference (vad.py:90,152)

@@ -1,4 +1,4 @@
-"""The rule of include/svk_cluster.h in plain Python: sets, one float32 comparison per slot and a union-find by minimum.
+"""The rule of include/svk.h ("shared-neighbour (Jarvis-Patrick) clustering of k-NN lists") in plain Python: sets, one float32 comparison per slot and a union-find by minimum.
 Nothing from the package.  The GPU tests hold svk_knn_cluster to it exactly; tests/test_knn_cluster_host.py holds it to
 scipy's connected components."""
 import numpy as np

@@ -241,7 +241,7 @@ def keeps_prefill(arena, region, what):
 # sources and the directory listing against the three, so that a later entry point or source file cannot be left out silently.
 CONTRACT_SOURCES = ("scoring.hip", "search.hip", "plda.hip", "backend.hip", "pool.hip", "snorm.hip", "calibration.hip", "roc.hip",
                     "head.hip", "cluster.hip", "spectral.hip", "frontend.hip", "stages.hip", "vad.hip", "ingest.hip", "c3d2.hip",
-                    "c3d2_tail.hip", "context.hip", "comm.hip")
+                    "c3d2_tail.hip", "context.hip", "comm.hip", "knn_cluster.hip")
 CASES = {
     "svk_frontend_run": "test_memory_contract_frontend",
     "svk_preemphasis": "test_memory_contract_stages",
@@ -260,6 +260,7 @@ CASES = {
     "svk_cube_gather_delta": "test_memory_contract_stages",
     "svk_cube_draw_crops": "test_memory_contract_stages",
     "svk_vad_energy": "test_memory_contract_ingest",
+    "svk_vad_adaptive": "test_memory_contract_vad_adaptive",
     "svk_ingest_resample": "test_memory_contract_ingest",
     "svk_c3d2_stage1": "test_memory_contract_network",
     "svk_c3d2_stage1_c3": "test_memory_contract_network",
@@ -277,6 +278,7 @@ CASES = {
     "svk_plda_pair_scores": "test_memory_contract_scoring",
     "svk_plda_scores": "test_memory_contract_scoring",
     "svk_cosine_topk": "test_memory_contract_scoring",
+    "svk_cosine_topk_norm": "test_memory_contract_search_norm",
     "svk_class_scatter": "test_memory_contract_backend",
     "svk_embedding_project": "test_memory_contract_backend",
     "svk_embedding_pool": "test_memory_contract_backend",
@@ -286,6 +288,8 @@ CASES = {
     "svk_roc_dcf": "test_memory_contract_evaluation",
     "svk_decision_counts": "test_memory_contract_evaluation",
     "svk_top1": "test_memory_contract_evaluation",
+    "svk_rocch": "test_memory_contract_rocch",
+    "svk_pav_apply": "test_memory_contract_rocch",
     "svk_calibration_stats": "test_memory_contract_evaluation",
     "svk_calibration_apply": "test_memory_contract_evaluation",
     "svk_cohort_moments": "test_memory_contract_evaluation",
@@ -295,6 +299,7 @@ CASES = {
     "svk_segment_affinity": "test_memory_contract_diarization",
     "svk_ahc": "test_memory_contract_diarization",
     "svk_spectral_embed": "test_memory_contract_diarization",
+    "svk_knn_cluster": "test_memory_contract_cluster",
 }
 _SIZE_ONLY = "host arithmetic on its arguments: touches no device memory (the cases pass its value as the workspace's exact length)"
 _HOST_ONLY = "reads or writes host memory only: no device memory the caller owns"
@@ -335,6 +340,11 @@ EXEMPT = {
     "svk_calibration_stats_workspace_bytes": _SIZE_ONLY,
     "svk_ahc_workspace_bytes": _SIZE_ONLY,
     "svk_spectral_workspace_bytes": _SIZE_ONLY,
+    "svk_rocch_workspace_bytes": _SIZE_ONLY,
+    "svk_rocch_level_counts_offset": "host arithmetic on its argument (an offset into svk_rocch's workspace, for diagnostics): touches no device memory",
+    "svk_rocch_max_vertices": "host arithmetic on its argument: touches no device memory (the cases pass its value as the planes' capacity)",
+    "svk_cosine_topk_norm_workspace_bytes": _SIZE_ONLY,
+    "svk_knn_cluster_workspace_bytes": _SIZE_ONLY,
     "svk_ahc_limits": "writes two constants to a host array: no device memory",
     "svk_spectral_limits": "writes three constants to a host array: no device memory",
 }

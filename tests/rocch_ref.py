@@ -1,4 +1,4 @@
-"""The reference for the ROC convex hull (include/svk_rocch.h) in Python integers and Fractions, and the case list the GPU tests
+"""The reference for the ROC convex hull (include/svk.h, "the ROC convex hull") in Python integers and Fractions, and the case list the GPU tests
 run.  Nothing here imports the package: the chain, the pool-adjacent-violators pass and the derived values are restated from the
 header's definitions, so that tests/test_rocch*.py compare two independent statements of one object."""
 import math
@@ -45,7 +45,7 @@ def hull_chain(points, pop_collinear=True):
 
 
 def bridge(points, A, B, right_strict=False, bisect=True):
-    """The merge predicate of include/svk_rocch.h on two adjacent hulls given as index lists: every candidate u is tried, and
+    """The merge predicate of include/svk.h ("the ROC convex hull", merge levels) on two adjacent hulls given as index lists: every candidate u is tried, and
     exactly one must qualify.  v(u) is found as the kernel's hull_bridge_at finds it, by bisection -- which is right only if the
     predicate is monotone along B -- or (bisect=False) as the definition states it, by the first i from the left; the host test
     holds the two to each other.  right_strict=True is the mutant '> 0 in the bridge's right test'."""

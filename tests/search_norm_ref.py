@@ -1,4 +1,4 @@
-"""The reference of svk_cosine_topk_norm (include/svk_search_norm.h), built from the PLAIN entry's own bits so that the GPU
+"""The reference of svk_cosine_topk_norm (include/svk.h, "top-k search on normalised scores"), built from the PLAIN entry's own bits so that the GPU
 comparisons need no tolerance:
 
   raw_matrix   the full raw score matrix of a small problem, recovered by calling svk_cosine_topk over gallery chunks of at

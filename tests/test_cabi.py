@@ -19,19 +19,30 @@ def lib():
     return _lib.load()
 
 
-def _declared_symbols():
+def _header_code():
+    """include/svk.h without its comments"""
     text = open(os.path.join(REPO, "include", "svk.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(svk_[a-z0-9_]+)\s*\(", text)))
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
 
 
 def test_header_and_binding_agree(lib):
+    """The one header <-> binding table <-> library walk: every entry point is declared once in include/svk.h, bound in
+    _lib.SIGNATURES with the declaration's parameter count, exported by the built library and typed on the loaded one."""
     from speaker_verification_amd import _lib
-    declared = _declared_symbols()
-    assert len(declared) >= 25
-    assert sorted(_lib.SIGNATURES) == declared
-    for name in declared:
-        assert getattr(lib, name) is not None            # dlsym succeeds
+    assert os.listdir(os.path.join(REPO, "include")) == ["svk.h"]          # one header: a second one is a second boundary
+    code = _header_code()
+    declared = sorted(set(re.findall(r"\b(svk_[a-z0-9_]+)\s*\(", code)))
+    assert declared == sorted(_lib.SIGNATURES) and len(declared) == 97
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        decls = re.findall(r"\b%s\s*\((.*?)\)\s*;" % name, code, flags=re.S)
+        assert len(decls) == 1, name                                        # exactly one declaration `name ( ... ) ;`
+        params = decls[0].strip()
+        assert (0 if params in ("", "void") else len(params.split(","))) == len(argtypes), name
+        assert getattr(raw, name) is not None                               # dlsym succeeds on a raw handle
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    assert re.search(r"#define\s+SVK_KNN_CLUSTER_MUTUAL\s+%d\b" % _lib.KNN_CLUSTER_MUTUAL, code)
 
 
 def test_version_and_pure_host_entry_points(lib):

@@ -1,4 +1,4 @@
-"""svk_cosine_topk_norm (include/svk_search_norm.h) on the MI355X against tests/search_norm_ref.py, as bytes: the reference takes
+"""svk_cosine_topk_norm (include/svk.h, "top-k search on normalised scores") on the MI355X against tests/search_norm_ref.py, as bytes: the reference takes
 the raw scores from svk_cosine_topk's own lists, svk_score_norm's expression in NumPy float64 and the total order in pure
 Python, so no comparison here has a tolerance.  Shapes: one ragged tile on the hoisted instance; the streamed instance with
 4-byte loads, two row blocks and a ragged second tile; four spans and the merge; chunks accumulated in both orders with an

@@ -1,4 +1,4 @@
-"""svk_knn_cluster (include/svk_cluster.h) on hand-made k-NN lists: every output exactly equal to the plain-Python reference
+"""svk_knn_cluster (include/svk.h, "shared-neighbour (Jarvis-Patrick) clustering of k-NN lists") on hand-made k-NN lists: every output exactly equal to the plain-Python reference
 of tests/knn_cluster_ref.py, gave_up == 0 and two runs byte-identical in every case -- partial waves and workgroups, every k
 and list_stride path, the deepest union-find (a 5 000-row path from every direction), the threshold's edge cases, the
 shared-neighbour count at its boundary, every kind of bad slot, min_size, random lists in both modes, and the refusals."""

@@ -1,16 +1,13 @@
-"""Corpus clustering without a GPU: the header / binding / library walk for include/svk_cluster.h, the returns that need no
-device, the reference of tests/knn_cluster_ref.py against scipy's connected components, the host metrics on hand-made
-labelings, `clustering.segments` against `pipeline.speaker_segments`, and the separation the pipeline test's corpus relies on."""
-import ctypes
+"""Corpus clustering without a GPU: the names of the entries of include/svk.h's section "shared-neighbour (Jarvis-Patrick)
+clustering of k-NN lists" in the binding, the returns that need no device, the reference of tests/knn_cluster_ref.py against
+scipy's connected components, the host metrics on hand-made labelings, `clustering.segments` against
+`pipeline.speaker_segments`, and the separation the pipeline test's corpus relies on."""
 import os
-import re
 
 import numpy as np
 import pytest
 
 import knn_cluster_ref as R
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -22,34 +19,14 @@ def lib():
     return binding.load()
 
 
-def _stripped(header):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-
-
-def _declared(header):
-    return sorted(set(re.findall(r"\b(svk_[a-z0-9_]+)\s*\(", _stripped(header))))
-
-
-# ---- header <-> binding <-> library ------------------------------------------------------------------------------------
-def test_header_and_binding_agree(lib):
+# ---- the entries in the binding ----------------------------------------------------------------------------------------
+def test_the_two_entries_are_bound():
+    """(tests/test_cabi.py walks the header, the table and the library for every entry, and holds SVK_KNN_CLUSTER_MUTUAL to
+    the binding's value; this pins the names)"""
     from speaker_verification_amd import _lib as binding
-    declared = _declared("svk_cluster.h")
-    assert declared == sorted(binding.CLUSTER_SIGNATURES) == ["svk_knn_cluster", "svk_knn_cluster_workspace_bytes"]
-    others = set(binding.SIGNATURES) | set(binding.EXT_SIGNATURES) | set(binding.ROCCH_SIGNATURES) | set(binding.SEARCH_NORM_SIGNATURES)
-    for header in ("svk.h", "svk_vad.h", "svk_rocch.h", "svk_search_norm.h"):
-        others |= set(_declared(header))
-    assert not set(declared) & others
-    raw = ctypes.CDLL(binding.LIB_PATH)
-    text = _stripped("svk_cluster.h")
-    for name, (restype, argtypes) in binding.CLUSTER_SIGNATURES.items():
-        assert getattr(raw, name) is not None                   # dlsym succeeds
-        fn = getattr(lib, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes)
-        decl = re.search(r"\b%s\s*\((.*?)\)\s*;" % name, text, flags=re.S).group(1)
-        assert len(decl.split(",")) == len(argtypes), name      # the declaration's parameter count is the binding's
-    assert re.search(r"#define\s+SVK_KNN_CLUSTER_MUTUAL\s+%d\b" % binding.KNN_CLUSTER_MUTUAL, text)
-    import inspect
-    assert "svk_cluster.h" in inspect.getsource(binding.provenance)          # the header is part of the sources' hash
+    assert sorted(n for n in binding.SIGNATURES if n.startswith("svk_knn_cluster")) == [
+        "svk_knn_cluster", "svk_knn_cluster_workspace_bytes"]
+    assert binding.KNN_CLUSTER_MUTUAL == 1
 
 
 def test_refusals_need_no_device(lib):

@@ -1,5 +1,5 @@
-"""The memory contract of include/svk.h (Conventions) for the entry of include/svk_cluster.h, svk_knn_cluster
-(csrc/knn_cluster.h, included by csrc/cluster.hip): called directly on guarded arenas (tests/memory_contract.py) in the
+"""The memory contract of include/svk.h (Conventions) for the entry of its section "shared-neighbour (Jarvis-Patrick) clustering of k-NN lists", svk_knn_cluster
+(csrc/knn_cluster.hip): called directly on guarded arenas (tests/memory_contract.py) in the
 environments A, B and C, placed on 256-byte boundaries and one element past them (the alignment the header asks for and no
 more; the workspace 16 bytes past).  The lists are strided where list_stride > k: the slots behind k hold the payload pattern
 (0, -1 / NaN, another finite number) and are not read.  The guards stay intact, the inputs byte-identical, and the four

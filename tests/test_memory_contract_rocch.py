@@ -1,4 +1,4 @@
-"""The memory contract of include/svk.h (Conventions) for the entries of include/svk_rocch.h, svk_rocch and svk_pav_apply
+"""The memory contract of include/svk.h (Conventions) for the entries of its sections "the ROC convex hull" and "the PAV map", svk_rocch and svk_pav_apply
 (csrc/roc.hip, csrc/rocch.h): called directly on guarded arenas (tests/memory_contract.py) in the environments A, B and C,
 placed for the vector paths and for the scalar ones.  The guards stay intact, the inputs byte-identical, and the results are the
 same bits in all three environments and equal the Engine wrapper's on ordinary tensors -- so nothing in the workspace (the two

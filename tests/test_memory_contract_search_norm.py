@@ -1,4 +1,4 @@
-"""The memory contract of include/svk.h (Conventions) for the entry of include/svk_search_norm.h, svk_cosine_topk_norm
+"""The memory contract of include/svk.h (Conventions) for the entry of its section "top-k search on normalised scores", svk_cosine_topk_norm
 (csrc/search.hip): called directly on guarded arenas (tests/memory_contract.py) in the environments A, B and C, placed for the
 vector paths and for the scalar ones (the moment tables one float64 past a 256-byte boundary: the alignment the header asks
 for and no more).  The guards stay intact -- the tables are read in their [n][2] extent only, each flush against its trailing

@@ -1,4 +1,4 @@
-"""The memory contract of include/svk.h (Conventions) for svk_vad_adaptive (include/svk_vad.h, csrc/vad.hip), in the form of
+"""The memory contract of include/svk.h (Conventions) for svk_vad_adaptive ("level-adaptive energy VAD"; csrc/vad.hip), in the form of
 tests/test_memory_contract_ingest.py::test_vad_energy and on its batch: called directly on guarded arenas
 (tests/memory_contract.py) in the environments A, B and C, placed for the vector paths and for the scalar ones, on the
 short-clip kernel, the long-clip kernels and the general route, with every optional output present or NULL -- d_levels and

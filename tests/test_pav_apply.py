@@ -11,7 +11,7 @@ import rocch_ref as R                    # noqa: E402  (tests/ is on sys.path)
 pytestmark = pytest.mark.gpu
 
 SIZES = (1, 3, 4, 5, 4099)
-BINS = (1, 2, 33, 3177, 4096, 4097)      # 4 096 is the LDS table's bound (include/svk_rocch.h)
+BINS = (1, 2, 33, 3177, 4096, 4097)      # 4 096 is the LDS table's bound (include/svk.h, "the PAV map")
 # (floats past a 256-byte boundary of the scores, of the output); None: in place
 PLACED = {"aligned": (0, 0), "aligned-in-place": (0, None), "one-past": (1, 1), "one-past-in-place": (1, None),
           "scores-one-past": (1, 0), "two-and-three-past": (2, 3)}

@@ -1,17 +1,16 @@
 """The ROC convex hull without a GPU: the reference of tests/rocch_ref.py against an independent statement of the same object
 (pool adjacent violators), the device's merge predicate restated in Python against the chain, the teeth of the GPU case list
-(every mutant of the hull rule differs on some case), the vertex bound, the header / binding / library walk for
-include/svk_rocch.h, and PavCalibration's host logic through injected hull vertices.  All integers: every comparison is exact."""
+(every mutant of the hull rule differs on some case), the vertex bound, the names of the entries of include/svk.h's sections
+"the ROC convex hull" and "the PAV map" in the binding, the returns that need no device, and PavCalibration's host logic
+through injected hull vertices.  All integers: every comparison is exact."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
 import rocch_ref as R
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = list(R.gpu_cases())
 SMALL = [c for c in CASES if c != "n300000"]          # (what the mutants and the PAV tables run on: they die, or hold, earlier)
 
@@ -80,7 +79,7 @@ def test_every_mutant_of_the_rule_differs_on_some_case(mutant):
     assert caught, mutant
 
 
-# ---- header <-> binding <-> library ------------------------------------------------------------------------------------------
+# ---- the entries in the binding and the library ------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def lib():
     import __graft_entry__ as entry
@@ -90,29 +89,11 @@ def lib():
     return binding.load()
 
 
-def _stripped(header):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-
-
-def _declared(header):
-    return sorted(set(re.findall(r"\b(svk_[a-z0-9_]+)\s*\(", _stripped(header))))
-
-
-def test_header_and_binding_agree(lib):
+def test_the_five_entries_are_bound():
+    """(tests/test_cabi.py walks the header, the table and the library for every entry; this pins the names)"""
     from speaker_verification_amd import _lib as binding
-    declared = _declared("svk_rocch.h")
-    assert declared == sorted(binding.ROCCH_SIGNATURES) == ["svk_pav_apply", "svk_rocch", "svk_rocch_level_counts_offset",
-                                                            "svk_rocch_max_vertices", "svk_rocch_workspace_bytes"]
-    others = set(binding.SIGNATURES) | set(binding.EXT_SIGNATURES) | set(_declared("svk.h")) | set(_declared("svk_vad.h"))
-    assert not set(declared) & others
-    raw = ctypes.CDLL(binding.LIB_PATH)
-    text = _stripped("svk_rocch.h")
-    for name, (restype, argtypes) in binding.ROCCH_SIGNATURES.items():
-        assert getattr(raw, name) is not None                   # dlsym succeeds
-        fn = getattr(lib, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes)
-        decl = re.search(r"\b%s\s*\((.*?)\)\s*;" % name, text, flags=re.S).group(1)
-        assert len(decl.split(",")) == len(argtypes), name      # the declaration's parameter count is the binding's
+    assert sorted(n for n in binding.SIGNATURES if n.startswith(("svk_rocch", "svk_pav"))) == [
+        "svk_pav_apply", "svk_rocch", "svk_rocch_level_counts_offset", "svk_rocch_max_vertices", "svk_rocch_workspace_bytes"]
 
 
 def test_refusals_need_no_device(lib):

@@ -1,18 +1,16 @@
-"""The search on normalised scores without a GPU: the header / binding / library walk for include/svk_search_norm.h, the
-reference of tests/search_norm_ref.py against an independent brute-force statement of the total order, the staircase case's
+"""The search on normalised scores without a GPU: the binding of the entries of include/svk.h's section "top-k search on
+normalised scores" against the plain search's, the returns that need no device, the reference of tests/search_norm_ref.py
+against an independent brute-force statement of the total order, the staircase case's
 claim (equal and adjacent float32 normalised values, the k-th place decided in the last bit) established from the reference
 alone, and the span counts of the GPU shapes through svk_cosine_topk_norm_workspace_bytes."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
 import search_f64_ref as S
 import search_norm_ref as R
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -24,36 +22,15 @@ def lib():
     return binding.load()
 
 
-def _stripped(header):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-
-
-def _declared(header):
-    return sorted(set(re.findall(r"\b(svk_[a-z0-9_]+)\s*\(", _stripped(header))))
-
-
-# ---- header <-> binding <-> library ------------------------------------------------------------------------------------
-def test_header_and_binding_agree(lib):
+# ---- the entries in the binding ----------------------------------------------------------------------------------------
+def test_the_binding_is_the_plain_search_plus_two_tables():
+    """(tests/test_cabi.py walks the header, the table and the library for every entry; this pins what is these entries' own)"""
     from speaker_verification_amd import _lib as binding
-    declared = _declared("svk_search_norm.h")
-    assert declared == sorted(binding.SEARCH_NORM_SIGNATURES) == ["svk_cosine_topk_norm", "svk_cosine_topk_norm_workspace_bytes"]
-    others = set(binding.SIGNATURES) | set(binding.EXT_SIGNATURES) | set(binding.ROCCH_SIGNATURES)
-    for header in ("svk.h", "svk_vad.h", "svk_rocch.h"):
-        others |= set(_declared(header))
-    assert not set(declared) & others
-    raw = ctypes.CDLL(binding.LIB_PATH)
-    text = _stripped("svk_search_norm.h")
-    for name, (restype, argtypes) in binding.SEARCH_NORM_SIGNATURES.items():
-        assert getattr(raw, name) is not None                   # dlsym succeeds
-        fn = getattr(lib, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes)
-        decl = re.search(r"\b%s\s*\((.*?)\)\s*;" % name, text, flags=re.S).group(1)
-        assert len(decl.split(",")) == len(argtypes), name      # the declaration's parameter count is the binding's
+    assert sorted(n for n in binding.SIGNATURES if n.startswith("svk_cosine_topk_norm")) == [
+        "svk_cosine_topk_norm", "svk_cosine_topk_norm_workspace_bytes"]
     # the plain entry's parameters plus the two tables, in front of the workspace
-    plain, norm = binding.SIGNATURES["svk_cosine_topk"][1], binding.SEARCH_NORM_SIGNATURES["svk_cosine_topk_norm"][1]
+    plain, norm = binding.SIGNATURES["svk_cosine_topk"][1], binding.SIGNATURES["svk_cosine_topk_norm"][1]
     assert list(norm) == list(plain[:10]) + [ctypes.c_void_p, ctypes.c_void_p] + list(plain[10:])
-    import inspect
-    assert "svk_search_norm.h" in inspect.getsource(binding.provenance)      # the header is part of the sources' hash
 
 
 def test_refusals_need_no_device(lib):

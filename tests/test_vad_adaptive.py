@@ -1,4 +1,4 @@
-"""svk_vad_adaptive (include/svk_vad.h) against the Python-integer reference of tests/vad_adaptive_ref.py on every kernel route:
+"""svk_vad_adaptive (include/svk.h, "level-adaptive energy VAD") against the Python-integer reference of tests/vad_adaptive_ref.py on every kernel route:
 the short-clip kernel, the long-clip kernels (SVK_VAD_SPLIT=1 and clips beyond 512 frames) and the general route
 (SVK_VAD_SPLIT=2 and frame lengths that are no multiple of 8 or exceed 512).  Integer arithmetic: every comparison is exact.
 

@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE for tests/test_vad_adaptive*.py: the level-adaptive VAD rule of include/svk_vad.h restated in Python
+"""TEST INFRASTRUCTURE for tests/test_vad_adaptive*.py: the level-adaptive VAD rule of include/svk.h ("level-adaptive energy VAD") restated in Python
 integers, its mutants, and the case list the GPU tests run (the CPU tests hold the list to having teeth).
 
 The rule (all integers): nf whole frames, E_f = sum(x^2) of frame f; rank(q) = (q (nf - 1)) >> 16; E_lo, E_hi = the

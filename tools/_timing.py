@@ -45,10 +45,6 @@ def load_lib():
         lib = _lib.C.CDLL(_lib.LIB_PATH)
         _lib.VERSION = lib.svk_version()
         _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(lib, k)}
-        _lib.EXT_SIGNATURES = {k: v for k, v in _lib.EXT_SIGNATURES.items() if hasattr(lib, k)}
-        _lib.ROCCH_SIGNATURES = {k: v for k, v in _lib.ROCCH_SIGNATURES.items() if hasattr(lib, k)}
-        _lib.SEARCH_NORM_SIGNATURES = {k: v for k, v in _lib.SEARCH_NORM_SIGNATURES.items() if hasattr(lib, k)}
-        _lib.CLUSTER_SIGNATURES = {k: v for k, v in _lib.CLUSTER_SIGNATURES.items() if hasattr(lib, k)}
     return _lib, _lib.load()
 
 

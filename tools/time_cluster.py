@@ -1,4 +1,4 @@
-"""HIP-event medians of svk_knn_cluster (include/svk_cluster.h: k-NN lists -> shared-neighbour components -> labels) on a
+"""HIP-event medians of svk_knn_cluster (include/svk.h "shared-neighbour (Jarvis-Patrick) clustering of k-NN lists": k-NN lists -> shared-neighbour components -> labels) on a
 synthetic corpus of the development set's size: --rows 148 642 embeddings of --speakers 1 211 (a random unit centre per
 speaker + --noise N(0, I), rows in shuffled order), k = 10 and k = 32, mutual arcs at --threshold with --min-shared common
 neighbours.  Per k, ALTERNATED call by call in the same process:

@@ -1,4 +1,4 @@
-"""HIP-event medians of the ROC convex hull and the PAV map (include/svk_rocch.h), 20 calls each, alternated call by call:
+"""HIP-event medians of the ROC convex hull and the PAV map (include/svk.h: "the ROC convex hull", "the PAV map"), 20 calls each, alternated call by call:
 
   svk_rocch against svk_roc_dcf on the same buffers at 148 642 x 1 211 = 1.8e8 trials (cosine scores of seeded unit-norm
   embeddings, as tools/time_roc.py) and at the 581 480 trials of VoxCeleb1-E (seeded N(0, 1) + 2 label scores): the difference

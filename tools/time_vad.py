@@ -1,4 +1,4 @@
-"""HIP-event medians of svk_vad_adaptive (include/svk_vad.h) ALTERNATED call by call with svk_vad_energy on the same device
+"""HIP-event medians of svk_vad_adaptive (include/svk.h, "level-adaptive energy VAD") ALTERNATED call by call with svk_vad_energy on the same device
 buffers, called through the C-ABI on outputs allocated once:
   * "short_index" / "short_copy": --clips (16 384) clips of 3 s, the benchmark's shape (99 frames of 480 samples: the one-kernel
     route of both entries), in the index form (nothing copied) and in the copying form;
