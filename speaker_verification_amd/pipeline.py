@@ -925,6 +925,31 @@ class VerificationPipeline:
         return Clustering(*self.eng.knn_cluster(scores, indices, threshold=threshold, min_shared=min_shared, mutual=mutual,
                                                 min_size=min_size))
 
+    def _raw_cosine_rows(self, what, emb):
+        """The rows as `cluster` searched them (through the back end), for the calls that go on from its labels; they raise
+        where `cluster` does, in its words."""
+        if self.plda is not None:
+            raise ValueError("%s ranks by cosine score: top-k by PLDA log-likelihood ratio is not built (use score)" % what)
+        if self.calibration is not None:
+            raise ValueError("%s ranks by raw cosine score: calibrated top-k is `identify` (or use score)" % what)
+        if self.score_norm is not None:
+            raise ValueError("%s ranks by raw cosine score: top-k on normalised scores is `identify` (or use score)" % what)
+        return self.project(self.eng.to_device(emb, torch.float32))
+
+    def merge_clusters(self, emb, labels, **kw):
+        """The second stage after `cluster` when k fragments a speaker: `clustering.merge_clusters` (which lists the
+        keywords; `threshold` and `k` have no default) on the rows as `cluster` saw them -- projected through the back end
+        first -> `clustering.Merged`.  Raises with a PLDA, a score normalisation or a calibration, as `cluster` does."""
+        from .clustering import merge_clusters
+        return merge_clusters(self.eng, self._raw_cosine_rows("merge_clusters", emb), labels, **kw)
+
+    def adopt_rows(self, emb, labels, **kw):
+        """The rows `cluster`'s min_size left at -1 join the nearest cluster centroid at `threshold` or above:
+        `clustering.adopt_rows` on the rows as `cluster` saw them (projected first) -> `clustering.Adopted`.  Raises with a
+        PLDA, a score normalisation or a calibration, as `cluster` does."""
+        from .clustering import adopt_rows
+        return adopt_rows(self.eng, self._raw_cosine_rows("adopt_rows", emb), labels, **kw)
+
     def diarize(self, pcm, **kw):
         """"Who spoke when": int16 PCM [n_rec, samples] of recordings with several speakers -> one list of
         `diarization.Turn(start_s, end_s, speaker)` per recording (`diarization.Diarizer.diarize`, which lists the keywords:

@@ -49,10 +49,14 @@ def load_lib():
 
 
 def header(_lib, lib, sha=True, **fields):
-    """Starts the result line: the library's path, version and (sha) source digest, then the tool's own fields -- among them
+    """Starts the result line: the library's path (relative to the repository; the file name alone for a library outside
+    it), version and (sha) source digest, then the tool's own fields -- among them
     the empty dicts (ms, spread_ms, bytes, tb_s, flop, tf_s, ...) that `put` is to fill."""
     _res.clear()
-    _res.update(lib=_lib.LIB_PATH, version=int(lib.svk_version()))
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    path = os.path.abspath(_lib.LIB_PATH)           # inside the repository: relative to it, so that a filed line names no machine
+    _res.update(lib=os.path.relpath(path, repo) if path.startswith(repo + os.sep) else os.path.basename(path),
+                version=int(lib.svk_version()))
     if sha:
         _res["csrc_sha"] = _lib.provenance()["csrc_sha"]
     _res.update(fields)
