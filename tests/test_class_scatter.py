@@ -18,8 +18,9 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from backend_f64_ref import rows, scatter_ref       # noqa: E402  (tests/ is on sys.path)
+
 LENGTHS = [1, 2, 7, 0, 300, 65]
-U = 2.0 ** -53
 
 
 @pytest.fixture(scope="module")
@@ -32,35 +33,6 @@ def eng():
 def C_off(t, nbytes):
     """the tensor's address moved by nbytes: a misaligned pointer"""
     return ctypes.c_void_p(t.data_ptr() + nbytes)
-
-
-def rows(n, dim, seed):
-    return (np.random.default_rng(seed).standard_normal((n, dim)) + 3.0).astype(np.float32)
-
-
-def scatter_ref(x, groups, flags):
-    """np.longdouble restatement -> (means, sw, bound of the means, bound of sw)."""
-    v = x.astype(np.longdouble)
-    if flags & 1:
-        nrm = np.sqrt((v * v).sum(1, keepdims=True))
-        with np.errstate(invalid="ignore", divide="ignore"):
-            v = np.where(nrm == 0, np.longdouble(0), v / nrm)
-    dim = x.shape[1]
-    means = np.zeros((len(groups), dim), dtype=np.longdouble)
-    mean_bound = np.zeros((len(groups), dim))
-    sw = np.zeros((dim, dim), dtype=np.longdouble)
-    mag = np.zeros((dim, dim), dtype=np.longdouble)
-    n_max = max(len(g) for g in groups)
-    for c, g in enumerate(groups):
-        if len(g) == 0:
-            continue
-        means[c] = v[g].sum(0) / len(g)
-        mean_bound[c] = (len(g) + 2) * U * np.abs(v[g]).mean(0).astype(np.float64)
-        d = v[g] - means[c]
-        sw += d.T @ d
-        a = np.abs(v[g]) + np.abs(means[c])
-        mag += a.T @ a
-    return means, sw, mean_bound, (2 * n_max + 8) * U * mag.astype(np.float64)
 
 
 def check(got_mean, got_sw, ref, what):

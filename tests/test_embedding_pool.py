@@ -14,6 +14,8 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from backend_f64_ref import assert_f32_or_neighbour, pool_ref, rows       # noqa: E402  (tests/ is on sys.path)
+
 LENGTHS = [1, 2, 7, 0, 300]
 
 
@@ -22,40 +24,6 @@ def eng():
     from speaker_verification_amd.engine import get_engine
     assert torch.cuda.is_available(), "these tests need the MI355X"
     return get_engine(0)
-
-
-def pool_ref(x, groups, flags):
-    """float64 restatement: groups = a list of row-index arrays."""
-    x = x.astype(np.float64)
-    out = np.zeros((len(groups), x.shape[1]))
-    for s, rows in enumerate(groups):
-        if len(rows) == 0:
-            continue
-        v = x[rows]
-        if flags & 1:
-            nrm = np.sqrt((v * v).sum(1, keepdims=True))
-            with np.errstate(invalid="ignore", divide="ignore"):
-                v = np.where(nrm == 0, 0.0, v / nrm)
-        m = v.sum(0) / len(rows)
-        if flags & 2:
-            nrm = np.sqrt((m * m).sum())
-            m = m if nrm == 0 else m / nrm
-        out[s] = m
-    return out
-
-
-def assert_f32_or_neighbour(got, ref64, what):
-    want = ref64.astype(np.float32)
-    ok = (got == want) | (got == np.nextafter(want, np.float32(np.inf))) | (got == np.nextafter(want, np.float32(-np.inf)))
-    ok |= np.isnan(got) & np.isnan(want)
-    exact = float((got == want).mean())
-    print("%s: %d values, %.4f equal float32(ref64), worst |got - ref64| / ulp = %.3f"
-          % (what, got.size, exact, float(np.nanmax(np.abs(got.astype(np.float64) - ref64) / np.maximum(np.spacing(np.abs(want)), 1e-45)))))
-    assert ok.all(), "%s: %d values are neither float32(ref64) nor its neighbour" % (what, int((~ok).sum()))
-
-
-def rows(n, dim, seed):
-    return (np.random.default_rng(seed).standard_normal((n, dim)) + 3.0).astype(np.float32)
 
 
 @pytest.mark.parametrize("dim", [128, 40])

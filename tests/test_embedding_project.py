@@ -18,6 +18,8 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from backend_f64_ref import assert_f32_or_neighbour, l2_f32, project_ref, rows, unit_rows       # noqa: E402  (tests/ is on sys.path)
+
 N_ROWS = (1, 15, 16, 17, 300)
 # the issue's five shapes, then one for each tile-count instance they do not reach: 2 tiles (40, 20), 16 (300, 200), 32 (512, 300)
 SHAPES = [(128, 128), (128, 50), (128, 1), (40, 13), (130, 7), (40, 20), (300, 200), (512, 300)]
@@ -28,40 +30,6 @@ def eng():
     from speaker_verification_amd.engine import get_engine
     assert torch.cuda.is_available(), "these tests need the MI355X"
     return get_engine(0)
-
-
-def rows(n, dim, seed):
-    return (np.random.default_rng(seed).standard_normal((n, dim)) + 3.0).astype(np.float32)
-
-
-def l2_f32(x):
-    """x' = float32(x / ||x||), norm and division in float64; a zero row stays zero."""
-    x64 = x.astype(np.float64)
-    nrm = np.sqrt((x64 * x64).sum(1, keepdims=True))
-    with np.errstate(invalid="ignore", divide="ignore"):
-        return np.where(nrm == 0, 0.0, x64 / nrm).astype(np.float32)
-
-
-def project_ref(x, mu, w, flags):
-    """float64 restatement of the un-normalised output -> (y, bound)."""
-    dim = x.shape[1]
-    xp = (l2_f32(x) if flags & 1 else x).astype(np.float64)
-    mu64 = np.zeros(dim) if mu is None else mu.astype(np.float64)
-    w64 = w.astype(np.float64)
-    return (xp - mu64) @ w64, (dim + 8) * 2.0 ** -24 * ((np.abs(xp) + np.abs(mu64)) @ np.abs(w64))
-
-
-def assert_f32_or_neighbour(got, ref64, what):
-    want = ref64.astype(np.float32)
-    ok = (got == want) | (got == np.nextafter(want, np.float32(np.inf))) | (got == np.nextafter(want, np.float32(-np.inf)))
-    ok |= np.isnan(got) & np.isnan(want)
-    assert ok.all(), "%s: %d values are neither float32(ref64) nor its neighbour" % (what, int((~ok).sum()))
-
-
-def unit_rows(y):
-    y64 = y.astype(np.float64)
-    nrm = np.sqrt((y64 * y64).sum(1, keepdims=True))
-    return y64 / np.where(nrm == 0, 1.0, nrm)
 
 
 @pytest.mark.parametrize("dim,out_dim", SHAPES)
